@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- attention TFLOPS of the gfx950 SageAttention hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5|...] [--no-configs] [--no-sweep] [--sweep]
-                    [--no-cpu-baseline] [--replay] [--dry-run-ranks N]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5|...] [--dump-outputs DIR]
+                    [--full [--no-configs] [--no-sweep] [--no-cpu-baseline]] [--sweep] [--replay] [--dry-run-ranks N]
 
 Workload of the headline line (default `c3` = BASELINE.json configs[2], the configuration the north-star target is quoted on):
 B=2, H=32, N=8192, D=128, causal, INT8 QK^T + FP8 PV with two-level FP32 accumulation.  FLOPs = 4*B*H*N*N*D / 2 (causal) -- the
@@ -10,10 +10,17 @@ reference's formula (bench/bench_qk_int8_pv_fp8_cuda_sm90.py:34).
 
 A "step" is one launch of the fused attention kernel on pre-quantised operands resident in HBM (exactly what the reference's bench
 scripts time and what its published TOPS mean: "attention kernel only, excluding quantization and smoothing", README.md:174).
-`value` is that kernel-only throughput.  The same run also times the whole `sageattn()` call (K mean + Q/K INT8 quantisation + V FP8
-pre-pass + attention) and reports it under "end_to_end", plus accuracy vs fp32 SDPA under "accuracy".
+`value` is that kernel-only throughput, `ms_per_step` the wall time of one of the K timed steps.  A plain run does only that: inputs,
+pre-quantisation, clock ramp, W warm-up steps, K timed steps, the result line (with the `roofline` of the same timed launches).
 
-The default single-GPU run appends, under "configs", every other BASELINE.json configuration, each with its own `roofline` object
+--dump-outputs DIR: after the timed steps, what the last step returned (the attention output `o`) is written as DIR/o.npy in float32 --
+a fixed sample of its rows if it is larger than DUMP_BYTES (`dump_outputs`).  The inputs come from fixed seeds, so two builds run with the
+same arguments can be compared output for output.
+
+--full adds everything else, each part measured in runs of its own after the headline: the whole `sageattn()` call (K mean + Q/K INT8
+quantisation + V FP8 pre-pass + attention) under "end_to_end", the opt-in folded score variant, accuracy vs fp32 SDPA under "accuracy",
+the CPU baseline, the N = 1k..32k sweeps (`--sweep` asks for them outside --full too), and for the single-GPU c3 run, under "configs",
+every other BASELINE.json configuration, each with its own `roofline` object
 (HIP events around the attention launch on the launch stream; peaks as for the headline):
   c2   qk_int8_pv_fp16 B=2 H=32 N=4096 D=128 causal: kernel-only + whole call; and the Triton-named API
        (sageattn_qk_int8_pv_fp16_triton, bench/bench_qk_int8_pv_fp16_triton.py) at the same shape: whole call + its attention kernel
@@ -298,6 +305,27 @@ def timed(fn, steps, warmup, dist_on, ramp_s=0.0):
     return wall, dev_ms
 
 
+DUMP_BYTES = 32 << 20          # per array written by --dump-outputs (at most 64 MB in all)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as <out_dir>/<name>.npy in float32.  A tensor of more than DUMP_BYTES
+    (as float32) is written as a sample of its rows (last axis whole): the sorted row indices numpy.random.default_rng(0) draws without
+    replacement, the same rows in every run of the same shape."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        rows = t.reshape(-1, t.shape[-1])
+        n = max(1, DUMP_BYTES // (4 * rows.shape[1]))
+        if rows.shape[0] > n:
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], n, replace=False))
+            rows = rows[torch.from_numpy(idx).to(rows.device)]
+            arr = rows.float().cpu().numpy()
+        else:
+            arr = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def _median(xs):
     """Median launch duration of a sweep point (20 launches): one stray multi-millisecond launch -- seen once in this round's runs, N = 4096
     at 224 instead of ~1400 TFLOP/s by the mean -- must not decide a point of the curve.  The headline and the `roofline` objects keep the
@@ -518,7 +546,7 @@ def replay(cfg, q, k, v, layers, steps, dist_on=False):
 
 
 def other_configs(args, device):
-    """The `configs` block of the default line: every BASELINE.json configuration besides the headline's, and the reference bench
+    """The `configs` block of the --full line: every BASELINE.json configuration besides the headline's, and the reference bench
     script's own sweep shape."""
     ramp = min(args.ramp_seconds, 0.2)
     steps, warmup = max(10, args.steps // 2), max(5, args.warmup // 2)
@@ -585,6 +613,8 @@ def run_replay(args, cfg, device, rank, world, dist_on):
     q, k, v, (lo, hi) = rank_inputs(cfg, device, 4321, rank, world, weak=False)
     calls = args.replay_layers * args.replay_steps
     wall, per_step, o = replay(cfg, q, k, v, args.replay_layers, args.replay_steps, dist_on)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"o": o})
     stats = torch.tensor([wall], dtype=torch.float64, device=device)
     if dist_on:
         dist.all_reduce(stats, op=dist.ReduceOp.MAX)
@@ -685,9 +715,13 @@ def main():
     ap.add_argument("--ramp-seconds", type=float, default=0.3,
                     help="untimed clock-ramp phase before the warmup steps (0 disables); reported in the JSON")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS) + ["c4"])
-    ap.add_argument("--sweep", action="store_true", help="also batch 4 (per-thread scales) in the N=1k..32k kernel-only sweep")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the N=1k..32k kernel-only sweep that the default c3 run appends (BASELINE.json's metric)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (c2, c4, c5, the reference bench script's sweep) of the default c3 run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32; a fixed row sample of a large output)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the whole call, folded variant, accuracy, CPU baseline, sweeps and (c3, 1 GPU) every other configuration")
+    ap.add_argument("--sweep", action="store_true", help="run the N=1k..32k kernel-only sweep (also without --full), with batch 4 (per-thread scales) added")
+    ap.add_argument("--no-sweep", action="store_true", help="skip the N=1k..32k kernel-only sweep that the --full c3 run appends (BASELINE.json's metric)")
+    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (c2, c4, c5, the reference bench script's sweep) of the --full c3 run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--replay", action="store_true", help="drop-in replay of the model's attention calls (use with --config c5)")
     ap.add_argument("--replay-layers", type=int, default=42)
@@ -695,6 +729,8 @@ def main():
     ap.add_argument("--dry-run-ranks", type=int, default=0, help="walk the N-rank split of the configuration on the host (no GPU) and print it")
     ap.add_argument("--dist-check", action="store_true", help="run the distributed bookkeeping of a --gpus N launch on CPU ranks over gloo (no GPU, no kernels)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config == "c4":
+        ap.error("--dump-outputs covers the dense configurations and --replay, not --config c4")
 
     if args.dry_run_ranks:
         cfg = CONFIGS[args.config if args.config != "c4" else "c3"]
@@ -743,10 +779,20 @@ def main():
     ops = prequantize(cfg, q, k, v)
     torch.cuda.synchronize()
 
-    wall_k, dev_k = timed(lambda: kernel_only_step(cfg, ops, sm_scale), args.steps, args.warmup, dist_on, args.ramp_seconds)
-    wall_e, dev_e = timed(lambda: e2e_step(cfg, q, k, v), max(3, args.steps // 2), 2, dist_on, args.ramp_seconds)
-    e2e_steps = max(3, args.steps // 2)
-    prepass = prepass_roofline(cfg, k, v, args.config, between=lambda: kernel_only_step(cfg, ops, sm_scale))
+    last = [None]                                         # what the last timed step returned (--dump-outputs)
+
+    def step():
+        last[0] = kernel_only_step(cfg, ops, sm_scale)
+
+    wall_k, dev_k = timed(step, args.steps, args.warmup, dist_on, args.ramp_seconds)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"o": last[0]})
+    last[0] = None
+    wall_e = 0.0
+    if args.full:
+        e2e_steps = max(3, args.steps // 2)
+        wall_e, _ = timed(lambda: e2e_step(cfg, q, k, v), e2e_steps, 2, dist_on, args.ramp_seconds)
+        prepass = prepass_roofline(cfg, k, v, args.config, between=lambda: kernel_only_step(cfg, ops, sm_scale))
 
     stats = torch.tensor([wall_k, wall_e], dtype=torch.float64, device=device)
     per_rank_ms = None
@@ -773,25 +819,27 @@ def main():
         "config": {"workload": cfg["workload"], "global_batch": cfg["B_global"] * world, "heads": CONFIGS[args.config]["H"], "seq_len": cfg["N"],
                    "head_dim": cfg["D"], "parallelism": f"batch*head shard x{world} (shard.shard_range units of the global batch), no collective"},
         "roofline": roofline_obj(fl, kern_ms, cfg["pv"], "sage_attn_kernel", args.config),
-        "end_to_end": {"ms_per_call": round(wall_e / e2e_steps * 1e3, 4),
-                       "tflops": round(fl * world / (wall_e / e2e_steps) / 1e12, 2),
-                       "what": "sageattn(): K mean + INT8 Q/K quant + V pre-pass + attention",
-                       "prepass": prepass},
     }
-    if cfg["pv"] == "fp8" and world == 1:
+    if args.full:
+        out["end_to_end"] = {"ms_per_call": round(wall_e / e2e_steps * 1e3, 4),
+                             "tflops": round(fl * world / (wall_e / e2e_steps) / 1e12, 2),
+                             "what": "sageattn(): K mean + INT8 Q/K quant + V pre-pass + attention",
+                             "prepass": prepass}
+    if args.full and cfg["pv"] == "fp8" and world == 1:
         out["fp8_folded_variant"] = folded_variant(cfg, ops, fl, max(10, args.steps // 2), 5, min(args.ramp_seconds, 0.2))
     if ranks_seen is not None:
         out["ranks_seen"] = ranks_seen
         out["ms_per_step_per_rank"] = per_rank_ms
     if rank == 0:
-        try:
-            out["accuracy"] = accuracy(cfg, q, k, v)
-        except Exception as e:   # accuracy is informational here; the gate is tests/ -m gpu
-            out["accuracy"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            try:
+                out["accuracy"] = accuracy(cfg, q, k, v)
+            except Exception as e:   # accuracy is informational here; the gate is tests/ -m gpu
+                out["accuracy"] = {"error": repr(e)}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
-        if (args.sweep or (args.config == "c3" and world == 1)) and not args.no_sweep:
-            # BASELINE.json's metric is the whole curve "hd=128 causal at N=1k..32k", so the default run carries it: kernel-only,
+        if (args.sweep or (args.full and args.config == "c3" and world == 1)) and not args.no_sweep:
+            # BASELINE.json's metric is the whole curve "hd=128 causal at N=1k..32k", so the --full run carries it: kernel-only,
             # the config's batch (2); --sweep adds batch 4 with the same per-thread scales (the reference bench script's own
             # per-warp batch-4 sweep is in the `configs` block)
             batches = [("sweep_kernel_only_tflops", cfg["B_global"])] + ([("sweep_kernel_only_tflops_batch4", 4)] if args.sweep else [])
@@ -831,7 +879,7 @@ def main():
                                          "Cache is 256 MB): median of 12 single launches each, every launch timed on its own behind the flush")
             out["sweep_note"] = ("kernel-only TFLOP/s of the workload's kernel at N = 1k .. 32k (B=%d, H=%d, D=%d, %s): median of 20 launches each, HIP events"
                                  % (cfg["B_global"], CONFIGS[args.config]["H"], cfg["D"], "causal" if cfg["causal"] else "non-causal"))
-        if args.config == "c3" and world == 1 and not args.no_configs:
+        if args.full and args.config == "c3" and world == 1 and not args.no_configs:
             del q, k, v, ops
             torch.cuda.empty_cache()
             try:

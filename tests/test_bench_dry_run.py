@@ -61,6 +61,22 @@ def test_dry_run_command_line():
     assert d["world"] == 8 and d["scaling"] == "strong" and [r["units"][1] - r["units"][0] for r in d["ranks"]] == [12] * 8
 
 
+def test_dump_outputs_writes_float32_and_a_fixed_row_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a small output whole, a large one as the same sample of its rows in every run, float32, within the byte budget."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 * 16 * 4)
+    small = torch.randn(2, 3, 8, 16).half()
+    big = torch.randn(1, 4, 100, 16).to(torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s, a, b = (np.load(tmp_path / d / f) for d, f in (("a", "small.npy"), ("a", "big.npy"), ("b", "big.npy")))
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
+    assert a.dtype == np.float32 and a.shape == (64, 16) and a.nbytes <= bench.DUMP_BYTES and np.array_equal(a, b)
+    rows = big.float().reshape(-1, 16).numpy()
+    hit = [np.flatnonzero((rows == r).all(axis=1)) for r in a]
+    assert all(len(h) == 1 for h in hit) and len({int(h[0]) for h in hit}) == 64      # distinct rows of the output, unchanged
+
+
 def test_rank_records_are_checked():
     """`ranks_seen` of a --gpus N run: every rank present once, and over RCCL one distinct device per rank."""
     recs = [dict(rank=r, local_rank=r, device=r, device_count=8, name="MI355X", pci_bus_id=None, uuid=f"GPU-{r:02d}", pid=100 + r) for r in range(8)]

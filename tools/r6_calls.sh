@@ -10,7 +10,7 @@ call1() {   # exact-by-default build + lazy FP16 reference: the GPU suite, A/B o
   timeout 1700 python -m pytest tests -m gpu -q -x > $out/pytest.log 2>&1; echo "pytest rc $?" | tee -a $out/pytest.log; filter < $out/pytest.log | tail -8
   cp gpurun_out/parity_report.json $out/ 2>/dev/null
   for t in c2 c2t c4 c4nc; do SAGE_AB_ALLOW_DIFF=1 timeout 300 python tools/lib_ab.py $t main nolazy r5 2>&1 | filter | tee -a $out/fp16_lazy_ab.txt; done
-  timeout 600 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc $?"; tail -2 $out/bench.err; cut -c1-1800 $out/bench.json
+  timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc $?"; tail -2 $out/bench.err; cut -c1-1800 $out/bench.json
 }
 
 call2() {   # the whole GPU suite (no -x), 100 seeds
@@ -43,7 +43,7 @@ call6() {   # full suite at the commit + PMC passes per configuration + bench li
   timeout 2400 python -m pytest tests -m gpu -q > $out/pytest.log 2>&1; echo "pytest rc $?" | tee -a $out/pytest.log; filter < $out/pytest.log | tail -6
   cp gpurun_out/parity_report.json $out/ 2>/dev/null
   timeout 1500 python tools/pmc_collect.py r6f c3 c3f c2 c2r c2t c4 c4nc c5 c5f pp 2>&1 | filter | tee $out/pmc_summary.txt
-  timeout 600 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc $?"; tail -2 $out/bench.err; cut -c1-600 $out/bench.json
+  timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc $?"; tail -2 $out/bench.err; cut -c1-600 $out/bench.json
 }
 
 call7() {   # stress: the seeded sweeps with 400 seeds each (the suite draws 100), both FP8 score forms as the process default
