@@ -31,7 +31,13 @@
 extern "C" {
 #endif
 
-#define SAGE_ABI_VERSION 21
+#define SAGE_ABI_VERSION 22
+/* Changes (newest first):
+ *   22  FP8 PV for packed (varlen) batches: sage_prep_v_fp8_varlen (+ _ws_floats), sage_attn_qk_int8_pv_f8_varlen,
+ *       sage_attn_fused_qblock_pv_f8_varlen.  Nothing else changed.
+ *   21  sage_attn_qk_int8_pv_f16_vrows (INT8 q / k, V read in place).
+ *   20  the exact FP8 score form is the default; SageLaunchAttr.struct_bytes = 0 is refused; launch workspaces re-arm themselves;
+ *       sage_attn_fused_q*_pv_f16_vrows. */
 
 #if defined(__GNUC__)
 #define SAGE_API __attribute__((visibility("default")))
@@ -270,13 +276,29 @@ SAGE_API int sage_prep_v_f16_varlen(const void *v, void *v_image, const int32_t 
                            const int32_t *cu_tiles, int nseq, int max_seqlen, int H, int D,
                            int64_t v_sl, int64_t v_sh, int dtype, void *stream);
 
+/* FP8 V pre-pass of a PACKED batch, v [sum L, H, D] (ABI 22): one e4m3 scale per (sequence, head, channel), amax / scale_max over that
+ * sequence's tokens alone (what sage_prep_v_fp8 computes for one sequence; an outlier token costs no other sequence its precision; an empty
+ * sequence gets 0), and the e4m3 tile image [cu_tiles[nseq], H, D, 64] bytes in sage_prep_v_fp8's tile layout, ordered [tile, head] as
+ * sage_prep_v_f16_varlen's, the tail of a sequence's last tile zero.  cu_tiles = prefix sums of ceil(L_i / 64) (the k scale prefix).
+ * v_scale [nseq, H, D] fp32.  Statistics: with the slab map of sage_varlen_plan (slab_first / slab_seq / hdr together, nslab_bound = its
+ * host-known bound) the 512-token slabs of sage_channel_mean_varlen, else (all three NULL, nslab_bound = 0: more sequences than the plan
+ * takes) ceil(max_seqlen / 512) slabs per sequence; max and min do not depend on the partition, so both give the same bits.
+ * ws: sage_prep_v_fp8_varlen_ws_floats(nseq, H, max_seqlen, nslab_bound, D) floats.  total_tokens = rows of v.  scale_max = 448.
+ * Replaces: nothing in the reference, whose varlen path has FP16 PV only (core.py:334-448). */
+SAGE_API int64_t sage_prep_v_fp8_varlen_ws_floats(int nseq, int H, int max_seqlen, int nslab_bound, int D);
+SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale, float *ws, const int32_t *cu_seqlens, const int32_t *cu_tiles,
+                                    const int32_t *slab_first, const int32_t *slab_seq, const int32_t *hdr,
+                                    int nseq, int total_tokens, int max_seqlen, int nslab_bound, int H, int D, int64_t v_sl, int64_t v_sh,
+                                    float scale_max, int dtype, void *stream);
+
 /*
  * Launch attributes of the attention entry points below: every sage_attn_* function takes a trailing `const SageLaunchAttr *attr`
  * (NULL = all defaults).  The attributes are ARGUMENTS of the call they travel with -- the library keeps nothing between calls (ABI 18's
  * thread-local sage_attn_launch_ws setter is gone).  The reference has no counterpart: its kernels leave the order of their thread blocks
  * to the hardware (qk_int_sv_f8_cuda_sm89.cuh:720-738) and have one score form.  Results do not depend on launch_ws / flags bit 1.
  *
- *  struct_bytes     sizeof(SageLaunchAttr) as the caller compiled it (fields past it read as zero; 0 is taken as the full struct)
+ *  struct_bytes     sizeof(SageLaunchAttr) as the caller compiled it (fields past it read as zero); at least the 8-byte header -- 0 is refused
+ *                   (SAGE_EINVAL) since ABI 20
  *  flags            SAGE_ATTR_* below
  *  launch_ws        nullable: sage_attn_launch_ws_bytes() bytes of device memory, 128-byte aligned, ZERO when this launch starts (zeroed by the
  *                   caller in stream order before its first use) and untouched by anyone else until the launch has finished.  A launch that
@@ -397,6 +419,17 @@ SAGE_API int sage_attn_qk_int8_pv_f16_varlen(const int8_t *q, const int8_t *k, c
                                     int64_t o_sl, int64_t o_sh,
                                     int is_causal, float sm_scale_log2, int pv_accum, int out_dtype,
                                     void *stream, const SageLaunchAttr *attr);
+/* The FP8-PV counterpart (ABI 22): v_image / v_scale [nseq, Hkv, D] from sage_prep_v_fp8_varlen, pv_accum SAGE_PV_ACCUM_TWO_LEVEL or
+ * _SINGLE, the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES is refused).  lse nullable: fp32 [Hq, lse_sh] in log2 units, row
+ * cu_seqlens_q[i] + r of head h at h * lse_sh + cu_seqlens_q[i] + r (lse_sh >= cu_seqlens_q[nseq]). */
+SAGE_API int sage_attn_qk_int8_pv_f8_varlen(const int8_t *q, const int8_t *k, const void *v_image, void *o, float *lse,
+                                            const float *q_scale, const float *k_scale, const float *v_scale,
+                                            const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k,
+                                            const int32_t *cu_q_scale, const int32_t *cu_k_scale, const int32_t *seq_order,
+                                            const int32_t *work_items, const int32_t *work_hdr, int items_bound,
+                                            int nseq, int max_seqlen_q, int Hq, int Hkv, int D,
+                                            int64_t q_sl, int64_t q_sh, int64_t k_sl, int64_t k_sh, int64_t o_sl, int64_t o_sh, int64_t lse_sh,
+                                            int is_causal, float sm_scale_log2, int pv_accum, int out_dtype, void *stream, const SageLaunchAttr *attr);
 
 /* FP8-PV attention (two-level accumulation, "per-thread" granularity) with the Q quantisation fused into the kernel:
  * q is the fp16 / bf16 query tensor itself (element strides); each workgroup quantises its 128 rows in registers with
@@ -477,6 +510,17 @@ SAGE_API int sage_attn_fused_qblock_pv_f16_varlen(const void *q, const int8_t *k
                                                   int nseq, int max_seqlen_q, int Hq, int Hkv, int D,
                                                   int64_t q_sl, int64_t q_sh, int64_t k_sl, int64_t k_sh, int64_t o_sl, int64_t o_sh,
                                                   int is_causal, float q_premul, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr);
+/* Its FP8-PV form (ABI 22): the operands of sage_attn_qk_int8_pv_f8_varlen without q_scale / cu_q_scale, q in fp16 / bf16 quantised per
+ * 128-row block in the prologue after the multiplication by q_premul (= sm_scale log2(e)); pv_accum two-level / single, exact score form,
+ * lse as there. */
+SAGE_API int sage_attn_fused_qblock_pv_f8_varlen(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
+                                                 const float *k_scale, const float *v_scale,
+                                                 const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, const int32_t *cu_k_scale,
+                                                 const int32_t *seq_order, const int32_t *work_items, const int32_t *work_hdr, int items_bound,
+                                                 int nseq, int max_seqlen_q, int Hq, int Hkv, int D,
+                                                 int64_t q_sl, int64_t q_sh, int64_t k_sl, int64_t k_sh, int64_t o_sl, int64_t o_sh, int64_t lse_sh,
+                                                 int is_causal, float q_premul, int pv_accum, int q_dtype, int out_dtype, void *stream,
+                                                 const SageLaunchAttr *attr);
 
 /* The same kernel over a key range split into kv_split chunks of Lk_chunk keys each (a whole number of 64-key tiles), folded
  * into the kv-head dimension: k / k_scale / v_image / v_scale / v_mean are the operands of the unsplit call viewed as

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from . import _cabi, ops
 from .quant import (LOG2E, _aligned, _cu_blocks, _dims, _p, _quant, _squeeze_km, _stream, channel_mean, channel_mean_packed, per_block_int8, per_block_int8_varlen,
-                    per_channel_fp8, prep_v_fp16, prep_v_fp16_varlen, prepass_fused_ok, prepass_kv_fp8, prepass_kv_varlen,
+                    per_channel_fp8, per_channel_fp8_varlen, prep_v_fp16, prep_v_fp16_varlen, prepass_fused_ok, prepass_kv_fp8, prepass_kv_varlen,
                     prepass_varlen_fused_ok, sub_mean, varlen_plan)
 
 _SUPPORTED_ARCH_PREFIX = "gfx950"
@@ -386,14 +386,16 @@ def sageattn_qk_int8_pv_fp16_triton(q, k, v, tensor_layout: str = "HND", quantiz
 class _VarlenState:
     """Operands of the attention launch of one ``sageattn_varlen`` call (what its pre-pass produces)."""
     __slots__ = ("q", "q_int8", "q_scale", "k_int8", "k_scale", "v_image", "cu_q", "cu_k", "cu_qs", "cu_ks", "order", "plan", "fuse_q",
-                 "max_seqlen_q", "is_causal", "q_premul", "dtype", "head_dim_og")
+                 "max_seqlen_q", "is_causal", "q_premul", "dtype", "head_dim_og", "v_scale", "km", "sm_scale")
 
 
 @torch.compiler.disable
-def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k, kwargs) -> _VarlenState:
+def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k, kwargs,
+                    v_fp8: bool = False) -> _VarlenState:
     """Everything of ``sageattn_varlen`` in front of the attention launch (core.py:427-444): the index arrays (one launch, no host
     synchronisation), ``km`` over all packed tokens, INT8 K, the fp16 V image -- one launch that reads K and V once where the head barrier
-    reaches (``prepass_kv_varlen``), else the kernel sequence with the same bits."""
+    reaches (``prepass_kv_varlen``), else the kernel sequence with the same bits.  ``v_fp8`` (``sageattn_qk_int8_pv_fp8_varlen``): the same
+    Q / K half, and V as the e4m3 image with per-(sequence, head, channel) scales (``per_channel_fp8_varlen``) instead of the fp16 image."""
     st = _VarlenState()
     st.dtype = q.dtype
     _check_inputs(q, k, v)
@@ -405,6 +407,7 @@ def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     assert Hq % Hkv == 0, "num_qo_heads must be divisible by num_kv_heads"
     if sm_scale is None:
         sm_scale = 1.0 / (st.head_dim_og ** 0.5)
+    st.sm_scale = sm_scale
     st.fuse_q = fuse_q = kwargs.get("fuse_q_quant", True)      # the Q half of the quantiser in the attention kernel's prologue (same bits)
     st.cu_q = cu_q = cu_seqlens_q.to(torch.int32).contiguous()
     st.cu_k = cu_k = cu_seqlens_k.to(torch.int32).contiguous()
@@ -412,28 +415,32 @@ def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     # block-count prefix sums, the attention launch's work list and the pre-pass's slab map from one small launch (None: more sequences than
     # it takes -- then torch prefix sums, an on-device argsort for the order and the kernel sequence)
     plan = varlen_plan(cu_q, cu_k, want_q_blocks=not fuse_q, total_q=q.shape[0], total_k=k.shape[0], is_causal=is_causal, Hq=Hq, Hkv=Hkv,
-                       head_dim=D, pv_fp8=False) if kwargs.get("varlen_plan", True) else None
+                       head_dim=D, pv_fp8=v_fp8) if kwargs.get("varlen_plan", True) else None
     st.plan = plan if (plan is not None and kwargs.get("work_list", True)) else None
     fused = kwargs.get("fused_prepass")
     if fused is None:
         fused = os.environ.get("SAGE_PREPASS", "") not in ("seq", "sequence", "0")
     fused = bool(fused) and k.shape == v.shape and prepass_varlen_fused_ok(k, plan, max_seqlen_k, smooth_k)
+    st.v_scale = None
     if fused:
-        _, st.k_int8, st.k_scale, st.v_image = prepass_kv_varlen(k, v, cu_k, plan, max_seqlen_k, smooth_k=smooth_k)
+        st.km, st.k_int8, st.k_scale, st.v_image = prepass_kv_varlen(k, None if v_fp8 else v, cu_k, plan, max_seqlen_k, smooth_k=smooth_k)
         st.cu_ks = plan.cu_ks
         st.q_int8 = st.q_scale = st.cu_qs = None
         if not fuse_q:
             st.q_int8, st.q_scale, _, _, st.cu_qs, _ = per_block_int8_varlen(q, None, cu_q, cu_k, max_seqlen_q, max_seqlen_k, sm_scale=sm_scale,
                                                                             cu_qs=plan.cu_qs)
     else:
-        km = channel_mean_packed(k, cu_k, plan) if smooth_k else None   # mean over ALL packed tokens, as core.py:432-434
+        st.km = km = channel_mean_packed(k, cu_k, plan) if smooth_k else None   # mean over ALL packed tokens, as core.py:432-434
         # (prefix arrays from the plan, or from torch ops on the device: either way the scale tensors are allocated at their host-known
         #  bounds and nothing synchronises -- the reference's `.item()` pair is gone on every route)
         st.q_int8, st.q_scale, st.k_int8, st.k_scale, st.cu_qs, st.cu_ks = per_block_int8_varlen(
             None if fuse_q else q, k, cu_q, cu_k, max_seqlen_q, max_seqlen_k, km=km, sm_scale=sm_scale,
             cu_ks=plan.cu_ks if plan is not None else _cu_blocks(cu_k, 64),
             cu_qs=None if fuse_q else (plan.cu_qs if plan is not None else _cu_blocks(cu_q, 128)))
-        st.v_image = prep_v_fp16_varlen(v, cu_k, st.cu_ks, max_seqlen_k, ntiles=(k.shape[0] + 63) // 64 + nseq)
+        if not v_fp8:
+            st.v_image = prep_v_fp16_varlen(v, cu_k, st.cu_ks, max_seqlen_k, ntiles=(k.shape[0] + 63) // 64 + nseq)
+    if v_fp8:
+        st.v_image, st.v_scale = per_channel_fp8_varlen(v, cu_k, st.cu_ks, max_seqlen_k, plan=plan, ntiles=(v.shape[0] + 63) // 64 + nseq)
     # without a work list: schedule the longest sequences first (on the device, no sync); results do not depend on the order
     st.order = plan.order if plan is not None else torch.argsort(cu_q[1:] - cu_q[:-1], descending=True).to(torch.int32)
     st.q = _aligned(q, 8) if fuse_q else None
@@ -483,6 +490,65 @@ def sageattn_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_
     per-sequence ones: equal up to the last bit of an input-dtype rounding)."""
     return _varlen_attend(_varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k,
                                           kwargs))
+
+
+@torch.compiler.disable
+def _varlen_attend_f8(st: _VarlenState, two_level: bool, return_lse: bool):
+    """The attention launch of ``sageattn_qk_int8_pv_fp8_varlen``: ``_varlen_attend``'s, with the e4m3 V image and its scales, the FP8
+    accumulation asked for and the packed LSE ``[Hq, sum Lq]`` (log2 units) when asked for."""
+    q = st.q if st.fuse_q else st.q_int8
+    T, Hq, D = q.shape
+    Hkv = st.k_int8.shape[1]
+    o = torch.empty(q.shape, dtype=st.dtype, device=q.device)
+    lse = torch.empty((Hq, T), dtype=torch.float32, device=q.device) if return_lse else None
+    code = _cabi.DTYPE_F16 if st.dtype == torch.float16 else _cabi.DTYPE_BF16
+    accum = _cabi.PV_ACCUM_TWO_LEVEL if two_level else _cabi.PV_ACCUM_SINGLE
+    plan = st.plan
+    items, hdr, bound = (plan.items, plan.hdr, plan.items_bound) if plan is not None else (None, None, 0)
+    nseq = st.cu_q.shape[0] - 1
+    attr = ops.attn_attr(q.device, st.is_causal, Hq * (T // 128), packed=st.fuse_q) if plan is not None else None
+    if st.fuse_q:
+        rc = _cabi.load().sage_attn_fused_qblock_pv_f8_varlen(
+            _p(q), _p(st.k_int8), _p(st.v_image), _p(o), _p(lse), _p(st.k_scale), _p(st.v_scale), _p(st.cu_q), _p(st.cu_k), _p(st.cu_ks),
+            _p(st.order), _p(items), _p(hdr), bound, nseq, st.max_seqlen_q, Hq, Hkv, D, q.stride(0), q.stride(1), st.k_int8.stride(0),
+            st.k_int8.stride(1), o.stride(0), o.stride(1), T, int(st.is_causal), st.q_premul, accum, code, code, _stream(o), _cabi.attr_arg(attr))
+        ops.attn_check(rc, "sage_attn_fused_qblock_pv_f8_varlen", attr, q.device)
+    else:
+        rc = _cabi.load().sage_attn_qk_int8_pv_f8_varlen(
+            _p(q), _p(st.k_int8), _p(st.v_image), _p(o), _p(lse), _p(st.q_scale), _p(st.k_scale), _p(st.v_scale), _p(st.cu_q), _p(st.cu_k),
+            _p(st.cu_qs), _p(st.cu_ks), _p(st.order), _p(items), _p(hdr), bound, nseq, st.max_seqlen_q, Hq, Hkv, D, q.stride(0), q.stride(1),
+            st.k_int8.stride(0), st.k_int8.stride(1), o.stride(0), o.stride(1), T, int(st.is_causal), 1.0, accum, code, _stream(o),
+            _cabi.attr_arg(attr))
+        ops.attn_check(rc, "sage_attn_qk_int8_pv_f8_varlen", attr, q.device)
+    return o[..., :st.head_dim_og], lse
+
+
+@torch.compiler.disable
+def sageattn_qk_int8_pv_fp8_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, is_causal: bool = False,
+                                   sm_scale: Optional[float] = None, smooth_k: bool = True, pv_accum_dtype: str = "fp32+fp32",
+                                   return_lse: bool = False, **kwargs: Any):
+    """Variable-length batches with FP8 (e4m3) PV: ``sageattn_varlen``'s packed ``[sum L, H, D]`` inputs, GQA, head-dim padding, causal
+    masking and Q / K half bit for bit (per-block INT8, Triton rounding, sm_scale log2(e) folded into Q, K smoothed by the mean over ALL
+    packed tokens), and V in e4m3 with one scale per (sequence, kv-head, channel) -- an outlier token costs no other sequence its V precision.
+    ``pv_accum_dtype`` "fp32+fp32" (two-level accumulation) or "fp32" (single level); the exact score form.  ``return_lse``: ``(o, lse)``
+    with ``lse`` fp32 ``[Hq, sum Lq]`` in natural-log units, smooth_k corrected as the dense calls' (core.py:328-329).  Route switches as
+    ``sageattn_varlen``'s (``fuse_q_quant``, ``work_list``, ``varlen_plan``, ``fused_prepass``): the same bits either way.  No host
+    synchronisation on any route."""
+    if pv_accum_dtype not in ("fp32", "fp32+fp32"):
+        raise ValueError(f"Unsupported pv_accum_dtype: {pv_accum_dtype}")
+    st = _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k, kwargs, v_fp8=True)
+    o, lse = _varlen_attend_f8(st, pv_accum_dtype == "fp32+fp32", return_lse)
+    if not return_lse:
+        return o
+    lse = lse / 1.44269504                 # kernel LSE: log2 units (core.py:328-329)
+    if smooth_k:
+        # q . km^T per (query head, packed row), km broadcast over the GQA group, in the input dtype as _lse_correction computes it
+        # (the padded channels of km are zero: the unpadded q with the first head_dim channels of km gives the same products)
+        Hq, Hkv = q.shape[1], st.km.shape[1]
+        km = st.km[0, :, :q.shape[-1]]
+        km = km if Hq == Hkv else torch.repeat_interleave(km, Hq // Hkv, dim=0)
+        lse = lse + torch.matmul(q.transpose(0, 1), km.unsqueeze(-1)).squeeze(-1).to(torch.float32) * st.sm_scale
+    return o, lse
 
 
 _ROUTE_KWARGS = ("split_kv", "fused_prepass", "fuse_q_quant", "fp8_scores", "v_in_place")

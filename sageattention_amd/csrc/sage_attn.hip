@@ -48,6 +48,11 @@ static int set_work_order(AttnParams &q, bool causal, int head_dim, bool pv_fp8,
 // the instantiation unit of (head_dim, PV format, FP8 score form)
 static hipError_t launch_unit(const AttnParams &p, int head_dim, bool pv_fp8, const AttnVariant &v, int nwork, const AttnLaunchOpts &o)
 {
+    if (pv_fp8 && (v.qf == 3 || v.qf == 4)) {       // the packed FP8 route's per-block fused-Q kernels (exact score form only)
+        if (head_dim == 128) return launch_attn_f8_varlen<128>(p, v, nwork, o);
+        if (head_dim == 64) return launch_attn_f8_varlen<64>(p, v, nwork, o);
+        return hipErrorInvalidValue;
+    }
     if (head_dim == 128) {
         if (!pv_fp8) return launch_attn_part<128, false, true>(p, v, nwork, o);
         return o.fp8_folded ? launch_attn_part<128, true, true>(p, v, nwork, o) : launch_attn_part<128, true, false>(p, v, nwork, o);
@@ -72,16 +77,18 @@ hipError_t launch_attn_fused_q(const AttnParams &p_in, int head_dim, bool causal
     return launch_unit(p, head_dim, pv_fp8, v, nwork, o);
 }
 
-hipError_t launch_attn_fused_qblock(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o)
+hipError_t launch_attn_fused_qblock(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, bool pv_fp8, bool two_level,
+                                   const AttnLaunchOpts &o)
 {
     AttnParams p = p_in;
-    const int nwork = set_work_order(p, causal, head_dim, false, false);
+    const int nwork = set_work_order(p, causal, head_dim, pv_fp8, false);
     if (o.grid_out != nullptr) *o.grid_out = 0;
     if (nwork <= 0) return hipSuccess;
     if (q_dtype != DT_F16 && q_dtype != DT_BF16) return hipErrorInvalidValue;
-    if (p.v_rows != 0 && (q_dtype != DT_F16 || p.cu_q != nullptr)) return hipErrorInvalidValue;
-    const AttnVariant v = {causal, false, true, 0, q_dtype == DT_F16 ? 3 : 4, p.v_rows != 0};
-    return launch_unit(p, head_dim, false, v, nwork, o);
+    if (p.v_rows != 0 && (pv_fp8 || q_dtype != DT_F16 || p.cu_q != nullptr)) return hipErrorInvalidValue;
+    if (pv_fp8 && p.cu_q == nullptr) return hipErrorInvalidValue;          // FP8 PV with the per-block Q quantiser: packed batches only
+    const AttnVariant v = {causal, false, pv_fp8 ? two_level : true, 0, q_dtype == DT_F16 ? 3 : 4, p.v_rows != 0};
+    return launch_unit(p, head_dim, pv_fp8, v, nwork, o);
 }
 
 hipError_t launch_attn(const AttnParams &p_in, int head_dim, bool pv_fp8, bool causal, bool kthread,

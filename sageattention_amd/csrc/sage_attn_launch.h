@@ -134,4 +134,28 @@ hipError_t launch_attn_part(const AttnParams &p, const AttnVariant &v, int nwork
     return hipErrorInvalidValue;
 }
 
+// FP8 PV over a packed batch with the per-block Q quantiser in the prologue (qf 3 / 4: fp16 / bf16 q, sm_scale log2(e) folded into q), the
+// exact score form, per-block k scales, two-level or single accumulation: the instantiation units sage_attn_d{128,64}_f8v.hip.  Causal
+// launches over the device-built work list take the ticket route as the FP16 ones do (CPERS); without a work list the hardware's dispatch.
+template <int D>
+hipError_t launch_attn_f8_varlen(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
+{
+    using C = TileCfg<D, true, 1>;
+    if (p.cu_q == nullptr || l.fp8_folded || v.kthread || v.vrows || v.mask_kind != 0 || (v.qf != 3 && v.qf != 4)) return hipErrorInvalidValue;
+    const bool pers = !v.causal;
+    if (v.causal && p.work_items != nullptr) {
+#define SAGE_F8VP(F_, T_) if (v.qf == F_ && v.two_level == T_) \
+        return launch_kernel<sage_attn_kernel<D, true, true, false, T_, 1, 0, F_, false, true>>(C::LDS_BYTES, p, nwork, l, true);
+        SAGE_F8VP(3, false) SAGE_F8VP(3, true) SAGE_F8VP(4, false) SAGE_F8VP(4, true)
+#undef SAGE_F8VP
+        return hipErrorInvalidValue;
+    }
+#define SAGE_F8V(C_, F_, T_) if (v.causal == C_ && v.qf == F_ && v.two_level == T_) \
+    return launch_kernel<sage_attn_kernel<D, true, C_, false, T_, 1, 0, F_, false>>(C::LDS_BYTES, p, nwork, l, pers);
+    SAGE_F8V(false, 3, false) SAGE_F8V(false, 3, true) SAGE_F8V(false, 4, false) SAGE_F8V(false, 4, true)
+    SAGE_F8V(true, 3, false)  SAGE_F8V(true, 3, true)  SAGE_F8V(true, 4, false)  SAGE_F8V(true, 4, true)
+#undef SAGE_F8V
+    return hipErrorInvalidValue;
+}
+
 }  // namespace sage

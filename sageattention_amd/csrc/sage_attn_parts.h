@@ -1,6 +1,6 @@
 // sage_attn_parts.h -- interface between the host-side dispatch of the attention launches (sage_attn.hip) and the instantiation units
 // sage_attn_d{128,64}_{f8,f8f,f16}.hip, each of which compiles the kernel family of sage_attn_kernel.h for one head size, one PV format and
-// (FP8) one score form.  The split exists for build time only: the units are independent and compile in parallel.
+// (FP8) one score form, and sage_attn_d{128,64}_f8v.hip (the packed FP8 route's fused-Q kernels).  The split exists for build time only: the units are independent and compile in parallel.
 #pragma once
 #include "sage_kernels.h"
 
@@ -26,5 +26,11 @@ extern template hipError_t launch_attn_part<128, false, true>(const AttnParams &
 extern template hipError_t launch_attn_part<64, true, true>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_part<64, true, false>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_part<64, false, true>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+
+// FP8 PV over a packed batch, per-block Q quantised in the prologue (qf 3 / 4), exact score form: units sage_attn_d{128,64}_f8v.hip
+template <int D>
+hipError_t launch_attn_f8_varlen(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l);
+extern template hipError_t launch_attn_f8_varlen<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_f8_varlen<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 
 }  // namespace sage

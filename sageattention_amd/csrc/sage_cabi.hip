@@ -74,10 +74,13 @@ int attn_common(bool fp8, bool varlen, const int8_t *q, const int8_t *k, const v
                 int64_t o_sb, int64_t o_sh, int64_t o_sl,
                 int is_causal, int gran, int q_warp, float sm_scale_log2, int pv_accum, int out_dtype, void *stream, const SageLaunchAttr *attr,
                 const MaskArg *mask = nullptr, const int32_t *seq_order = nullptr,
-                const int32_t *work_items = nullptr, const int32_t *work_hdr = nullptr, int items_bound = 0, const int64_t *v_strides = nullptr)
+                const int32_t *work_items = nullptr, const int32_t *work_hdr = nullptr, int items_bound = 0, const int64_t *v_strides = nullptr,
+                int64_t lse_sh = 0)
 {
     LaunchAttr la;
     if (const int rc = read_attr(attr, stream, mask == nullptr, la)) return rc;
+    SAGE_REQUIRE(!(fp8 && varlen && la.opts.fp8_folded), "packed (varlen) FP8 attention has the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES)");
+    SAGE_REQUIRE(!varlen || lse == nullptr || lse_sh > 0, "varlen lse [Hq, sum Lq]: its head stride lse_sh must be positive (got %lld)", (long long)lse_sh);
     if (v_strides != nullptr) {            // `v_image` is the caller's fp16 value tensor itself (rows), read in place
         SAGE_REQUIRE(!fp8 && !varlen && mask == nullptr, "V rows in place: dense, unmasked FP16-PV calls");
         SAGE_REQUIRE(v_strides[0] % 8 == 0 && v_strides[1] % 8 == 0 && v_strides[2] % 8 == 0 && v_strides[2] >= D, "v strides must be multiples of 8 elements (16-byte rows)");
@@ -130,7 +133,7 @@ int attn_common(bool fp8, bool varlen, const int8_t *q, const int8_t *k, const v
     p.ks_shift = k128 ? 1 : 0;
     p.nks = ((Lk + (sage::BLKK << p.ks_shift) - 1) / (sage::BLKK << p.ks_shift)) * (kthread ? 4 : 1);
     p.out_dtype = out_dtype;
-    p.lse_sh = 0;
+    p.lse_sh = varlen ? lse_sh : 0;
     p.sm_scale_log2 = sm_scale_log2;
     if (v_strides != nullptr) { p.v_rows = 1; p.v_sb = v_strides[0]; p.v_sh = v_strides[1]; p.v_sl = v_strides[2]; }
     int mask_kind = 0;
@@ -371,6 +374,50 @@ SAGE_API int sage_prep_v_fp8(const void *v, void *v_image, float *v_scale, float
     int rc = stats_common(v, nullptr, ws, stats, B, H, L, D, v_sb, v_sh, v_sl, dtype, stream, "sage_v_stats launch");
     if (rc != SAGE_OK) return rc;
     return prep_v_common(v, v_image, v_scale, v_mean, nullptr, stats, nullptr, nullptr, B, H, L, D, v_sb, v_sh, v_sl,
+                         scale_max, dtype, 1, stream);
+}
+
+// per-sequence V statistics of a packed batch: the stage-1 partials (the slab map's layout [1,H,nslab_bound], or nslab_bound = 0: without a
+// map, [nseq,H,ceil(max_seqlen/512)]), then the final block [nseq,H,3,D]
+static int64_t prep_v_varlen_partials(int nseq, int H, int max_seqlen, int nslab_bound, int D)
+{
+    if (nslab_bound > 0) return (int64_t)H * nslab_bound * 3 * D;
+    return (int64_t)nseq * H * ((max_seqlen + sage::kStatsSlab - 1) / sage::kStatsSlab) * 3 * D;
+}
+
+SAGE_API int64_t sage_prep_v_fp8_varlen_ws_floats(int nseq, int H, int max_seqlen, int nslab_bound, int D)
+{
+    if (nseq < 1 || H < 1 || max_seqlen < 1 || nslab_bound < 0 || D < 1) return 0;
+    return prep_v_varlen_partials(nseq, H, max_seqlen, nslab_bound, D) + (int64_t)nseq * H * 3 * D;
+}
+
+SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale, float *ws, const int32_t *cu_seqlens, const int32_t *cu_tiles,
+                                    const int32_t *slab_first, const int32_t *slab_seq, const int32_t *hdr,
+                                    int nseq, int total_tokens, int max_seqlen, int nslab_bound, int H, int D, int64_t v_sl, int64_t v_sh,
+                                    float scale_max, int dtype, void *stream)
+{
+    SAGE_REQUIRE(v && v_image && v_scale && ws && cu_seqlens && cu_tiles, "null tensor pointer");
+    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
+    SAGE_REQUIRE(nseq >= 1 && H > 0 && total_tokens > 0 && max_seqlen > 0, "empty problem (nseq=%d H=%d total_tokens=%d max_seqlen=%d)",
+                 nseq, H, total_tokens, max_seqlen);
+    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
+    SAGE_REQUIRE(aligned16(v) && aligned16(v_image), "v / v_image must be 16-byte aligned");
+    SAGE_REQUIRE(v_sl % 8 == 0 && v_sh % 8 == 0, "v strides must be multiples of 8 elements");
+    SAGE_REQUIRE(scale_max > 0.0f, "scale_max must be positive");
+    const bool map = slab_seq != nullptr;
+    SAGE_REQUIRE((slab_first != nullptr) == map && (hdr != nullptr) == map, "the slab map comes as (slab_first, slab_seq, hdr) together");
+    SAGE_REQUIRE(!map || (nseq <= sage::kVarlenPlanMaxSeq && nslab_bound >= (total_tokens + sage::kStatsSlab - 1) / sage::kStatsSlab),
+                 "slab map: nseq <= %d and nslab_bound >= ceil(total_tokens / %d) (got nseq=%d nslab_bound=%d)", sage::kVarlenPlanMaxSeq,
+                 sage::kStatsSlab, nseq, nslab_bound);
+    SAGE_REQUIRE(map || nslab_bound == 0, "nslab_bound is the slab map's (0 without one)");
+    sage::StatsParams st{};
+    st.x = v; st.ws = ws; st.stats = ws + prep_v_varlen_partials(nseq, H, max_seqlen, nslab_bound, D); st.mean_out = nullptr;
+    st.B = nseq; st.H = H; st.L = total_tokens; st.D = D;
+    st.nslab = map ? nslab_bound : (max_seqlen + sage::kStatsSlab - 1) / sage::kStatsSlab;
+    st.x_sb = 0; st.x_sh = v_sh; st.x_sl = v_sl; st.dtype = dtype;
+    st.cu = cu_seqlens; st.slab_first = slab_first; st.slab_seq = slab_seq; st.hdr = hdr; st.nseq = nseq; st.seq_stats = 1;
+    if (const int rc = check_launch(sage::launch_stats(st, static_cast<hipStream_t>(stream)), "sage_v_stats_varlen launch")) return rc;
+    return prep_v_common(v, v_image, v_scale, nullptr, nullptr, st.stats, cu_seqlens, cu_tiles, nseq, H, max_seqlen, D, 0, v_sh, v_sl,
                          scale_max, dtype, 1, stream);
 }
 
@@ -665,6 +712,22 @@ SAGE_API int sage_attn_qk_int8_pv_f16_varlen(const int8_t *q, const int8_t *k, c
                        work_items, work_hdr, items_bound);
 }
 
+SAGE_API int sage_attn_qk_int8_pv_f8_varlen(const int8_t *q, const int8_t *k, const void *v_image, void *o, float *lse,
+                                            const float *q_scale, const float *k_scale, const float *v_scale,
+                                            const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k,
+                                            const int32_t *cu_q_scale, const int32_t *cu_k_scale, const int32_t *seq_order,
+                                            const int32_t *work_items, const int32_t *work_hdr, int items_bound,
+                                            int nseq, int max_seqlen_q, int Hq, int Hkv, int D,
+                                            int64_t q_sl, int64_t q_sh, int64_t k_sl, int64_t k_sh, int64_t o_sl, int64_t o_sh, int64_t lse_sh,
+                                            int is_causal, float sm_scale_log2, int pv_accum, int out_dtype, void *stream, const SageLaunchAttr *attr)
+{
+    return attn_common(true, true, q, k, v_image, o, lse, q_scale, k_scale, v_scale, nullptr,
+                       cu_seqlens_q, cu_seqlens_k, cu_q_scale, cu_k_scale,
+                       nseq, Hq, Hkv, max_seqlen_q, 0, D, 0, q_sh, q_sl, 0, k_sh, k_sl, 0, o_sh, o_sl,
+                       is_causal, SAGE_GRAN_PER_BLOCK, 128, sm_scale_log2, pv_accum, out_dtype, stream, attr, nullptr, seq_order,
+                       work_items, work_hdr, items_bound, nullptr, lse_sh);
+}
+
 static int fused_q_common(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
                           const float *k_scale, const float *v_scale, const float *v_mean,
                           int B, int Hq, int Hkv, int Lq, int Lk, int D,
@@ -745,6 +808,7 @@ SAGE_API int sage_attn_fused_q_pv_f16_vrows(const void *q, const int8_t *k, cons
 }
 
 // q in fp16 / bf16, quantised per 128-row block in the kernel prologue (dense: cu_q == nullptr; varlen: packed tensors, B = nseq)
+// FP8 PV (fp8 = true, ABI 22): packed batches only, v_scale [nseq,Hkv,D], pv_accum single / two-level, lse nullable [Hq, lse_sh] by packed row
 static int fused_qblock_common(const void *q, const int8_t *k, const void *v_image, void *o, float *lse, const float *k_scale,
                                const int32_t *cu_q, const int32_t *cu_k, const int32_t *cu_ks, const int32_t *seq_order,
                                const int32_t *work_items, const int32_t *work_hdr, int items_bound,
@@ -752,11 +816,19 @@ static int fused_qblock_common(const void *q, const int8_t *k, const void *v_ima
                                int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
                                int64_t o_sb, int64_t o_sh, int64_t o_sl,
                                int is_causal, float q_premul, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr,
-                               const int64_t *v_strides = nullptr)
+                               const int64_t *v_strides = nullptr, bool fp8 = false, const float *v_scale = nullptr,
+                               int pv_accum = SAGE_PV_ACCUM_TRITON, int64_t lse_sh = 0)
 {
     LaunchAttr la;
     if (const int rc = read_attr(attr, stream, true, la)) return rc;
     const bool varlen = cu_q != nullptr;
+    if (fp8) {
+        SAGE_REQUIRE(varlen && v_strides == nullptr, "FP8 PV with the per-block Q quantiser: packed (varlen) batches only");
+        SAGE_REQUIRE(v_scale, "fp8 PV needs v_scale");
+        SAGE_REQUIRE(pv_accum == SAGE_PV_ACCUM_SINGLE || pv_accum == SAGE_PV_ACCUM_TWO_LEVEL, "bad pv_accum %d", pv_accum);
+        SAGE_REQUIRE(!la.opts.fp8_folded, "packed (varlen) FP8 attention has the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES)");
+        SAGE_REQUIRE(lse == nullptr || lse_sh > 0, "varlen lse [Hq, sum Lq]: its head stride lse_sh must be positive (got %lld)", (long long)lse_sh);
+    }
     if (v_strides != nullptr) {
         SAGE_REQUIRE(!varlen && q_dtype == SAGE_DTYPE_F16, "V rows in place: dense calls on fp16 inputs");
         SAGE_REQUIRE(v_strides[0] % 8 == 0 && v_strides[1] % 8 == 0 && v_strides[2] % 8 == 0 && v_strides[2] >= D, "v strides must be multiples of 8 elements (16-byte rows)");
@@ -773,11 +845,12 @@ static int fused_qblock_common(const void *q, const int8_t *k, const void *v_ima
     SAGE_REQUIRE(k_sl % 16 == 0 && k_sh % 16 == 0 && k_sb % 16 == 0, "int8 k strides must be multiples of 16");
     SAGE_REQUIRE(o_sl % 8 == 0 && o_sh % 8 == 0 && o_sb % 8 == 0, "output strides must be multiples of 8 elements");
     SAGE_REQUIRE(!varlen || (cu_k && cu_ks), "varlen needs cu_seqlens_k and the k scale prefix array");
-    SAGE_REQUIRE(!varlen || lse == nullptr, "varlen returns no lse");
+    SAGE_REQUIRE(!varlen || fp8 || lse == nullptr, "varlen FP16 PV returns no lse");
     sage::AttnParams p{};
     p.sched = la.ws; p.trace = la.trace; p.trace_wgs = la.trace_wgs;
     p.q = q; p.k = k; p.v = v_image; p.o = o; p.lse = lse;
-    p.k_scale = k_scale;
+    p.k_scale = k_scale; p.v_scale = fp8 ? v_scale : nullptr;
+    p.lse_sh = varlen ? lse_sh : 0;
     p.cu_q = cu_q; p.cu_k = cu_k; p.cu_qs = nullptr; p.cu_ks = cu_ks; p.seq_order = varlen ? seq_order : nullptr;
     SAGE_REQUIRE((work_items == nullptr) == (work_hdr == nullptr) && (work_items == nullptr || (varlen && items_bound > 0)),
                  "the work list comes as (work_items, work_hdr, items_bound > 0), varlen only");
@@ -795,7 +868,8 @@ static int fused_qblock_common(const void *q, const int8_t *k, const void *v_ima
     p.sm_scale_log2 = 1.0f;                 // sm_scale * log2(e) is folded into the quantised q (q_premul), as the reference's quantiser does
     p.q_premul = q_premul;
     if (v_strides != nullptr) { p.v_rows = 1; p.v_sb = v_strides[0]; p.v_sh = v_strides[1]; p.v_sl = v_strides[2]; }
-    return check_launch(sage::launch_attn_fused_qblock(p, D, is_causal != 0, q_dtype, la.opts), "sage_attn_fused_qblock launch");
+    return check_launch(sage::launch_attn_fused_qblock(p, D, is_causal != 0, q_dtype, fp8, pv_accum == SAGE_PV_ACCUM_TWO_LEVEL, la.opts),
+                        "sage_attn_fused_qblock launch");
 }
 
 SAGE_API int sage_attn_fused_qblock_pv_f16(const void *q, const int8_t *k, const void *v_image, void *o, float *lse, const float *k_scale,
@@ -830,6 +904,21 @@ SAGE_API int sage_attn_fused_qblock_pv_f16_varlen(const void *q, const int8_t *k
     return fused_qblock_common(q, k, v_image, o, nullptr, k_scale, cu_seqlens_q, cu_seqlens_k, cu_k_scale, seq_order,
                                work_items, work_hdr, items_bound, nseq, Hq, Hkv, max_seqlen_q, 0, D, 0, q_sh, q_sl, 0, k_sh, k_sl, 0, o_sh, o_sl,
                                is_causal, q_premul, q_dtype, out_dtype, stream, attr);
+}
+
+SAGE_API int sage_attn_fused_qblock_pv_f8_varlen(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
+                                                 const float *k_scale, const float *v_scale,
+                                                 const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, const int32_t *cu_k_scale,
+                                                 const int32_t *seq_order, const int32_t *work_items, const int32_t *work_hdr, int items_bound,
+                                                 int nseq, int max_seqlen_q, int Hq, int Hkv, int D,
+                                                 int64_t q_sl, int64_t q_sh, int64_t k_sl, int64_t k_sh, int64_t o_sl, int64_t o_sh, int64_t lse_sh,
+                                                 int is_causal, float q_premul, int pv_accum, int q_dtype, int out_dtype, void *stream,
+                                                 const SageLaunchAttr *attr)
+{
+    SAGE_REQUIRE(cu_seqlens_q != nullptr, "varlen needs cu_seqlens_q");
+    return fused_qblock_common(q, k, v_image, o, lse, k_scale, cu_seqlens_q, cu_seqlens_k, cu_k_scale, seq_order,
+                               work_items, work_hdr, items_bound, nseq, Hq, Hkv, max_seqlen_q, 0, D, 0, q_sh, q_sl, 0, k_sh, k_sl, 0, o_sh, o_sl,
+                               is_causal, q_premul, q_dtype, out_dtype, stream, attr, nullptr, true, v_scale, pv_accum, lse_sh);
 }
 
 SAGE_API int sage_attn_fused_q_pv_f8_split(const void *q, const int8_t *k, const void *v_image, void *o_part, float *lse_part,

@@ -69,9 +69,10 @@ hipError_t launch_attn(const AttnParams &p, int head_dim, bool pv_fp8, bool caus
                        bool two_level, int mask_kind, const AttnLaunchOpts &o);
 // q in fp16 / bf16, quantised per-thread in the kernel prologue; dense only.  FP8 PV: two-level accumulation; FP16 PV: FP32 accumulation
 hipError_t launch_attn_fused_q(const AttnParams &p, int head_dim, bool causal, int q_dtype, bool pv_fp8, const AttnLaunchOpts &o);
-// q in fp16 / bf16, quantised per 128-row block in the prologue after the multiplication by p.q_premul; FP16 PV in the Triton kernels'
-// form, per-block k scales; dense or varlen (p.cu_q)
-hipError_t launch_attn_fused_qblock(const AttnParams &p, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o);
+// q in fp16 / bf16, quantised per 128-row block in the prologue after the multiplication by p.q_premul; per-block k scales.  FP16 PV in
+// the Triton kernels' form, dense or varlen (p.cu_q); FP8 PV (varlen only, the exact score form): two_level or single accumulation
+hipError_t launch_attn_fused_qblock(const AttnParams &p, int head_dim, bool causal, int q_dtype, bool pv_fp8, bool two_level,
+                                   const AttnLaunchOpts &o);
 
 // causal dense work order of the 128-row kernels: -1 grouped / folded by grid size, 0 head-major, n groups of n heads (SAGE_ORDER_GROUP)
 int work_order();
@@ -137,6 +138,10 @@ struct StatsParams {
     // packed batches (nullable, together): slabs per segment as sage_varlen_plan lays them out; nslab = host-known bound, L = rows of x
     const int32_t *cu, *slab_first, *slab_seq, *hdr;
     int nseq;
+    // seq_stats != 0 (packed batches, cu set; B = nseq): stage 2 per SEQUENCE, stats [nseq,H,3,D] (the V scales of sage_prep_v_fp8_varlen).
+    // With the slab map above stage 1 is the map's launch (ws [1,H,nslab,3,D]); without it stage 1 runs over (slab of a sequence, head,
+    // sequence), nslab = ceil(max L / 512) slabs per sequence (ws [nseq,H,nslab,3,D])
+    int seq_stats;
 };
 hipError_t launch_stats(const StatsParams &p, hipStream_t stream);
 

@@ -15,6 +15,9 @@
 // reads are conflict-free ds_read_b128.  Tokens >= L are zero (the reference zero-pads too,
 // fused.cu:283-286) so masked probabilities never multiply garbage.
 //
+// Packed batches (p.cu): one image per 64 tokens of one (sequence, kv-head), ordered [tile, head] from cu_tiles; FP8 (sage_prep_v_fp8_varlen)
+// reads the per-SEQUENCE statistics [nseq,H,3,D] of the stats pass, so every sequence has its own scales.
+//
 // HBM traffic: the statistics pass (sage_stats.hip) reads V once (2 B/elt); the quantise pass reads it
 // again and writes 1 B/elt (fp8) -- 5 B/elt against the reference's 9 B/elt (fp16 intermediate written + read twice).
 #include "sage_common.h"
@@ -35,7 +38,11 @@ prep_v_kernel(const PrepVParams p)
     if (p.cu != nullptr) {
         const int s0 = p.cu[b];
         L = p.cu[b + 1] - s0;
-        if (t * BLKK >= L) return;
+        if (t * BLKK >= L) {
+            // an empty sequence has no tile (its first tile index is the next sequence's); FP8: its scales are zero
+            if (FP8 && t == 0 && tid < D) p.v_scale[((long)b * p.H + h) * D + tid] = 0.0f;
+            return;
+        }
         voff = (long)s0 * p.v_sl + (long)h * p.v_sh;
         tile_idx = ((long)p.cu_tiles[b] + t) * p.H + h;
     } else {

@@ -37,6 +37,12 @@ stats_partial_kernel(const StatsParams p)
         varlen_segment(p.cu, p.nseq, p.L, seg, t0, len);
         start = t0 + (slab - p.slab_first[seg]) * kStatsSlab;
         end = min(t0 + len, start + kStatsSlab);
+    } else if (p.cu != nullptr) {
+        // packed batch without a slab map (per-sequence V statistics, p.seq_stats): slab `slab` of sequence b, rows of x counted from 0
+        int t0, len;
+        varlen_segment(p.cu, p.nseq, p.L, b, t0, len);
+        start = t0 + slab * kStatsSlab;
+        end = min(min(t0 + len, p.L), start + kStatsSlab);
     }
     // eight independent 16-byte loads in flight per thread: with one load per thread the 1024-workgroup grid keeps
     // only ~4 MB in flight chip-wide, half of what a cold HBM read stream needs; rows are still accumulated in order
@@ -103,9 +109,49 @@ __global__ void stats_final_kernel(const StatsParams p)
         reinterpret_cast<uint16_t *>(p.mean_out)[((long)b * p.H + h) * D + d] = st16<DT>(s / (float)p.L);
 }
 
+// Stage 2 of a packed batch, per sequence (p.seq_stats): grid (head, sequence).  The slabs of sequence s in index order -- its range of the
+// slab map, or its own ceil(L_s / 512) slabs -- reduced into stats[s,h] (an empty sequence: max -inf, min +inf, sum 0).  Max and min do not
+// depend on the partition, so the V scales are the same bits with or without the slab map.
+template <int D>
+__global__ void stats_seq_kernel(const StatsParams p)
+{
+    const int d = threadIdx.x, h = blockIdx.x, s = blockIdx.y;
+    const float *ws;
+    int first, last;
+    if (p.slab_seq != nullptr) {
+        ws = p.ws + (long)h * p.nslab * 3 * D;
+        first = p.slab_first[s];
+        last = min(p.slab_first[s + 1], min(p.hdr[4], p.nslab));
+    } else {
+        ws = p.ws + ((long)s * p.H + h) * p.nslab * 3 * D;
+        int t0, len;
+        varlen_segment(p.cu, p.nseq, p.L, s, t0, len);
+        first = 0;
+        last = min((len + kStatsSlab - 1) / kStatsSlab, p.nslab);
+    }
+    float a = -INFINITY, c = INFINITY, sm = 0.0f;
+    for (int i = first; i < last; i++) {
+        const float *wi = ws + (long)i * 3 * D;
+        a = fmaxf(a, wi[d]); c = fminf(c, wi[D + d]); sm += wi[2 * D + d];
+    }
+    float *st = p.stats + ((long)s * p.H + h) * 3 * D;
+    st[d] = a; st[D + d] = c; st[2 * D + d] = sm;
+}
+
 hipError_t launch_stats(const StatsParams &p, hipStream_t s)
 {
     if (p.B <= 0 || p.H <= 0 || p.nslab <= 0) return hipSuccess;
+    if (p.seq_stats) {
+        if (p.cu == nullptr || p.stats == nullptr || p.nseq != p.B) return hipErrorInvalidValue;
+        dim3 g1(p.nslab, p.H, p.slab_seq != nullptr ? 1 : p.B), g2(p.H, p.B);
+#define SAGE_SQ(D_, T_) do { hipLaunchKernelGGL((stats_partial_kernel<D_, T_>), g1, dim3(256), 0, s, p); \
+                             hipLaunchKernelGGL((stats_seq_kernel<D_>), g2, dim3(D_), 0, s, p); } while (0)
+        if (p.D == 128) { if (p.dtype == DT_F16) SAGE_SQ(128, DT_F16); else SAGE_SQ(128, DT_BF16); }
+        else if (p.D == 64) { if (p.dtype == DT_F16) SAGE_SQ(64, DT_F16); else SAGE_SQ(64, DT_BF16); }
+        else return hipErrorInvalidValue;
+#undef SAGE_SQ
+        return hipGetLastError();
+    }
     dim3 g1(p.nslab, p.H, p.B), g2(p.H, p.B);
 #define SAGE_ST(D_, T_) do { hipLaunchKernelGGL((stats_partial_kernel<D_, T_>), g1, dim3(256), 0, s, p); \
                              hipLaunchKernelGGL((stats_final_kernel<D_, T_>), g2, dim3(D_), 0, s, p); } while (0)

@@ -523,6 +523,35 @@ def sub_mean(v: torch.Tensor, tensor_layout: str = "HND"):
 
 
 @_eager
+def per_channel_fp8_varlen(v: torch.Tensor, cu_seqlens_k: torch.Tensor, cu_tiles: torch.Tensor, max_seqlen_k: int,
+                           plan: Optional["VarlenPlan"] = None, ntiles: Optional[int] = None, scale_max: float = 448.0
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Packed ``[sum L, H, D]`` V -> ``(v_image uint8 [ntiles, H, D, 64], v_scale fp32 [nseq, H, D])``: e4m3 with one scale per
+    (sequence, head, channel), ``amax / scale_max`` over that sequence's tokens alone -- ``per_channel_fp8`` of each sequence by itself --
+    in the tile layout the FP8 kernel reads (``sage_prep_v_fp8_varlen``).  With the slab map of a ``varlen_plan`` the statistics run over its
+    512-token slabs, else over ``ceil(max_seqlen_k / 512)`` slabs per sequence: the same bits.  ``ntiles``: a host-known bound of
+    ``cu_tiles[-1]`` (``ceil(sum L / 64) + nseq``) instead of the host synchronisation on the exact count."""
+    v = _aligned(v, 8)
+    T, H, D = v.shape
+    nseq = cu_seqlens_k.shape[0] - 1
+    if ntiles is None:
+        ntiles = int(cu_tiles[-1].item())
+    lib = _cabi.load()
+    mapped = plan is not None and plan.slab_seq is not None
+    nslab_bound = plan.slab_bound if mapped else 0
+    v_image = torch.empty((ntiles, H, D, 64), dtype=torch.uint8, device=v.device)
+    v_scale = torch.empty((nseq, H, D), dtype=torch.float32, device=v.device)
+    ws = torch.empty((int(lib.sage_prep_v_fp8_varlen_ws_floats(nseq, H, int(max_seqlen_k), nslab_bound, D)),), dtype=torch.float32,
+                     device=v.device)
+    rc = lib.sage_prep_v_fp8_varlen(_p(v), _p(v_image), _p(v_scale), _p(ws), _p(cu_seqlens_k), _p(cu_tiles),
+                                    _p(plan.slab_first) if mapped else None, _p(plan.slab_seq) if mapped else None,
+                                    _p(plan.hdr) if mapped else None, nseq, T, int(max_seqlen_k), nslab_bound, H, D, v.stride(0), v.stride(1),
+                                    float(scale_max), _dtype_code(v), _stream(v))
+    _cabi.check(rc, "sage_prep_v_fp8_varlen")
+    return v_image, v_scale
+
+
+@_eager
 def prep_v_fp16_varlen(v: torch.Tensor, cu_seqlens_k: torch.Tensor, cu_tiles: torch.Tensor, max_seqlen_k: int,
                        ntiles: Optional[int] = None) -> torch.Tensor:
     """Packed ``[sum L, H, D]`` V -> tile image ``[cu_tiles[-1], H, D, 64]`` fp16.  ``ntiles``: an upper bound of ``cu_tiles[-1]``

@@ -11,7 +11,7 @@ accumulating into the very same registers; and every non-transcendental instruct
 transcendental (v_exp_f32 ...) in the very next issue slot.  Back-to-back MFMAs are modelled as the matrix pipe issues them (one per `passes` issue
 slots: the wait in front of the second one counts for the first).  It follows the listing and, where MFMAs are still pending at a branch, the branch target too.
 
-    python tools/mfma_hazard_lint.py [unit.hip ...]        (default: the six attention units)"""
+    python tools/mfma_hazard_lint.py [unit.hip ...]        (default: the eight attention units)"""
 import os
 import re
 import shutil
@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "sageattention_amd", "csrc")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 UNITS = ("sage_attn_d128_f8.hip", "sage_attn_d128_f8f.hip", "sage_attn_d128_f16.hip", "sage_attn_d64_f8.hip", "sage_attn_d64_f8f.hip",
-         "sage_attn_d64_f16.hip")
+         "sage_attn_d64_f16.hip", "sage_attn_d128_f8v.hip", "sage_attn_d64_f8v.hip")
 NEED = {"v_mfma_f32_32x32x64_f8f6f4": 19, "v_mfma_scale_f32_32x32x64_f8f6f4": 19}        # 16 passes; everything else used here: 8 passes
 NEED_DEFAULT = 11
 PASSES = {k: 16 for k in NEED}
