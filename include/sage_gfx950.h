@@ -543,6 +543,34 @@ SAGE_API int sage_attn_fused_q_pv_f16_split(const void *q, const int8_t *k, cons
                                             int64_t o_sb, int64_t o_sh, int64_t o_sl,
                                             int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr);
 
+/* The exact split-KV route of sage_attn_fused_q_pv_f8 (fused per-thread Q quantiser, FP8 PV two-level, the exact score form).  The inexact
+ * split above starts every chunk's running maximum at -inf, so every P is rounded to e4m3 against another maximum than in the unsplit call.
+ * The exact route runs in three steps:
+ *   pass 1, sage_split_exact_chunk_max: chunk_max [B, Hkv, kv_split, group, Lq] fp32 (contiguous) receives, per query row and chunk of
+ *     Lk / 64 / kv_split whole 64-key tiles, the row maximum the attention kernel forms over the chunk's visible keys --
+ *     fma(max raw INT32 score, ldexp(sm_scale_log2 (q_scale k_scale), 26) 2^-26, -log2(448)) per k scale group, Q quantised per thread group
+ *     in the prologue exactly as sage_attn_fused_q_pv_f8 does; -inf where the chunk holds no visible key (is_causal: key <= row, global keys);
+ *   pass 2, sage_attn_fused_q_pv_f8_split_exact: tail = 0 runs the kv_split chunks, each with its running maximum started at the maximum of
+ *     chunk_max over the chunks in front of it (the value the unsplit call holds at the chunk's first tile: every P is the unsplit call's), into
+ *     o_part [B, Hq * kv_split, Lq, D] and lse_part [B, Hq * kv_split, Lq] (fp32, contiguous, query head index (hk * kv_split + chunk) * group
+ *     + g: the order of sage_merge_split); tail = 1 (Lk % 64 != 0) runs the keys behind the last whole tile, seeded with the maximum over all
+ *     chunks, into o_part [B, Hq, Lq, D] / lse_part [B, Hq, Lq].  The partials are normalised and scaled by v_scale (+ v_mean); an lse of -inf
+ *     (no visible key, or every P under the seed rounded to zero) weights a chunk 0 in the merge;
+ *   sage_merge_split_f32: the merge of sage_merge_split over the FP32 partials (and the FP32 tail).
+ * q, k, k_scale, v_image, v_scale, v_mean are the operands of the UNSPLIT call ([B, H, L, ...], element strides for q and k; k_scale
+ * [B, Hkv, ceil(Lk / 64) * 4], the V image [B, Hkv, ceil(Lk / 64), D, 64]), read in place.  Only the summation order of O and l differs
+ * from the unsplit call.  The folded score form (SAGE_ATTR_FP8_FOLDED_SCORES) is refused.  No host synchronisation: capturable.
+ * Replaces: nothing in the reference (whose kernels do not split the key range, qk_int_sv_f8_cuda_sm89.cuh:720-738). */
+SAGE_API int sage_split_exact_chunk_max(const void *q, const int8_t *k, const float *k_scale, float *chunk_max,
+                                        int B, int Hq, int Hkv, int kv_split, int Lq, int Lk, int D,
+                                        int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                        int is_causal, float sm_scale_log2, int q_dtype, void *stream);
+SAGE_API int sage_attn_fused_q_pv_f8_split_exact(const void *q, const int8_t *k, const void *v_image, float *o_part, float *lse_part,
+                                                 const float *k_scale, const float *v_scale, const float *v_mean, const float *chunk_max,
+                                                 int B, int Hq, int Hkv, int kv_split, int tail, int Lq, int Lk, int D,
+                                                 int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                                 int is_causal, float sm_scale_log2, int q_dtype, void *stream, const SageLaunchAttr *attr);
+
 /* Merge a partial attention state into a running FP32 state by log-sum-exp (natural log), in place:
  *   m = max(lse_acc, lse_new); w_a = e^(lse_acc-m); w_b = e^(lse_new-m);
  *   o_acc = (o_acc w_a + o_new w_b) / (w_a + w_b);  lse_acc = m + log(w_a + w_b)
@@ -568,6 +596,11 @@ SAGE_API int sage_merge_states(float *o_acc, float *lse_acc, const void *o_new, 
 SAGE_API int sage_merge_split(const void *o_part, const float *lse_part, const void *o_tail, const float *lse_tail,
                               void *o_out, float *lse_out, int B, int S, int H, int group, int L, int D,
                               int64_t o_sb, int64_t o_sh, int64_t o_sl, int out_dtype, void *stream);
+/* sage_merge_split over FP32 partials: o_part [B, Hkv, S, group, L, D] and o_tail [B, H, L, D] (nullable) fp32 contiguous, the rest as there
+ * (the exact split's last step, see sage_attn_fused_q_pv_f8_split_exact).  Replaces: nothing in the reference (see sage_merge_split). */
+SAGE_API int sage_merge_split_f32(const float *o_part, const float *lse_part, const float *o_tail, const float *lse_tail,
+                                  void *o_out, float *lse_out, int B, int S, int H, int group, int L, int D,
+                                  int64_t o_sb, int64_t o_sh, int64_t o_sl, int out_dtype, void *stream);
 
 #ifdef __cplusplus
 }

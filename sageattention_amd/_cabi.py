@@ -127,6 +127,11 @@ SYMBOLS = {   # (the trailing _P of every sage_attn_* entry point is `const Sage
                                                     _L, _L, _L, _L, _L, _L, _L, _I, _F, _I, _I, _I, _P, _P]),
     "sage_merge_states": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _I, _I, _P]),
     "sage_merge_split": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _I, _P]),
+    # the exact split-KV route: pass 1 (chunk maxima), pass 2 (seeded chunks, FP32 partials), the FP32 merge
+    "sage_split_exact_chunk_max": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _I, _F, _I, _P]),
+    "sage_attn_fused_q_pv_f8_split_exact": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I,
+                                                    _L, _L, _L, _L, _L, _L, _I, _F, _I, _P, _P]),
+    "sage_merge_split_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _I, _P]),
 }
 
 

@@ -204,9 +204,11 @@ def _split_kv_plan(B: int, Hq: int, Lq: int, Lk: int, is_causal: bool, override,
     64-key tiles (the quantisation groups and the V image tiles are unchanged by the fold), so only S | Lk/64 is considered.
     ``override``: 0 = never, an integer S >= 2 = that split, "auto" = the plan below, None = ``auto_default``.  The FP16-PV entry point
     plans by default (a split result meets the UNSPLIT oracle at the kernel tolerance: P is rounded to fp16).  The FP8-PV entry points do
-    NOT (round 5): a split changes which running maximum every P is rounded to e4m3 against -- measured rel-RMS up to 2.8e-2 against the
+    NOT (round 5): this split changes which running maximum every P is rounded to e4m3 against -- measured rel-RMS up to 2.8e-2 against the
     unsplit oracle, beyond the 1e-2 that a schedule variant may differ from the exact schedule by and still be a DEFAULT FP8 route
-     -- so there it is opt-in (``split_kv="auto"`` or S), held to 2e-3 against the schedule-matched oracle as before."""
+     -- so there it is opt-in (``split_kv="auto"`` or S), held to 2e-3 against the schedule-matched oracle as before.  The
+    FP8 entry point's exact split (``split_kv_exact=True``, :func:`_split_exact_plan`) seeds every chunk with the unsplit call's running
+    maximum instead: same P, only the FP32 summation order differs."""
     if override is None:
         override = "auto" if auto_default else 0
     if override == 0:
@@ -277,6 +279,84 @@ def _attn_fused_q_split(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_
     return o, lse
 
 
+def _split_exact_plan(B: int, Hq: int, Lq: int, Lk: int, is_causal: bool, override) -> int:
+    """Number of chunks S of the exact split-KV route (``split_kv_exact=True``; 0 = no split).  ``override`` is ``split_kv``: None /
+    "auto" = the inexact route's non-causal plan over the floor(Lk / 64) whole tiles (a ragged rest of the key range becomes a tail chunk,
+    so a ragged Lk is planned too), and no split for causal calls (dense causal splits measured slower, see :func:`_split_kv_plan`); an
+    integer S >= 2 = that split, causal or not, S | floor(Lk / 64); 0 = no split."""
+    if override is None:
+        override = "auto"
+    if override == 0 and not isinstance(override, bool):
+        return 0
+    ntw = Lk // 64
+    if override == "auto":
+        return 0 if is_causal else _split_kv_plan(B, Hq, Lq, ntw * 64, False, "auto")
+    if isinstance(override, bool) or not isinstance(override, int):
+        raise ValueError(f"split_kv={override!r}: 0, an integer >= 2 or 'auto'")
+    if override < 2 or override > ntw or ntw % override != 0:
+        raise ValueError(f"split_kv={override} with split_kv_exact=True must be >= 2 and divide the number of whole 64-key tiles "
+                         f"(kv_len {Lk}: {ntw} tiles)")
+    return override
+
+
+def _split_exact_args(kwargs, qk_quant_gran: str, pv_accum_dtype: str, Lk: int) -> bool:
+    """Whether ``split_kv_exact`` asks for the exact split route; its argument errors (checked before any work).  The route exists for the
+    default FP8 path only -- fused per-thread Q quantiser, two-level accumulation, the exact score form -- and is never swapped for another
+    route behind the caller's back."""
+    if not kwargs.get("split_kv_exact", False):
+        return False
+    if qk_quant_gran != "per_thread" or not kwargs.get("fuse_q_quant", True):
+        raise ValueError("split_kv_exact=True needs qk_quant_gran='per_thread' with the fused Q quantiser")
+    if pv_accum_dtype == "fp32":
+        raise ValueError("split_kv_exact=True needs pv_accum_dtype 'fp32+fp32' or 'fp32+fp16' (two-level accumulation)")
+    if ops.fp8_folded(kwargs.get("fp8_scores")):
+        raise ValueError("split_kv_exact=True takes the exact score form only (fp8_scores='folded' given)")
+    override = kwargs.get("split_kv")
+    if override is not None and override != "auto" and not (override == 0 and not isinstance(override, bool)):
+        _split_exact_plan(1, 1, 1, Lk, False, override)          # (raises on an S that does not divide the whole tiles)
+    return True
+
+
+@torch.compiler.disable
+def _attn_fused_q_split_exact(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, sm_scale_log2, S, return_lse, v_mean=None):
+    """Exact split-KV route of the fused-Q FP8 attention: pass 1 (``sage_split_exact_chunk_max``) computes every chunk's row maxima with
+    the attention kernel's arithmetic, pass 2 (``sage_attn_fused_q_pv_f8_split_exact``) runs the S chunks of floor(Lk / 64) / S whole tiles
+    with their running maximum started at the unsplit call's -- so every P is the unsplit call's -- into FP32 partials, a second launch
+    runs a ragged tail of the key range seeded with the maximum over all chunks, and ``sage_merge_split_f32`` merges them.  The operands
+    of the unsplit call are read in place; no host synchronisation."""
+    B, Hq, Lq, D, q_sb, q_sh, q_sl = _dims(q, tensor_layout)
+    _, Hkv, Lk, _, k_sb, k_sh, k_sl = _dims(k_int8, tensor_layout)
+    group = Hq // Hkv
+    assert v_image.is_contiguous() and k_scale.is_contiguous() and v_scale.is_contiguous()
+    assert k_scale.shape[-1] == ((Lk + 63) // 64) * 4, "per-thread k scales of 64-key tiles"
+    dev = q.device
+    chunk_max = torch.empty((B, Hq * S, Lq), dtype=torch.float32, device=dev)
+    o_part = torch.empty((B, Hq * S, Lq, D), dtype=torch.float32, device=dev)
+    lse_part = torch.empty((B, Hq * S, Lq), dtype=torch.float32, device=dev)
+    code = _cabi.DTYPE_F16 if q.dtype == torch.float16 else _cabi.DTYPE_BF16
+    lib, stream = _cabi.load(), _stream(q)
+    rc = lib.sage_split_exact_chunk_max(_p(q), _p(k_int8), _p(k_scale), _p(chunk_max), B, Hq, Hkv, S, Lq, Lk, D,
+                                        q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, int(is_causal), float(sm_scale_log2), code, stream)
+    _cabi.check(rc, "sage_split_exact_chunk_max")
+    o_tail = lse_tail = None
+    for tail in (0, 1) if Lk % 64 else (0,):
+        if tail:
+            o_tail = torch.empty((B, Hq, Lq, D), dtype=torch.float32, device=dev)
+            lse_tail = torch.empty((B, Hq, Lq), dtype=torch.float32, device=dev)
+        rc = lib.sage_attn_fused_q_pv_f8_split_exact(
+            _p(q), _p(k_int8), _p(v_image), _p(o_tail if tail else o_part), _p(lse_tail if tail else lse_part), _p(k_scale), _p(v_scale),
+            _p(v_mean), _p(chunk_max), B, Hq, Hkv, S, tail, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl,
+            int(is_causal), float(sm_scale_log2), code, stream, None)
+        _cabi.check(rc, "sage_attn_fused_q_pv_f8_split_exact")
+    o = torch.empty(q.shape, dtype=q.dtype, device=dev)
+    _, _, _, _, o_sb, o_sh, o_sl = _dims(o, tensor_layout)
+    lse = torch.empty((B, Hq, Lq), dtype=torch.float32, device=dev) if return_lse else None
+    rc = lib.sage_merge_split_f32(_p(o_part), _p(lse_part), _p(o_tail), _p(lse_tail), _p(o), _p(lse), B, S, Hq, group, Lq, D,
+                                  o_sb, o_sh, o_sl, code, stream)
+    _cabi.check(rc, "sage_merge_split_f32")
+    return o, lse
+
+
 @torch.compiler.disable
 def _attn_masked(q_int8, k_int8, v_image, q_scale, k_scale, attn_mask, out_dtype, tensor_layout, return_lse):
     """Triton-named API with ``attn_mask`` (core.py:313-324): the mask is broadcast to
@@ -324,7 +404,8 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
     if arch.startswith(_SUPPORTED_ARCH_PREFIX):
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32", split_kv=kwargs.get("split_kv"),
-                                            fused_prepass=kwargs.get("fused_prepass"), fp8_scores=kwargs.get("fp8_scores"))
+                                            fused_prepass=kwargs.get("fused_prepass"), fp8_scores=kwargs.get("fp8_scores"),
+                                            split_kv_exact=kwargs.get("split_kv_exact", False))
     raise ValueError(f"Unsupported architecture: {arch} (sageattention_amd targets gfx950 / MI355X only)")
 
 
@@ -551,7 +632,7 @@ def sageattn_qk_int8_pv_fp8_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seql
     return o, lse
 
 
-_ROUTE_KWARGS = ("split_kv", "fused_prepass", "fuse_q_quant", "fp8_scores", "v_in_place")
+_ROUTE_KWARGS = ("split_kv", "fused_prepass", "fuse_q_quant", "fp8_scores", "v_in_place", "split_kv_exact")
 
 
 def _compiled_call(api, q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse,
@@ -559,7 +640,8 @@ def _compiled_call(api, q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_sca
     """torch.compile route of the dense CUDA-named entry points: one opaque custom op around the eager pipeline (ops.py).
     The op takes the default routes; a route override (``split_kv`` / ``fused_prepass`` / ``fuse_q_quant``) cannot travel through
     it, and a compiled run that silently took another route than the eager one would be a trap, so it is refused."""
-    given = [n for n in _ROUTE_KWARGS if kwargs and kwargs.get(n) is not None]
+    # (split_kv_exact=False is the default route: only a truthy flag is an override)
+    given = [n for n in _ROUTE_KWARGS if kwargs and kwargs.get(n) is not None and (n != "split_kv_exact" or kwargs[n])]
     if given:
         raise ValueError(f"{', '.join(given)}: route overrides are not supported under torch.compile (the compiled op takes the default routes)")
     o, lse = ops.sageattn_call(q, k, v, api, tensor_layout, bool(is_causal), qk_quant_gran,
@@ -705,9 +787,16 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     """INT8 QK^T + FP8 (e4m3) PV (reference core.py:636-826).  "fp32+fp32" and "fp32+fp16" both
     run the two-level kernel with an FP32 tile buffer (gfx950's FP8 MFMA only writes FP32, so V
     keeps the full ``scale_max=448``; the reference's 2.25 is an FP16-accumulator artefact,
-    core.py:805-807); "fp32" accumulates every tile straight into the output registers."""
+    core.py:805-807); "fp32" accumulates every tile straight into the output registers.
+
+    ``split_kv_exact=True`` (gfx950 extension, opt-in): calls whose grid would not fill the chip -- few query rows against a long key range --
+    run as key-range chunks whose running maximum starts at the unsplit call's, so every P is the unsplit call's and only the FP32 summation
+    order of O and l differs (``split_kv``: None / "auto" plans S for non-causal calls, an integer S splits so, 0 never; a ragged rest of the
+    key range runs as a tail chunk).  It needs the default path: per-thread granularity with the fused Q quantiser, two-level accumulation,
+    the exact score form; anything else raises ValueError."""
     if torch.compiler.is_compiling():
         return _compiled_call("fp8", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse, kwargs)
+    exact = _split_exact_args(kwargs, qk_quant_gran, pv_accum_dtype, _dims(k, tensor_layout)[2])
     dtype = q.dtype
     _check_inputs(q, k, v)
     assert qk_quant_gran in ["per_warp", "per_thread", "per_block"], "qk_quant_gran must be either 'per_warp' or 'per_thread'."
@@ -731,7 +820,14 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
         lse_correction, _, k_int8, k_scale, v_image, v_scale, vm = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, smooth_v,
                                                                                return_lse, fused)
         B_, Hq_, Lq_, _, _, _, _ = _dims(q, tensor_layout)
-        n_split = _split_kv_plan(B_, Hq_, Lq_, _dims(k, tensor_layout)[2], is_causal, kwargs.get("split_kv"), auto_default=False)
+        if exact:
+            n_split = _split_exact_plan(B_, Hq_, Lq_, _dims(k, tensor_layout)[2], is_causal, kwargs.get("split_kv"))
+            if n_split:
+                o, lse = _attn_fused_q_split_exact(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal,
+                                                   _sm_log2(sm_scale), n_split, return_lse, v_mean=vm)
+                return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
+        else:
+            n_split = _split_kv_plan(B_, Hq_, Lq_, _dims(k, tensor_layout)[2], is_causal, kwargs.get("split_kv"), auto_default=False)
         if n_split:
             o, lse = _attn_fused_q_split(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal,
                                          _sm_log2(sm_scale), n_split, return_lse, v_mean=vm, folded_scores=folded)

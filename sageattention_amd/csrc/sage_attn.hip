@@ -77,6 +77,24 @@ hipError_t launch_attn_fused_q(const AttnParams &p_in, int head_dim, bool causal
     return launch_unit(p, head_dim, pv_fp8, v, nwork, o);
 }
 
+// the exact split's pass 2: grid over (batch, folded head, query block) in head-major order, like the inexact split's
+hipError_t launch_attn_fused_q_seeded(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o)
+{
+    AttnParams p = p_in;
+    p.order_group = 0;
+    p.order_fold = 0;
+    p.order_left = 0;
+    p.sched = nullptr;
+    const int nwork = p.B * p.Hq * p.nqblk;
+    if (o.grid_out != nullptr) *o.grid_out = 0;
+    if (nwork <= 0) return hipSuccess;
+    if (p.cu_q != nullptr || p.v_rows != 0 || (q_dtype != DT_F16 && q_dtype != DT_BF16)) return hipErrorInvalidValue;
+    const AttnVariant v = {causal, true, true, 0, q_dtype == DT_F16 ? 1 : 2, false};
+    if (head_dim == 128) return launch_attn_f8_seeded<128>(p, v, nwork, o);
+    if (head_dim == 64) return launch_attn_f8_seeded<64>(p, v, nwork, o);
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_attn_fused_qblock(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, bool pv_fp8, bool two_level,
                                    const AttnLaunchOpts &o)
 {

@@ -160,8 +160,12 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // 16-lane group element (i & 3) of the four 8-byte chunks that lanes (i >> 2), 4 + (i >> 2), 8 + .., 12 + .. address
 // (tools/microbench/ubench9_tr_b16.hip, profiles/r6_run_c_ubench9_tr_b16.txt).  For fp16 inputs the V half of the pre-pass -- 2/3 of its
 // bytes on an FP16-PV call -- disappears; the outputs are bit-identical to the image route's (same operands, same MFMAs).
+// SEED (FP8 PV, fused per-thread Q, exact score form: pass 2 of the exact split-KV route, units sage_attn_d{128,64}_f8s.hip): launch head
+// hk = hk0 * kv_split + chunk runs keys p.kv_base + chunk * Lk .. + Lk - 1 of kv head hk0 (the operands of the UNSPLIT call, read in place), its
+// running maximum starts from the exclusive prefix maximum of pass 1's chunk maxima (p.seed_max) -- the maximum the unsplit call holds at the
+// chunk's first tile, so every P is the unsplit call's -- and it writes an FP32 normalised partial output [B, Hq * kv_split, Lq, D].
 template <int D, bool PV_FP8, bool CAUSAL, bool KTHREAD, bool TWO_LEVEL, int NH, int MASK = 0, int QF = 0, bool SFOLD = true, bool CPERS = false,
-          bool VROWS = false>
+          bool VROWS = false, bool SEED = false>
 __global__ void __launch_bounds__(256, SAGE_MIN_WAVES(D, MASK))
 sage_attn_kernel(const AttnParams p_arg)
 {
@@ -187,6 +191,8 @@ sage_attn_kernel(const AttnParams p_arg)
     using C = TileCfg<D, PV_FP8, NH>;
     constexpr int KT = C::KT;
     constexpr int NS = 2 * NH;                       // 32-key S^T sub-tiles per iteration
+    static_assert(!SEED || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS),
+                  "the seeded split: FP8 PV, fused per-thread Q, exact score form, dense");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     // (wave index in an SGPR, lane index from v_mbcnt wherever it is needed: nothing derived from threadIdx.x has to stay in a VGPR across
@@ -364,6 +370,19 @@ sage_attn_kernel(const AttnParams p_arg)
         qs_stride = 0;
         ks_ptr = p.k_scale + (long)ks0 * p.Hkv + hk;                  // [sum nblk, Hkv]
         ks_tstride = p.Hkv;
+    } else if constexpr (SEED) {
+        // exact split (pass 2): chunk `chunk` of kv head hk0 starts at key kc0; q, k, its scales and the V image are the unsplit call's
+        const int hk0 = hk / p.kv_split, kc0 = p.kv_base + (hk - hk0 * p.kv_split) * Lk;
+        const long bh0 = (long)b * (p.Hkv / p.kv_split) + hk0;
+        q_off = (long)b * p.q_sb + (long)(hk0 * p.group + (h - hk * p.group)) * p.q_sh;
+        k_off = (long)b * p.k_sb + (long)hk0 * p.k_sh + (long)kc0 * p.k_sl;
+        o_off = (long)b * p.o_sb + (long)h * p.o_sh;
+        v_tile0 = bh0 * (p.nks >> 2) + (kc0 >> 6);      // (per-thread k scales: four per 64-key tile, so nks / 4 tiles per head)
+        v_tstride = 1;
+        qs_ptr = nullptr;
+        qs_stride = 0;
+        ks_ptr = p.k_scale + bh0 * p.nks + (kc0 >> 6) * 4;
+        ks_tstride = 4;
     } else {
         // split-KV (p.kv_split = S > 1): the key range is folded into the kv-head dimension, kv head hk = hk0 * S + chunk and query
         // head h = hk * group + g; the query rows are those of head hk0 * group + g (read in place, no per-chunk copy of Q)
@@ -385,7 +404,8 @@ sage_attn_kernel(const AttnParams p_arg)
     int my_row = row0 + n;                           // (re-derived behind the pipelined loops, see there)
     // causal mask in the chunk's key coordinates (split-KV: this workgroup sees keys kchunk0 .. kchunk0 + Lk - 1 as 0 .. Lk - 1):
     // key <= row  <=>  local key <= row - kchunk0
-    const int kchunk0 = (CAUSAL && p.kv_split > 1 && p.cu_q == nullptr) ? (hk % p.kv_split) * Lk : 0;
+    const int kchunk0 = SEED ? (CAUSAL ? p.kv_base + (hk % p.kv_split) * Lk : 0)
+                             : ((CAUSAL && p.kv_split > 1 && p.cu_q == nullptr) ? (hk % p.kv_split) * Lk : 0);
     const int crow0 = row0 - kchunk0;
     int cmy_row = my_row - kchunk0;
     const int ntk_all = (Lk + BLKK - 1) / BLKK;      // 64-key images that exist
@@ -635,6 +655,17 @@ sage_attn_kernel(const AttnParams p_arg)
         }
     }
 
+    if constexpr (SEED) {
+        // the running maximum the unsplit call holds in front of this chunk: the maximum of pass 1's values for the chunks before it
+        // ([B, Hkv, seed_chunks, group, Lq]; seed_first: the number of pass-1 chunks in front of this launch's chunk 0)
+        if (my_row < Lq) {
+            const int hk0 = hk / p.kv_split;
+            const long gl = (long)p.group * Lq;
+            const float *sm = p.seed_max + ((long)b * (p.Hkv / p.kv_split) + hk0) * p.seed_chunks * gl + (long)(h - hk * p.group) * Lq + my_row;
+            const int c_end = p.seed_first + (hk - hk0 * p.kv_split);
+            for (int c = 0; c < c_end; c++) m_run = fmaxf(m_run, sm[c * gl]);
+        }
+    }
     SAGE_TSTAMP(2);
     ring_wait(n_iters > 1);
     SAGE_TSTAMP(3);
@@ -974,8 +1005,9 @@ sage_attn_kernel(const AttnParams p_arg)
     // per-channel epilogue factors, fetched per 32-wide d tile as straight-line batches of 16-byte
     // vectors (a per-element "load if non-null" makes hipcc branch around every load and wait
     // vmcnt(0) each time: 128 serial L2 round trips per workgroup)
-    const float *vsc = PV_FP8 ? p.v_scale + ((long)b * p.Hkv + hk) * D : nullptr;
-    const float *vmn = (p.v_mean != nullptr) ? p.v_mean + ((long)b * p.Hkv + hk) * D : nullptr;
+    const long vbh = SEED ? (long)b * (p.Hkv / p.kv_split) + hk / p.kv_split : (long)b * p.Hkv + hk;      // (the seeded split: the unsplit kv head)
+    const float *vsc = PV_FP8 ? p.v_scale + vbh * D : nullptr;
+    const float *vmn = (p.v_mean != nullptr) ? p.v_mean + vbh * D : nullptr;
     // every factor of the tile is requested before the first one is used: one exposed memory latency per workgroup
     // instead of one per 32-channel tile (the slot is idle for the co-resident workgroup's sake until this one retires)
     v4f sc4[C::DT][4], mn4[C::DT][4];
@@ -1006,6 +1038,10 @@ sage_attn_kernel(const AttnParams p_arg)
                 if (PV_FP8) x[j] *= sc4[dt][r4][j];
                 x[j] += mn4[dt][r4][j];
             }
+            if constexpr (SEED) {      // FP32 partial rows straight from the registers: four channels per lane
+                if (my_row < Lq) *reinterpret_cast<v4f *>(reinterpret_cast<float *>(p.o) + o_off + (long)my_row * p.o_sl + d0) = v4f{x[0], x[1], x[2], x[3]};
+                continue;
+            }
             v2u pk;
             if (p.out_dtype == DT_F16) {
                 pk[0] = (unsigned)f32_to_f16_rne(x[0]) | ((unsigned)f32_to_f16_rne(x[1]) << 16);
@@ -1021,7 +1057,7 @@ sage_attn_kernel(const AttnParams p_arg)
     }
     // each wave transposes through its OWN 32-row region: its ds_writes and ds_reads execute in order, no workgroup barrier
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    {
+    if constexpr (!SEED) {
         constexpr int LPR = D * 2 / 16;          // lanes per row (16 B each)
         constexpr int RPP = 64 / LPR;            // rows per pass
         unsigned char *obase = reinterpret_cast<unsigned char *>(p.o) + 2 * o_off;

@@ -158,4 +158,20 @@ hipError_t launch_attn_f8_varlen(const AttnParams &p, const AttnVariant &v, int 
     return hipErrorInvalidValue;
 }
 
+// The exact split's pass 2 (sage_attn_kernel's SEED): the fused per-thread Q quantiser (qf 1 / 2), FP8 PV two-level, the exact score form; the
+// running maximum starts from pass 1's prefix maximum and the partial outputs are FP32: the units sage_attn_d{128,64}_f8s.hip.  Split launches
+// take the hardware's dispatch (as the inexact split's do).
+template <int D>
+hipError_t launch_attn_f8_seeded(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
+{
+    using C = TileCfg<D, true, 1>;
+    if (p.seed_max == nullptr || p.cu_q != nullptr || p.kv_split < 1 || l.fp8_folded || !v.kthread || !v.two_level || v.vrows || v.mask_kind != 0)
+        return hipErrorInvalidValue;
+#define SAGE_F8S(C_, F_) if (v.causal == C_ && v.qf == F_) \
+    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, false);
+    SAGE_F8S(false, 1) SAGE_F8S(false, 2) SAGE_F8S(true, 1) SAGE_F8S(true, 2)
+#undef SAGE_F8S
+    return hipErrorInvalidValue;
+}
+
 }  // namespace sage

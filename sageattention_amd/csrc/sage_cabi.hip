@@ -950,6 +950,76 @@ SAGE_API int sage_attn_fused_q_pv_f16_split(const void *q, const int8_t *k, cons
                           attr, false);
 }
 
+// the exact split (pass 1 / pass 2): the checks the two entries share
+static int split_exact_check(const void *q, const int8_t *k, const float *k_scale, int B, int Hq, int Hkv, int kv_split, int Lq, int Lk, int D,
+                             int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl, int q_dtype)
+{
+    SAGE_REQUIRE(q && k && k_scale, "null tensor pointer");
+    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d); pad on the host as core.py:260-271 does", D);
+    SAGE_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Lq > 0 && Lk > 0, "empty problem (B=%d Hq=%d Hkv=%d Lq=%d Lk=%d)", B, Hq, Hkv, Lq, Lk);
+    SAGE_REQUIRE(Hq % Hkv == 0, "num_qo_heads (%d) must be divisible by num_kv_heads (%d)", Hq, Hkv);
+    SAGE_REQUIRE(kv_split >= 1 && Lk / 64 >= kv_split && (Lk / 64) % kv_split == 0,
+                 "kv_split (%d) must divide the number of whole 64-key tiles (%d keys: %d tiles)", kv_split, Lk, Lk / 64);
+    SAGE_REQUIRE((int64_t)B * Hq * kv_split * ((Lq + 127) / 128) < ((int64_t)1 << 31), "grid too large");
+    SAGE_REQUIRE(q_dtype == SAGE_DTYPE_F16 || q_dtype == SAGE_DTYPE_BF16, "bad q_dtype %d", q_dtype);
+    SAGE_REQUIRE(aligned16(q) && aligned16(k), "q/k must be 16-byte aligned");
+    SAGE_REQUIRE(q_sl % 8 == 0 && q_sh % 8 == 0 && q_sb % 8 == 0, "q strides must be multiples of 8 elements");
+    SAGE_REQUIRE(k_sl % 16 == 0 && k_sh % 16 == 0 && k_sb % 16 == 0, "int8 k strides must be multiples of 16");
+    return SAGE_OK;
+}
+
+SAGE_API int sage_split_exact_chunk_max(const void *q, const int8_t *k, const float *k_scale, float *chunk_max,
+                                        int B, int Hq, int Hkv, int kv_split, int Lq, int Lk, int D,
+                                        int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                        int is_causal, float sm_scale_log2, int q_dtype, void *stream)
+{
+    if (const int rc = split_exact_check(q, k, k_scale, B, Hq, Hkv, kv_split, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, q_dtype)) return rc;
+    SAGE_REQUIRE(chunk_max != nullptr, "null chunk_max buffer");
+    sage::ChunkMaxParams p{};
+    p.q = q; p.k = k; p.k_scale = k_scale; p.out = chunk_max;
+    p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv; p.Lq = Lq; p.Lk = Lk; p.D = D;
+    p.S = kv_split; p.tiles = (Lk / 64) / kv_split;
+    p.nks = ((Lk + 63) / 64) * 4;
+    p.q_sb = q_sb; p.q_sh = q_sh; p.q_sl = q_sl; p.k_sb = k_sb; p.k_sh = k_sh; p.k_sl = k_sl;
+    p.sm_scale_log2 = sm_scale_log2; p.q_dtype = q_dtype; p.causal = is_causal != 0;
+    return check_launch(sage::launch_chunk_max(p, reinterpret_cast<hipStream_t>(stream)), "sage_split_exact_chunk_max launch");
+}
+
+SAGE_API int sage_attn_fused_q_pv_f8_split_exact(const void *q, const int8_t *k, const void *v_image, float *o_part, float *lse_part,
+                                                 const float *k_scale, const float *v_scale, const float *v_mean, const float *chunk_max,
+                                                 int B, int Hq, int Hkv, int kv_split, int tail, int Lq, int Lk, int D,
+                                                 int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                                 int is_causal, float sm_scale_log2, int q_dtype, void *stream, const SageLaunchAttr *attr)
+{
+    LaunchAttr la;
+    if (const int rc = read_attr(attr, stream, false, la)) return rc;
+    SAGE_REQUIRE(!la.opts.fp8_folded, "the exact split takes the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES given)");
+    if (const int rc = split_exact_check(q, k, k_scale, B, Hq, Hkv, kv_split, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, q_dtype)) return rc;
+    SAGE_REQUIRE(v_image && v_scale && o_part && lse_part && chunk_max, "null tensor pointer");
+    SAGE_REQUIRE(tail == 0 || tail == 1, "tail must be 0 (the whole chunks) or 1 (the ragged tail), got %d", tail);
+    SAGE_REQUIRE(tail == 0 || Lk % 64 != 0, "tail = 1 needs a ragged key range (Lk = %d is a multiple of 64)", Lk);
+    SAGE_REQUIRE(aligned16(v_image) && aligned16(o_part), "v_image / o_part must be 16-byte aligned");
+    const int nch = tail ? 1 : kv_split;                // chunks of this launch
+    sage::AttnParams p{};
+    p.q = q; p.k = k; p.v = v_image; p.o = o_part; p.lse = lse_part;
+    p.k_scale = k_scale; p.v_scale = v_scale; p.v_mean = v_mean;
+    p.B = B; p.Hq = Hq * nch; p.Hkv = Hkv * nch; p.group = Hq / Hkv;
+    p.Lq = Lq;
+    p.Lk = tail ? Lk % 64 : (Lk / 64 / kv_split) * 64;
+    p.nqblk = (Lq + sage::BLKQ - 1) / sage::BLKQ;
+    p.q_sb = q_sb; p.q_sh = q_sh; p.q_sl = q_sl;
+    p.k_sb = k_sb; p.k_sh = k_sh; p.k_sl = k_sl;
+    p.o_sl = D; p.o_sh = (int64_t)Lq * D; p.o_sb = (int64_t)p.Hq * Lq * D;      // FP32 partials [B, Hq * nch, Lq, D], contiguous
+    p.q_gran = sage::QG_PER_THREAD; p.qs_per_blk = 32;
+    p.nks = ((Lk + 63) / 64) * 4;
+    p.out_dtype = SAGE_DTYPE_F16;        // (unused: FP32 partials)
+    p.sm_scale_log2 = sm_scale_log2;
+    p.kv_split = nch;
+    p.kv_base = tail ? (Lk / 64) * 64 : 0;
+    p.seed_max = chunk_max; p.seed_chunks = kv_split; p.seed_first = tail ? kv_split : 0;
+    return check_launch(sage::launch_attn_fused_q_seeded(p, D, is_causal != 0, q_dtype, la.opts), "sage_attn_fused_q_pv_f8_split_exact launch");
+}
+
 SAGE_API int sage_merge_states(float *o_acc, float *lse_acc, const void *o_new, const float *lse_new, void *o_out,
                                int B, int H, int L, int D, int64_t n_sb, int64_t n_sh, int64_t n_sl,
                                int64_t o_sb, int64_t o_sh, int64_t o_sl, int dtype, int first, void *stream)
@@ -988,6 +1058,26 @@ SAGE_API int sage_merge_split(const void *o_part, const float *lse_part, const v
     p.B = B; p.S = S; p.H = H; p.L = L; p.D = D; p.group = group; p.o_sb = o_sb; p.o_sh = o_sh; p.o_sl = o_sl; p.dtype = out_dtype;
     const hipError_t e = sage::launch_merge_split(p, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(SAGE_ELAUNCH, "sage_merge_split launch: %s", hipGetErrorString(e));
+    return SAGE_OK;
+}
+
+SAGE_API int sage_merge_split_f32(const float *o_part, const float *lse_part, const float *o_tail, const float *lse_tail,
+                                  void *o_out, float *lse_out, int B, int S, int H, int group, int L, int D,
+                                  int64_t o_sb, int64_t o_sh, int64_t o_sl, int out_dtype, void *stream)
+{
+    SAGE_REQUIRE(group > 0 && H % group == 0, "num heads (%d) must be divisible by the GQA group size (%d)", H, group);
+    SAGE_REQUIRE(o_part && lse_part && o_out, "null tensor pointer");
+    SAGE_REQUIRE((o_tail == nullptr) == (lse_tail == nullptr), "o_tail and lse_tail come together");
+    SAGE_REQUIRE(B > 0 && S > 0 && H > 0 && L > 0, "empty problem (B=%d S=%d H=%d L=%d)", B, S, H, L);
+    SAGE_REQUIRE(D > 0 && D % 8 == 0 && D <= 512, "head_dim must be a positive multiple of 8, at most 512 (got %d)", D);
+    SAGE_REQUIRE(out_dtype == SAGE_DTYPE_F16 || out_dtype == SAGE_DTYPE_BF16, "bad out_dtype %d", out_dtype);
+    SAGE_REQUIRE(aligned16(o_part) && aligned16(o_out) && (o_tail == nullptr || aligned16(o_tail)), "o tensors must be 16-byte aligned");
+    SAGE_REQUIRE(o_sb % 8 == 0 && o_sh % 8 == 0 && o_sl % 8 == 0, "o_out strides must be multiples of 8 elements");
+    sage::SplitMergeParams p{};
+    p.o_part = o_part; p.lse_part = lse_part; p.o_tail = o_tail; p.lse_tail = lse_tail; p.o_out = o_out; p.lse_out = lse_out;
+    p.B = B; p.S = S; p.H = H; p.L = L; p.D = D; p.group = group; p.o_sb = o_sb; p.o_sh = o_sh; p.o_sl = o_sl; p.dtype = out_dtype;
+    const hipError_t e = sage::launch_merge_split_f32(p, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(SAGE_ELAUNCH, "sage_merge_split_f32 launch: %s", hipGetErrorString(e));
     return SAGE_OK;
 }
 

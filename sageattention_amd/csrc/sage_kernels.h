@@ -55,6 +55,12 @@ struct AttnParams {
     int order_left;           // (B * Hq) % 8 heads whose query blocks are dealt to all eight XCDs
     unsigned *trace;          // -DSAGE_ATTN_TRACE=1 builds (tools/attn_trace.py): 16 words per logical workgroup, nullable; ignored otherwise
     int trace_wgs;
+    // the exact split's pass 2 (launch_attn_fused_q_seeded; zero / null for every other launch): kv_split chunks of Lk keys from key kv_base on,
+    // folded into the kv-head dimension as above but reading the unsplit operands in place (nks: k scale slots per head of the unsplit call);
+    // seed_max: pass 1's chunk maxima [B, Hkv, seed_chunks, group, Lq], seed_first: the pass-1 chunks in front of this launch's chunk 0
+    const float *seed_max;
+    int seed_chunks, seed_first;
+    int kv_base;
 };
 
 // launch attributes of an attention call that are not kernel parameters (the C ABI's SageLaunchAttr, include/sage_gfx950.h)
@@ -69,6 +75,9 @@ hipError_t launch_attn(const AttnParams &p, int head_dim, bool pv_fp8, bool caus
                        bool two_level, int mask_kind, const AttnLaunchOpts &o);
 // q in fp16 / bf16, quantised per-thread in the kernel prologue; dense only.  FP8 PV: two-level accumulation; FP16 PV: FP32 accumulation
 hipError_t launch_attn_fused_q(const AttnParams &p, int head_dim, bool causal, int q_dtype, bool pv_fp8, const AttnLaunchOpts &o);
+// the exact split's pass 2: q in fp16 / bf16, quantised per thread group in the prologue, FP8 PV two-level, exact score form, running maximum
+// seeded from p.seed_max, FP32 partial outputs (p.o) and log2-domain LSEs (p.lse) per chunk; p.kv_split >= 1 chunks of p.Lk keys from p.kv_base
+hipError_t launch_attn_fused_q_seeded(const AttnParams &p, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o);
 // q in fp16 / bf16, quantised per 128-row block in the prologue after the multiplication by p.q_premul; per-block k scales.  FP16 PV in
 // the Triton kernels' form, dense or varlen (p.cu_q); FP8 PV (varlen only, the exact score form): two_level or single accumulation
 hipError_t launch_attn_fused_qblock(const AttnParams &p, int head_dim, bool causal, int q_dtype, bool pv_fp8, bool two_level,
@@ -236,5 +245,23 @@ struct SplitMergeParams {
     int cpr_pad;              // set by the launcher
 };
 hipError_t launch_merge_split(const SplitMergeParams &p, hipStream_t stream);
+// the same merge over FP32 partials (o_part, o_tail: float; the exact split's pass 2 writes them)
+hipError_t launch_merge_split_f32(const SplitMergeParams &p, hipStream_t stream);
+
+// ---- the exact split's pass 1: per (batch, query head, query row, chunk) the row maximum the attention kernel forms over the chunk's keys ---------
+struct ChunkMaxParams {
+    const void *q;            // fp16 / bf16 [B, Hq, Lq, D] (element strides), quantised per thread group exactly as the fused-Q kernels do
+    const int8_t *k;          // INT8 K of the unsplit call (strides in bytes = elements), per-thread k scales [B, Hkv, nks]
+    const float *k_scale;
+    float *out;               // [B, Hkv, S, group, Lq]: fma(max raw score, c, -log2(448)) over the chunk's visible keys, -inf where none is
+    int B, Hq, Hkv, group, Lq, Lk, D;
+    int S, tiles;             // chunks, 64-key tiles per chunk (chunk c: tiles c * tiles .. + tiles - 1)
+    int nqblk, nks;
+    long q_sb, q_sh, q_sl;
+    long k_sb, k_sh, k_sl;
+    float sm_scale_log2;
+    int q_dtype, causal;
+};
+hipError_t launch_chunk_max(const ChunkMaxParams &p, hipStream_t stream);
 
 }  // namespace sage

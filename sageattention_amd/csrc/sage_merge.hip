@@ -80,8 +80,26 @@ merge_states_kernel(const MergeParams p)
 // order the attention kernel wrote them with the KV chunks folded into the kv-head dimension: [B, Hkv, S, group, L, D]
 // (query head h = hk * group + g), and their log-sum-exps (log2 domain, as the kernel leaves them) [B, Hkv, S, group, L];
 // an optional (S+1)-th chunk (a ragged tail of the key range computed by a second launch) comes as [B, H, L, D] / [B, H, L].
-// One thread owns 8 channels of one row.
-template <int DT>
+// One thread owns 8 channels of one row.  PT: the element type of the partial outputs -- uint16_t (fp16, sage_merge_split) or float (the exact
+// split's FP32 partials, sage_merge_split_f32; same arithmetic)
+template <typename PT>
+__device__ __forceinline__ void ld_part8(const PT *src, float (&x)[8])
+{
+    if constexpr (sizeof(PT) == 4) {
+        const v4f a = *reinterpret_cast<const v4f *>(src), b = *reinterpret_cast<const v4f *>(src + 4);
+#pragma unroll
+        for (int j = 0; j < 4; j++) { x[j] = a[j]; x[4 + j] = b[j]; }
+    } else {
+        const v4u raw = *reinterpret_cast<const v4u *>(src);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const unsigned wd = raw[j >> 1];
+            x[j] = f16_to_f32((uint16_t)((j & 1) ? (wd >> 16) : (wd & 0xffffu)));
+        }
+    }
+}
+
+template <int DT, typename PT>
 __global__ void __launch_bounds__(256)
 merge_split_kernel(const SplitMergeParams p)
 {
@@ -98,26 +116,24 @@ merge_split_kernel(const SplitMergeParams p)
     const long HL = (long)p.group * p.L;                                              // chunk stride in rows
     const long r0 = (((long)b * (p.H / p.group) + hk) * p.S) * HL + (long)gq * p.L + l;   // row of chunk 0
     const float *la = p.lse_part + r0;                                                // + s * HL
-    const uint16_t *oa = reinterpret_cast<const uint16_t *>(p.o_part) + r0 * p.D + c8;
+    const PT *oa = reinterpret_cast<const PT *>(p.o_part) + r0 * p.D + c8;
     const bool tail = p.o_tail != nullptr;
     const float lt = tail ? p.lse_tail[row] : -INFINITY;
     float m = lt;
     for (int s = 0; s < p.S; s++) m = fmaxf(m, la[(long)s * HL]);
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, wsum = 0.0f;
-    auto add = [&](const uint16_t *src, float lse) {
+    auto add = [&](const PT *src, float lse) {
         if (lse == -INFINITY) return;                       // chunk with no visible key for this row
         const float w = __builtin_amdgcn_exp2f(lse - m);
-        const v4u raw = *reinterpret_cast<const v4u *>(src);
+        float x[8];
+        ld_part8(src, x);
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const unsigned wd = raw[j >> 1];
-            acc[j] += w * f16_to_f32((uint16_t)((j & 1) ? (wd >> 16) : (wd & 0xffffu)));
-        }
+        for (int j = 0; j < 8; j++) acc[j] += w * x[j];
         wsum += w;
     };
     if (m != -INFINITY) {
         for (int s = 0; s < p.S; s++) add(oa + (long)s * HL * p.D, la[(long)s * HL]);
-        if (tail) add(reinterpret_cast<const uint16_t *>(p.o_tail) + row * p.D + c8, lt);
+        if (tail) add(reinterpret_cast<const PT *>(p.o_tail) + row * p.D + c8, lt);
     }
     const float inv = wsum > 0.0f ? 1.0f / wsum : 0.0f;
     uint16_t *oo = reinterpret_cast<uint16_t *>(p.o_out) + (long)b * p.o_sb + (long)h * p.o_sh + (long)l * p.o_sl + c8;
@@ -128,7 +144,8 @@ merge_split_kernel(const SplitMergeParams p)
     if (p.lse_out != nullptr && c8 == 0) p.lse_out[row] = wsum > 0.0f ? m + __builtin_amdgcn_logf(wsum) : -INFINITY;   // v_log_f32 = log2
 }
 
-hipError_t launch_merge_split(const SplitMergeParams &p, hipStream_t stream)
+template <typename PT>
+static hipError_t merge_split(const SplitMergeParams &p, hipStream_t stream)
 {
     const long rows = (long)p.B * p.H * p.L;
     if (rows <= 0) return hipSuccess;
@@ -138,10 +155,13 @@ hipError_t launch_merge_split(const SplitMergeParams &p, hipStream_t stream)
     if (q.cpr_pad > 64) return hipErrorInvalidValue;
     const long rpb = 256 / q.cpr_pad;
     const dim3 grid((unsigned)((rows + rpb - 1) / rpb));
-    if (p.dtype == DT_F16) hipLaunchKernelGGL(merge_split_kernel<DT_F16>, grid, dim3(256), 0, stream, q);
-    else hipLaunchKernelGGL(merge_split_kernel<DT_BF16>, grid, dim3(256), 0, stream, q);
+    if (p.dtype == DT_F16) hipLaunchKernelGGL((merge_split_kernel<DT_F16, PT>), grid, dim3(256), 0, stream, q);
+    else hipLaunchKernelGGL((merge_split_kernel<DT_BF16, PT>), grid, dim3(256), 0, stream, q);
     return hipGetLastError();
 }
+
+hipError_t launch_merge_split(const SplitMergeParams &p, hipStream_t stream) { return merge_split<uint16_t>(p, stream); }
+hipError_t launch_merge_split_f32(const SplitMergeParams &p, hipStream_t stream) { return merge_split<float>(p, stream); }
 
 hipError_t launch_merge_states(const MergeParams &p, hipStream_t stream)
 {
