@@ -35,6 +35,28 @@ def get_gcn_arch(device: torch.device) -> str:
     return torch.cuda.get_device_properties(device).gcnArchName.split(":")[0]
 
 
+def _check_shapes(q, k, v, tensor_layout: Optional[str] = "HND", cu_seqlens_q=None, cu_seqlens_k=None):
+    """Refuse operands that do not agree, before any launch: the C ABI takes raw pointers and one set of sizes, so a ``v`` with fewer tokens
+    or heads than ``k`` would be read past its end (the reference refuses at its op boundary, ``CHECK_SHAPE(value, ...)``,
+    qk_int_sv_f16_cuda_sm80.cu:731-751).  Dense (``tensor_layout`` "HND" / "NHD"): k and v agree in batch, kv-head count, length and head
+    dim, q and k in batch and head dim.  Packed (``tensor_layout=None``, ``[sum L, H, D]``): k and v have one shape, q and k one head dim,
+    the two prefix arrays one length.  That ``cu_seqlens_*[-1]`` stays within the packed rows is NOT checked: it would take a device-to-host
+    read on every call and break graph capture."""
+    if tensor_layout is None:
+        assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3, f"packed q, k, v must be [sum L, H, D] (got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})"
+        assert k.shape == v.shape, f"k and v must have the same shape (got k {tuple(k.shape)}, v {tuple(v.shape)})"
+        assert q.shape[2] == k.shape[2], f"q and k must have the same head_dim (got q {tuple(q.shape)}, k {tuple(k.shape)})"
+        assert cu_seqlens_q.dim() == 1 and cu_seqlens_q.shape == cu_seqlens_k.shape, \
+            f"cu_seqlens_q and cu_seqlens_k must be 1-D and of one length (got {tuple(cu_seqlens_q.shape)}, {tuple(cu_seqlens_k.shape)})"
+        return
+    assert q.dim() == 4 and k.dim() == 4 and v.dim() == 4, f"q, k, v must be 4-D (got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})"
+    qB, _, _, qD = _dims(q, tensor_layout)[:4]
+    kB, kH, kL, kD = _dims(k, tensor_layout)[:4]
+    assert (kB, kH, kL, kD) == _dims(v, tensor_layout)[:4], \
+        f"k and v must agree in batch, kv-head count, length and head_dim (got k {tuple(k.shape)}, v {tuple(v.shape)}, layout {tensor_layout})"
+    assert (qB, qD) == (kB, kD), f"q and k must agree in batch and head_dim (got q {tuple(q.shape)}, k {tuple(k.shape)}, layout {tensor_layout})"
+
+
 def _check_inputs(q, k, v):
     dtype = q.dtype
     assert q.is_cuda, "Input tensors must be on cuda."
@@ -397,6 +419,7 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
     (the reference's sm90 choice, ``pv_accum_dtype="fp32+fp32"``).  Extra SDPA-style kwargs
     (``attn_mask=``, ``dropout_p=``, ``scale=`` ...) are accepted and ignored exactly as the
     reference ignores them."""
+    _check_shapes(q, k, v, tensor_layout)      # (again in the entry point called below: this one is in front of the device query)
     if torch.compiler.is_compiling():      # the device query is not traceable; the opaque op checks the device when it runs
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32")
@@ -418,6 +441,7 @@ def sageattn_qk_int8_pv_fp16_triton(q, k, v, tensor_layout: str = "HND", quantiz
     here, the same HIP kernel family runs it)."""
     dtype = q.dtype
     _check_inputs(q, k, v)
+    _check_shapes(q, k, v, tensor_layout)
     if attn_mask is not None:
         assert attn_mask.dtype == torch.bool or attn_mask.dtype == q.dtype, "attn_mask must be of dtype bool or the same dtype as q."
         assert attn_mask.device == q.device, "All tensors must be on the same device."
@@ -433,7 +457,7 @@ def sageattn_qk_int8_pv_fp16_triton(q, k, v, tensor_layout: str = "HND", quantiz
     v_rows = fuse_q and _v_rows_wanted(q, k, v, tensor_layout, is_causal, kwargs.get("v_in_place"))
     # K mean + INT8 K (Triton rounding) + the fp16 V image as ONE launch that reads K and V once (sage_prepass_kv), when it is the faster route
     k_done = v_image = None
-    if quantization_backend == "triton" and k.shape == v.shape and _fused_prepass_wanted(k, tensor_layout, kwargs.get("fused_prepass")):
+    if quantization_backend == "triton" and _fused_prepass_wanted(k, tensor_layout, kwargs.get("fused_prepass")):
         km_s, k8, ks, v_image, _, _ = prepass_kv_fp8(k, None if v_rows else v, tensor_layout, smooth_k=smooth_k, qk_quant_gran="per_block_triton",
                                                      v_fp16=True)
         k_done = (k8, ks)
@@ -480,6 +504,7 @@ def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     st = _VarlenState()
     st.dtype = q.dtype
     _check_inputs(q, k, v)
+    _check_shapes(q, k, v, None, cu_seqlens_q, cu_seqlens_k)
     torch.cuda.set_device(v.device)
     q, k, v, st.head_dim_og = _pad_head_dim(q, k, v)
     assert q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1, "Last dim of qkv must be contiguous."
@@ -501,7 +526,7 @@ def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     fused = kwargs.get("fused_prepass")
     if fused is None:
         fused = os.environ.get("SAGE_PREPASS", "") not in ("seq", "sequence", "0")
-    fused = bool(fused) and k.shape == v.shape and prepass_varlen_fused_ok(k, plan, max_seqlen_k, smooth_k)
+    fused = bool(fused) and prepass_varlen_fused_ok(k, plan, max_seqlen_k, smooth_k)
     st.v_scale = None
     if fused:
         st.km, st.k_int8, st.k_scale, st.v_image = prepass_kv_varlen(k, None if v_fp8 else v, cu_k, plan, max_seqlen_k, smooth_k=smooth_k)
@@ -735,6 +760,7 @@ def sageattn_qk_int8_pv_fp16_cuda(q, k, v, tensor_layout: str = "HND", is_causal
         return _compiled_call("fp16", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse, kwargs)
     dtype = q.dtype
     _check_inputs(q, k, v)
+    _check_shapes(q, k, v, tensor_layout)
     assert qk_quant_gran in ["per_warp", "per_thread", "per_block"], "qk_quant_gran must be either 'per_warp' or 'per_thread'."
     if pv_accum_dtype not in ("fp32", "fp16", "fp16+fp32"):
         raise ValueError(f"Unsupported pv_accum_dtype: {pv_accum_dtype}")
@@ -757,7 +783,7 @@ def sageattn_qk_int8_pv_fp16_cuda(q, k, v, tensor_layout: str = "HND", is_causal
     # fp16 inputs on that route: the kernel reads V's rows in place, no V image and no V half of the pre-pass (core.py:613's
     # `v.to(torch.float16)` is the identity for them); same bits as the image route
     v_rows = fuse_q and not n_split and not smooth_v and _v_rows_wanted(q, k, v, tensor_layout, is_causal, kwargs.get("v_in_place"))
-    v_in_prepass = fused and not smooth_v and k.shape == v.shape and not v_rows          # the fp16 image comes out of the same launch as K
+    v_in_prepass = fused and not smooth_v and not v_rows          # the fp16 image comes out of the same launch as K
     lse_correction, _, k_int8, k_scale, v_image, _, _ = _prepass_kv(q, k, v, tensor_layout, qk_quant_gran, 64, smooth_k, False, return_lse,
                                                                     fused, v_fp8=False, v_fp16=v_in_prepass)
     vm = None
@@ -796,6 +822,7 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     the exact score form; anything else raises ValueError."""
     if torch.compiler.is_compiling():
         return _compiled_call("fp8", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse, kwargs)
+    _check_shapes(q, k, v, tensor_layout)
     exact = _split_exact_args(kwargs, qk_quant_gran, pv_accum_dtype, _dims(k, tensor_layout)[2])
     dtype = q.dtype
     _check_inputs(q, k, v)
@@ -811,7 +838,7 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
         warnings.warn(f"pv_accum_dtype is '{pv_accum_dtype}', smooth_v will be ignored.")   # core.py:797-803
         smooth_v = False
     fuse_q = qk_quant_gran == "per_thread" and pv_accum_dtype != "fp32" and kwargs.get("fuse_q_quant", True)
-    fused = _fused_prepass_wanted(k, tensor_layout, kwargs.get("fused_prepass")) and k.shape == v.shape
+    fused = _fused_prepass_wanted(k, tensor_layout, kwargs.get("fused_prepass"))
     folded = ops.fp8_folded(kwargs.get("fp8_scores"))
     if fuse_q:
         # default route: Q is quantised inside the attention kernel (same bits, no INT8 copy of Q in HBM).
@@ -858,13 +885,14 @@ def sageattn_qk_int8_pv_fp8_cuda_sm90(q, k, v, tensor_layout: str = "HND", is_ca
         return _compiled_call("sm90", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, False, return_lse, kwargs)
     dtype = q.dtype
     _check_inputs(q, k, v)
+    _check_shapes(q, k, v, tensor_layout)
     assert qk_quant_gran in ["per_warp", "per_thread"], "qk_quant_gran must be either 'per_warp' or 'per_thread'."
     torch.cuda.set_device(v.device)
     q, k, v, head_dim_og = _pad_head_dim(q, k, v)
     assert q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1, "Last dim of qkv must be contiguous."
     if sm_scale is None:
         sm_scale = head_dim_og ** -0.5
-    fused = _fused_prepass_wanted(k, tensor_layout, kwargs.get("fused_prepass")) and k.shape == v.shape
+    fused = _fused_prepass_wanted(k, tensor_layout, kwargs.get("fused_prepass"))
     lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, qk_quant_gran, 128, smooth_k, False,
                                                                           return_lse, fused)
     q_int8, q_scale, gran, q_warp, sm_log2 = _quant_q(q, qk_quant_gran, tensor_layout, 16, sm_scale, blkk=128)

@@ -36,6 +36,8 @@ def forward(q, k, v, q_scale, k_scale, tensor_layout: str = "HND", attn_mask: Op
     B, Hq, Hkv, Lq, Lk = q.shape[0], q.shape[3 - seq], k.shape[3 - seq], q.shape[seq], k.shape[seq]
     assert Hq % Hkv == 0, "num_qo_heads must be divisible by num_kv_heads"
     assert q.shape[-1] in (64, 128), "head_dim 64 or 128 (core.py:260-271 pads before quantising)"
+    from .core import _check_shapes, _v_rows_ok
+    _check_shapes(q, k, v, tensor_layout)         # (v shorter or with fewer heads than k would be read past its end)
     q, k = q.contiguous(), k.contiguous()
     qs = _scales(q_scale, (B, Hq, (Lq + 127) // 128))
     ks = _scales(k_scale, (B, Hkv, (Lk + 63) // 64))
@@ -45,7 +47,7 @@ def forward(q, k, v, q_scale, k_scale, tensor_layout: str = "HND", attn_mask: Op
         o, lse = _attn_masked(q, k, prep_v_fp16(v, tensor_layout), qs, ks, attn_mask, output_dtype, tensor_layout, return_lse)
         return o, (lse if return_lse else _no_lse(q.device))
     o = torch.empty(q.shape, dtype=output_dtype, device=q.device)
-    in_place = v.stride(-1) == 1 and v.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in v.stride()[:-1])
+    in_place = _v_rows_ok(v, tensor_layout)       # rows of 16 bytes that do not overlap, within 2 GiB per head; else the tile image (same bits)
     lse = ops.qk_int8_sv_f16_attn_impl(q, k, v if in_place else prep_v_fp16(v, tensor_layout), o, qs, ks, None, 0 if tensor_layout == "NHD" else 1,
                                        int(is_causal), _cabi.GRAN_PER_BLOCK, 128, 1.0, _cabi.PV_ACCUM_TRITON, int(return_lse))
     return o, (lse if return_lse else _no_lse(q.device))
@@ -64,6 +66,8 @@ def forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, q_scale, k
     assert output_dtype in (torch.float16, torch.bfloat16)
     Hq, Hkv, D = q.shape[1], k.shape[1], q.shape[2]
     assert Hq % Hkv == 0 and D in (64, 128)
+    from .core import _check_shapes
+    _check_shapes(q, k, v, None, cu_seqlens_q, cu_seqlens_k)
     q, k = q.contiguous(), k.contiguous()
     cu_q, cu_k = cu_seqlens_q.to(torch.int32).contiguous(), cu_seqlens_k.to(torch.int32).contiguous()
     cu_qs, cu_ks = cu_seqlens_q_scale.to(torch.int32).contiguous(), cu_seqlens_k_scale.to(torch.int32).contiguous()

@@ -12,6 +12,7 @@ Bars (stated here, used below):
     one bf16 ulp more for bf16 outputs (the CPU interpreter truncates fp32->bf16).
   * vs fp32 SDPA on randn inputs: cos >= 0.9995 / rel-RMSE <= 2% (FP16 PV), cos >= 0.999 / <= 5% (FP8 PV).
 """
+import ctypes
 import json
 import os
 
@@ -25,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     import sageattention_amd as sa
-    from sageattention_amd import _cabi, ops as sa_ops, quant as sq
+    from sageattention_amd import _cabi, core as sc_core, kernel_api, ops as sa_ops, quant as sq
     DEV = torch.device("cuda:0")
     # the FP8 score form the product runs by default: "exact", the reference's formula (SAGE_FP8_SCORES=folded runs the whole suite on the
     # opt-in variant against the oracle mode that mirrors it).  Every default-route comparison below is against the EXACT oracle.
@@ -911,6 +912,62 @@ def test_errors_match_reference_contract():
     kh = torch.zeros(1, 2, 64, 64, dtype=torch.float16, device=DEV)
     with pytest.raises((AssertionError, ValueError)):
         sa.sageattn(qh, kh, kh)
+    # operands that do not agree are refused before anything is launched (the C ABI takes raw pointers: a short v would be read past its end)
+    probe = ctypes.c_int32(-1)
+    h = lambda *shape: torch.zeros(*shape, dtype=torch.float16, device=DEV)
+    dense = (sa.sageattn, sa.sageattn_qk_int8_pv_fp8_cuda, sa.sageattn_qk_int8_pv_fp8_cuda_sm90, sa.sageattn_qk_int8_pv_fp16_cuda,
+             sa.sageattn_qk_int8_pv_fp16_triton)
+    bad = {"HND": [("v shorter", h(2, 4, 200, 64), h(2, 2, 200, 64), h(2, 2, 136, 64)),
+                   ("v with fewer heads", h(2, 4, 200, 64), h(2, 2, 200, 64), h(2, 1, 200, 64)),
+                   ("batch mismatch", h(2, 4, 200, 64), h(1, 2, 200, 64), h(1, 2, 200, 64)),
+                   ("v of another head_dim", h(2, 4, 200, 64), h(2, 2, 200, 64), h(2, 2, 200, 128)),
+                   ("q of another head_dim", h(2, 4, 200, 128), h(2, 2, 200, 64), h(2, 2, 200, 64))],
+           "NHD": [("v shorter", h(2, 200, 4, 64), h(2, 200, 2, 64), h(2, 136, 2, 64)),
+                   ("v with fewer heads", h(2, 200, 4, 64), h(2, 200, 2, 64), h(2, 200, 1, 64))]}
+    with sa_ops.launch_hooks(grid_probe=probe):
+        for layout, cases in bad.items():
+            for what, qb, kb, vb in cases:
+                for fn in dense:
+                    with pytest.raises(AssertionError, match=r"must agree in .*\(got "):
+                        fn(qb, kb, vb, tensor_layout=layout)
+                    assert probe.value == -1, f"{fn.__name__}, {what}: an attention kernel was launched"
+        cu = torch.tensor([0, 100, 200], dtype=torch.int32, device=DEV)
+        pq, pk = h(200, 4, 64), h(200, 2, 64)
+        for fn in (sa.sageattn_varlen, sa.sageattn_qk_int8_pv_fp8_varlen):
+            with pytest.raises(AssertionError, match=r"k and v must have the same shape \(got k \(200, 2, 64\), v \(136, 2, 64\)\)"):
+                fn(pq, pk, h(136, 2, 64), cu, cu, 100, 100)                     # a packed v with fewer rows
+            with pytest.raises(AssertionError, match="same shape"):
+                fn(pq, pk, h(200, 1, 64), cu, cu, 100, 100)
+            with pytest.raises(AssertionError, match="same head_dim"):
+                fn(h(200, 4, 128), pk, pk, cu, cu, 100, 100)
+            with pytest.raises(AssertionError, match="of one length"):
+                fn(pq, pk, pk, cu, cu[:2], 100, 100)
+            assert probe.value == -1, f"{fn.__name__}: an attention kernel was launched"
+        # the kernel-level entry: a v shorter than k (it would be read in place, past its end)
+        q8, k8 = torch.zeros(1, 2, 200, 64, dtype=torch.int8, device=DEV), torch.zeros(1, 2, 200, 64, dtype=torch.int8, device=DEV)
+        with pytest.raises(AssertionError, match="must agree in"):
+            kernel_api.forward(q8, k8, h(1, 2, 136, 64), torch.ones(1, 2, 2, device=DEV), torch.ones(1, 2, 4, device=DEV))
+        assert probe.value == -1
+
+
+def test_kernel_level_forward_takes_an_expanded_v_by_the_image_route():
+    """A V whose rows cannot be read in place -- ``expand``ed along the sequence, stride 0 -- goes through the tile image instead of being refused
+    by the C ABI: the bits of the same call on its ``.contiguous()`` copy (which reads the rows in place)."""
+    q, k, _ = rand_qkv(1, 4, 2, 200, 333, 64, 0, seed=41, kbias=1.0)
+    g = torch.Generator().manual_seed(42)
+    for layout in ("HND", "NHD"):
+        qd, kd = to_dev(q, layout), to_dev(k, layout)
+        row = torch.randn((1, 2, 1, 64) if layout == "HND" else (1, 1, 2, 64), generator=g).half().to(DEV)
+        v = row.expand(kd.shape)
+        assert v.stride(2 if layout == "HND" else 1) == 0 and not sc_core._v_rows_ok(v, layout) and sc_core._v_rows_ok(v.contiguous(), layout)
+        q8, qs, k8, ks = sq.per_block_int8(qd, kd, km=sq.channel_mean(kd, layout).unsqueeze(2 if layout == "HND" else 1), tensor_layout=layout)
+        o, lse = kernel_api.forward(q8, k8, v, qs, ks, tensor_layout=layout, return_lse=True)
+        o2, lse2 = kernel_api.forward(q8, k8, v.contiguous(), qs, ks, tensor_layout=layout, return_lse=True)
+        torch.cuda.synchronize()
+        assert torch.isfinite(o.float()).all() and torch.equal(o, o2) and torch.equal(lse, lse2)
+        # every key has the same value row: the output is that row, whatever the weights (to the kernel bar of this file, 2e-3 max|o|)
+        want = to_hnd(row, layout).float().repeat_interleave(2, dim=1).expand(to_hnd(o, layout).shape)
+        assert (to_hnd(o, layout).float() - want).abs().max().item() <= 2e-3 * want.abs().max().item()
 
 
 def test_non_default_stream_and_reentrancy():

@@ -49,6 +49,37 @@ def test_cpu_tensors_are_rejected_not_emulated():
             fn(q, q, q)
 
 
+def test_operands_that_do_not_agree_are_refused_by_shape_alone():
+    """``core._check_shapes`` (called by every public entry point in front of any device work): k and v agree in batch, kv-head count, length and
+    head dim, q and k in batch and head dim; packed: k and v one shape, one head dim, prefix arrays of one length.  The messages name both shapes."""
+    h = lambda *s: torch.zeros(*s, dtype=torch.float16)
+    core._check_shapes(h(2, 4, 200, 64), h(2, 2, 333, 64), h(2, 2, 333, 64), "HND")            # GQA, cross lengths: fine
+    core._check_shapes(h(2, 200, 4, 64), h(2, 333, 2, 64), h(2, 333, 2, 64), "NHD")
+    bad = [("HND", h(2, 4, 200, 64), h(2, 2, 200, 64), h(2, 2, 136, 64), r"k \(2, 2, 200, 64\), v \(2, 2, 136, 64\)"),       # v shorter
+           ("HND", h(2, 4, 200, 64), h(2, 2, 200, 64), h(2, 1, 200, 64), r"k \(2, 2, 200, 64\), v \(2, 1, 200, 64\)"),       # v with fewer heads
+           ("NHD", h(2, 200, 4, 64), h(2, 200, 2, 64), h(2, 136, 2, 64), r"v \(2, 136, 2, 64\), layout NHD"),
+           ("HND", h(2, 4, 200, 64), h(2, 2, 200, 64), h(1, 2, 200, 64), "k and v must agree"),                              # batch
+           ("HND", h(2, 4, 200, 64), h(2, 2, 200, 64), h(2, 2, 200, 128), "k and v must agree"),                             # head dim
+           ("HND", h(2, 4, 200, 64), h(1, 2, 200, 64), h(1, 2, 200, 64), r"q and k must agree.*q \(2, 4, 200, 64\), k \(1, 2, 200, 64\)"),
+           ("HND", h(2, 4, 200, 128), h(2, 2, 200, 64), h(2, 2, 200, 64), "q and k must agree"),
+           ("HND", h(4, 200, 64), h(2, 200, 64), h(2, 200, 64), "must be 4-D")]
+    for layout, q, k, v, msg in bad:
+        with pytest.raises(AssertionError, match=msg):
+            core._check_shapes(q, k, v, layout)
+        if q.dim() == 4:
+            with pytest.raises(AssertionError, match=msg):          # in front of the device query of the dispatching entry point
+                sa.sageattn(q, k, v, tensor_layout=layout)
+    cu = torch.tensor([0, 100, 200], dtype=torch.int32)
+    core._check_shapes(h(200, 4, 64), h(300, 2, 64), h(300, 2, 64), None, cu, cu)
+    for q, k, v, cq, ck, msg in [(h(200, 4, 64), h(200, 2, 64), h(136, 2, 64), cu, cu, r"same shape \(got k \(200, 2, 64\), v \(136, 2, 64\)\)"),
+                                 (h(200, 4, 64), h(200, 2, 64), h(200, 1, 64), cu, cu, "same shape"),
+                                 (h(200, 4, 128), h(200, 2, 64), h(200, 2, 64), cu, cu, "same head_dim"),
+                                 (h(200, 4, 64), h(200, 2, 64), h(200, 2, 64), cu, cu[:2], r"of one length \(got \(3,\), \(2,\)\)"),
+                                 (h(1, 200, 4, 64), h(200, 2, 64), h(200, 2, 64), cu, cu, r"\[sum L, H, D\]")]:
+        with pytest.raises(AssertionError, match=msg):
+            core._check_shapes(q, k, v, None, cq, ck)
+
+
 def test_pad_head_dim_rules():
     for d, want in ((32, 64), (64, 64), (96, 128), (128, 128)):
         q = torch.zeros(1, 1, 4, d, dtype=torch.float16)
