@@ -35,6 +35,7 @@ extern "C" {
 /* Changes (newest first):
  *   22  FP8 PV for packed (varlen) batches: sage_prep_v_fp8_varlen (+ _ws_floats), sage_attn_qk_int8_pv_f8_varlen,
  *       sage_attn_fused_qblock_pv_f8_varlen.  Nothing else changed.
+ *       (added since, no existing entry changed: the exact split-KV entries; the per-sample key lengths entries sage_*_kvlens)
  *   21  sage_attn_qk_int8_pv_f16_vrows (INT8 q / k, V read in place).
  *   20  the exact FP8 score form is the default; SageLaunchAttr.struct_bytes = 0 is refused; launch workspaces re-arm themselves;
  *       sage_attn_fused_q*_pv_f16_vrows. */
@@ -444,6 +445,36 @@ SAGE_API int sage_attn_fused_q_pv_f8(const void *q, const int8_t *k, const void 
                                      int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
                                      int64_t o_sb, int64_t o_sh, int64_t o_sl,
                                      int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr);
+
+/* Per-sample key lengths for a dense, right-padded batch (added under ABI 22; Python: kv_lens=).  kv_lens: int32 [B] in device memory, read
+ * by the kernels only -- no host read, no synchronisation, so a captured graph follows the array's contents -- and clamped there to
+ * [0, L].  Sample b uses rows 0 .. kv_lens[b] - 1 of its keys and values and nothing behind them: rows, scale slots and V tiles past the
+ * length are never read (they may be uninitialised memory), and every result of sample b is, bit for bit, what the plain entries give on the
+ * sample's first kv_lens[b] rows.  The tensors keep the shapes and layouts of the plain entries for L rows.
+ *   sage_channel_mean_kvlens       sage_channel_mean over the valid rows (same 512-row slabs from row 0, same order); 0 for an empty sample
+ *   sage_quant_qk_int8_kvlens      keys: per-thread groups of 64-key blocks, Triton-thread rounding, mean (nullable) subtracted first
+ *   sage_prep_v_fp8_kvlens         statistics, scales and the e4m3 image over the valid rows (no smooth_v); positions past the length in the
+ *                                  last valid tile are zero; scales of an empty sample are 0.  ws: sage_stats_ws_floats(B, H, L, D)
+ *   sage_attn_fused_q_pv_f8_kvlens sage_attn_fused_q_pv_f8 over those operands: non-causal rows see keys < kv_lens[b], causal rows
+ *                                  key <= row and key < kv_lens[b]; an empty sample gets o = 0 and lse = -inf.  The exact score form only
+ *                                  (SAGE_ATTR_FP8_FOLDED_SCORES is refused); a NULL kv_lens is refused.
+ * Replaces nothing in the reference (its dense kernels take one kv_len per call). */
+SAGE_API int sage_channel_mean_kvlens(const void *x, void *mean_out, float *ws, const int32_t *kv_lens, int B, int H, int L, int D,
+                                      int64_t x_sb, int64_t x_sh, int64_t x_sl, int dtype, void *stream);
+SAGE_API int sage_quant_qk_int8_kvlens(const void *x, const void *mean, int8_t *out, float *scale, const int32_t *kv_lens,
+                                       int B, int H, int L, int D,
+                                       int64_t x_sb, int64_t x_sh, int64_t x_sl,
+                                       int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                                       int64_t mean_sb, int64_t mean_sh, int dtype, void *stream);
+SAGE_API int sage_prep_v_fp8_kvlens(const void *v, void *v_image, float *v_scale, float *ws, const int32_t *kv_lens,
+                                    int B, int H, int L, int D, int64_t v_sb, int64_t v_sh, int64_t v_sl,
+                                    float scale_max, int dtype, void *stream);
+SAGE_API int sage_attn_fused_q_pv_f8_kvlens(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
+                                            const float *k_scale, const float *v_scale, const float *v_mean, const int32_t *kv_lens,
+                                            int B, int Hq, int Hkv, int Lq, int Lk, int D,
+                                            int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                            int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                                            int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr);
 
 /* FP16-PV attention (FP32 accumulation, "per-thread" granularity) with the same fused Q quantisation: bit-identical to
  * sage_quant_qk_int8 + sage_attn_qk_int8_pv_f16(pv_accum = single).  v_image from sage_prep_v_f16; v_mean nullable [B,Hkv,D].

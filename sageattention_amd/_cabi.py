@@ -132,6 +132,12 @@ SYMBOLS = {   # (the trailing _P of every sage_attn_* entry point is `const Sage
     "sage_attn_fused_q_pv_f8_split_exact": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I,
                                                     _L, _L, _L, _L, _L, _L, _I, _F, _I, _P, _P]),
     "sage_merge_split_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _I, _P]),
+    # per-sample key lengths of a dense, right-padded batch (kv_lens: int32 [B] on the device): the pre-pass sequence and the attention call
+    "sage_channel_mean_kvlens": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _I, _P]),
+    "sage_quant_qk_int8_kvlens": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _I, _P]),
+    "sage_prep_v_fp8_kvlens": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _F, _I, _P]),
+    "sage_attn_fused_q_pv_f8_kvlens": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I,
+                                               _L, _L, _L, _L, _L, _L, _L, _L, _L, _I, _F, _I, _I, _P, _P]),
 }
 
 

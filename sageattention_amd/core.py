@@ -22,8 +22,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _cabi, ops
-from .quant import (LOG2E, _aligned, _cu_blocks, _dims, _p, _quant, _squeeze_km, _stream, channel_mean, channel_mean_packed, per_block_int8, per_block_int8_varlen,
-                    per_channel_fp8, per_channel_fp8_varlen, prep_v_fp16, prep_v_fp16_varlen, prepass_fused_ok, prepass_kv_fp8, prepass_kv_varlen,
+from .quant import (LOG2E, _aligned, _cu_blocks, _dims, _p, _quant, _squeeze_km, _stream, channel_mean, channel_mean_kvlens, channel_mean_packed,
+                    per_block_int8, per_block_int8_varlen, per_channel_fp8, per_channel_fp8_kvlens, per_channel_fp8_varlen, per_thread_int8_k_kvlens, prep_v_fp16, prep_v_fp16_varlen, prepass_fused_ok, prepass_kv_fp8, prepass_kv_varlen,
                     prepass_varlen_fused_ok, sub_mean, varlen_plan)
 
 _SUPPORTED_ARCH_PREFIX = "gfx950"
@@ -151,10 +151,11 @@ def _v_rows_wanted(q, k, v, tensor_layout: str, is_causal: bool, override) -> bo
 
 @torch.compiler.disable
 def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, sm_scale_log2, return_lse, v_mean=None, folded_scores=False,
-                  v_rows=False):
+                  v_rows=False, kv_lens=None):
     """FP8-PV two-level attention with the per-thread Q quantisation done in the kernel prologue
     (``sage_attn_fused_q_pv_f8``): bit-identical to ``per_thread_int8`` + the attention op, one launch and
-    3 B/element of HBM traffic less.  ``v_rows`` (FP16 PV): ``v_image`` is the fp16 V tensor itself, read in place."""
+    3 B/element of HBM traffic less.  ``v_rows`` (FP16 PV): ``v_image`` is the fp16 V tensor itself, read in place.
+    ``kv_lens`` (FP8 PV, int32 [B] on the device): a key length per sample (``sage_attn_fused_q_pv_f8_kvlens``)."""
     B, Hq, Lq, D, q_sb, q_sh, q_sl = _dims(q, tensor_layout)
     _, Hkv, Lk, _, k_sb, k_sh, k_sl = _dims(k_int8, tensor_layout)
     assert Hq % Hkv == 0, "num_qo_heads must be divisible by num_kv_heads"
@@ -179,6 +180,14 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
             B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl,
             int(is_causal), float(sm_scale_log2), code, code, _stream(q), _cabi.attr_arg(attr))
         ops.attn_check(rc, "sage_attn_fused_q_pv_f16", attr, q.device)
+        return o, lse
+    if kv_lens is not None:
+        assert v_scale is not None and not folded_scores and not v_rows
+        rc = _cabi.load().sage_attn_fused_q_pv_f8_kvlens(
+            _p(q), _p(k_int8), _p(v_image), _p(o), _p(lse), _p(k_scale), _p(v_scale), _p(v_mean), _p(kv_lens),
+            B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl,
+            int(is_causal), float(sm_scale_log2), code, code, _stream(q), _cabi.attr_arg(attr))
+        ops.attn_check(rc, "sage_attn_fused_q_pv_f8_kvlens", attr, q.device)
         return o, lse
     rc = _cabi.load().sage_attn_fused_q_pv_f8(
         _p(q), _p(k_int8), _p(v_image), _p(o), _p(lse), _p(k_scale), _p(v_scale), _p(v_mean),
@@ -339,6 +348,37 @@ def _split_exact_args(kwargs, qk_quant_gran: str, pv_accum_dtype: str, Lk: int) 
     return True
 
 
+def _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs) -> bool:
+    """Whether ``kv_lens`` asks for the per-sample key lengths route; its argument errors (checked before any work, on any device).  The route
+    exists for the default FP8 path only -- fused per-thread Q quantiser, two-level accumulation, the exact score form, no split -- and, as
+    with :func:`_split_exact_args`, is never swapped for another route behind the caller's back: anything else raises ValueError."""
+    if kv_lens is None:
+        return False
+    if not isinstance(kv_lens, torch.Tensor) or kv_lens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"kv_lens must be an int32 or int64 tensor (got {getattr(kv_lens, 'dtype', type(kv_lens).__name__)})")
+    B = q.shape[0]
+    if kv_lens.dim() != 1 or kv_lens.shape[0] != B:
+        raise ValueError(f"kv_lens must have shape [B] = [{B}] (got {tuple(kv_lens.shape)})")
+    if kv_lens.device != q.device:
+        raise ValueError(f"kv_lens must be on q's device {q.device} (got {kv_lens.device})")
+    if qk_quant_gran != "per_thread":
+        raise ValueError(f"kv_lens needs qk_quant_gran='per_thread' (got {qk_quant_gran!r})")
+    if not kwargs.get("fuse_q_quant", True):
+        raise ValueError("kv_lens needs the fused Q quantiser (fuse_q_quant=False given)")
+    if pv_accum_dtype == "fp32":
+        raise ValueError("kv_lens needs pv_accum_dtype 'fp32+fp32' or 'fp32+fp16' (two-level accumulation)")
+    if ops.fp8_folded(kwargs.get("fp8_scores")):
+        raise ValueError("kv_lens takes the exact score form only (fp8_scores='folded' given)")
+    if smooth_v:
+        raise ValueError("kv_lens does not support smooth_v=True")
+    split = kwargs.get("split_kv")
+    if split is not None and not (split == 0 and not isinstance(split, bool)):
+        raise ValueError(f"kv_lens cannot be combined with split_kv={split!r} (None or 0 only)")
+    if kwargs.get("split_kv_exact", False):
+        raise ValueError("kv_lens cannot be combined with split_kv_exact=True")
+    return True
+
+
 @torch.compiler.disable
 def _attn_fused_q_split_exact(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, sm_scale_log2, S, return_lse, v_mean=None):
     """Exact split-KV route of the fused-Q FP8 attention: pass 1 (``sage_split_exact_chunk_max``) computes every chunk's row maxima with
@@ -413,14 +453,17 @@ def _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
 
 # ------------------------------------------------------------------------------------------------
 def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND", is_causal: bool = False,
-             sm_scale: Optional[float] = None, return_lse: bool = False, **kwargs: Any):
+             sm_scale: Optional[float] = None, return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, **kwargs: Any):
     """Select the implementation for the device, as the reference does per compute capability
     (core.py:143-157).  On gfx950 that is INT8 QK^T + FP8 PV with two-level FP32 accumulation
     (the reference's sm90 choice, ``pv_accum_dtype="fp32+fp32"``).  Extra SDPA-style kwargs
     (``attn_mask=``, ``dropout_p=``, ``scale=`` ...) are accepted and ignored exactly as the
-    reference ignores them."""
+    reference ignores them.  ``kv_lens`` (gfx950 extension, int32 / int64 ``[B]`` on q's device): a key length per sample of a right-padded
+    batch, see :func:`sageattn_qk_int8_pv_fp8_cuda`."""
     _check_shapes(q, k, v, tensor_layout)      # (again in the entry point called below: this one is in front of the device query)
     if torch.compiler.is_compiling():      # the device query is not traceable; the opaque op checks the device when it runs
+        if kv_lens is not None:            # (the compiled op has no such argument: a compiled call that ignored the lengths would be a trap)
+            raise ValueError("kv_lens is not supported under torch.compile")
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32")
     arch = get_gcn_arch(q.device) if q.is_cuda else "cpu"
@@ -428,7 +471,7 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32", split_kv=kwargs.get("split_kv"),
                                             fused_prepass=kwargs.get("fused_prepass"), fp8_scores=kwargs.get("fp8_scores"),
-                                            split_kv_exact=kwargs.get("split_kv_exact", False))
+                                            split_kv_exact=kwargs.get("split_kv_exact", False), kv_lens=kv_lens)
     raise ValueError(f"Unsupported architecture: {arch} (sageattention_amd targets gfx950 / MI355X only)")
 
 
@@ -725,9 +768,20 @@ def _fused_prepass_wanted(k, tensor_layout: str, override: Optional[bool]) -> bo
 
 
 def _prepass_kv(q, k, v, tensor_layout, qk_quant_gran, blkk, smooth_k, smooth_v, return_lse, fused: bool, v_fp8: bool = True,
-                v_fp16: bool = False):
+                v_fp16: bool = False, kv_lens=None):
     """K mean + INT8 K (+ FP8 V image when ``v_fp8``).  Returns (lse_correction, km [B,H,D] | None, k_int8, k_scale, v_image,
-    v_scale, vm); the K conventions are those of ``per_thread_int8`` / ``per_warp_int8`` / ``per_block_int8(cuda)``."""
+    v_scale, vm); the K conventions are those of ``per_thread_int8`` / ``per_warp_int8`` / ``per_block_int8(cuda)``.
+    ``kv_lens`` (int32 [B] on the device; per-thread groups, FP8 V, no ``smooth_v``): every statistic of sample b over its first
+    ``kv_lens[b]`` rows only -- the kernel sequence whatever ``fused`` says (the one-launch pre-pass takes no lengths)."""
+    if kv_lens is not None:
+        assert qk_quant_gran == "per_thread" and blkk == 64 and v_fp8 and not smooth_v and not v_fp16
+        km_s = channel_mean_kvlens(k, kv_lens, tensor_layout) if smooth_k else None
+        lse_correction = None
+        if smooth_k and return_lse:
+            lse_correction = _lse_correction(q, km_s.unsqueeze(1 if tensor_layout == "NHD" else 2), tensor_layout)
+        k_int8, k_scale = per_thread_int8_k_kvlens(k, km_s, kv_lens, tensor_layout)
+        v_image, v_scale = per_channel_fp8_kvlens(v, kv_lens, tensor_layout, scale_max=448.0)
+        return lse_correction, km_s, k_int8, k_scale, v_image, v_scale, None
     if fused:
         km_s, k_int8, k_scale, v_image, v_scale, vm = prepass_kv_fp8(k, v if (v_fp8 or v_fp16) else None, tensor_layout, smooth_k=smooth_k,
                                                                      smooth_v=smooth_v, BLKK=blkk, qk_quant_gran=qk_quant_gran, v_fp16=v_fp16)
@@ -809,7 +863,7 @@ def sageattn_qk_int8_pv_fp16_cuda(q, k, v, tensor_layout: str = "HND", is_causal
 def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal: bool = False,
                                  qk_quant_gran: str = "per_thread", sm_scale: Optional[float] = None,
                                  pv_accum_dtype: str = "fp32+fp16", smooth_k: bool = True, smooth_v: bool = False,
-                                 return_lse: bool = False, **kwargs: Any):
+                                 return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, **kwargs: Any):
     """INT8 QK^T + FP8 (e4m3) PV (reference core.py:636-826).  "fp32+fp32" and "fp32+fp16" both
     run the two-level kernel with an FP32 tile buffer (gfx950's FP8 MFMA only writes FP32, so V
     keeps the full ``scale_max=448``; the reference's 2.25 is an FP16-accumulator artefact,
@@ -819,10 +873,22 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     run as key-range chunks whose running maximum starts at the unsplit call's, so every P is the unsplit call's and only the FP32 summation
     order of O and l differs (``split_kv``: None / "auto" plans S for non-causal calls, an integer S splits so, 0 never; a ragged rest of the
     key range runs as a tail chunk).  It needs the default path: per-thread granularity with the fused Q quantiser, two-level accumulation,
-    the exact score form; anything else raises ValueError."""
+    the exact score form; anything else raises ValueError.
+
+    ``kv_lens`` (gfx950 extension): an int32 / int64 tensor ``[B]`` on q's device for a dense, right-padded batch -- sample b attends to keys
+    ``0 .. kv_lens[b] - 1`` of ``k[b]`` / ``v[b]`` and to nothing else (causal: ``key <= row and key < kv_lens[b]``, top-left aligned).  Its
+    ``o`` and ``lse`` are, bit for bit, what this function returns for ``(q[b:b+1], k[b:b+1, :, :len_b], v[b:b+1, :, :len_b])``: the K mean,
+    the K scale groups and the V scales are formed over the valid rows only, and the padding rows are never read (they may be
+    uninitialised).  The lengths are clamped to ``[0, kv_len]`` on the device and never read by the host, so the call can be captured in a
+    HIP graph and replayed with other lengths in the same tensor; ``kv_lens[b] == 0`` gives ``o[b] = 0`` and ``lse[b] = -inf``.  The default
+    path only: per-thread granularity with the fused Q quantiser, two-level accumulation, the exact score form, no ``smooth_v``, no
+    split-KV, not under torch.compile; anything else raises ValueError."""
     if torch.compiler.is_compiling():
+        if kv_lens is not None:
+            raise ValueError("kv_lens is not supported under torch.compile (the compiled op takes the default routes)")
         return _compiled_call("fp8", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse, kwargs)
     _check_shapes(q, k, v, tensor_layout)
+    with_lens = _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     exact = _split_exact_args(kwargs, qk_quant_gran, pv_accum_dtype, _dims(k, tensor_layout)[2])
     dtype = q.dtype
     _check_inputs(q, k, v)
@@ -840,6 +906,15 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     fuse_q = qk_quant_gran == "per_thread" and pv_accum_dtype != "fp32" and kwargs.get("fuse_q_quant", True)
     fused = _fused_prepass_wanted(k, tensor_layout, kwargs.get("fused_prepass"))
     folded = ops.fp8_folded(kwargs.get("fp8_scores"))
+    if with_lens:
+        # per-sample key lengths: the length-aware kernel sequence (mean -> K quantiser -> V statistics -> V image), then the KVLEN kernels;
+        # nothing here reads the lengths on the host (int64 is converted on the device)
+        lens = kv_lens.to(torch.int32).contiguous()
+        lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
+                                                                              return_lse, False, kv_lens=lens)
+        o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
+                               kv_lens=lens)
+        return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
     if fuse_q:
         # default route: Q is quantised inside the attention kernel (same bits, no INT8 copy of Q in HBM).
         # (Running the V pre-pass on a side stream beside the K chain was measured and rejected: the two HBM-bound chains

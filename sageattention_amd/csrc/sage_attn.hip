@@ -95,6 +95,21 @@ hipError_t launch_attn_fused_q_seeded(const AttnParams &p_in, int head_dim, bool
     return hipErrorInvalidValue;
 }
 
+// per-sample key lengths (p.cu_k = the [B] lengths, device memory): the work order is planned for the padded p.Lk -- it is a permutation of the
+// items whatever the lengths are, and nothing on the host depends on their values
+hipError_t launch_attn_fused_q_kvlens(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o)
+{
+    AttnParams p = p_in;
+    if (o.grid_out != nullptr) *o.grid_out = 0;
+    if (p.cu_k == nullptr || p.cu_q != nullptr || p.v_rows != 0 || p.kv_split > 1 || (q_dtype != DT_F16 && q_dtype != DT_BF16)) return hipErrorInvalidValue;
+    const int nwork = set_work_order(p, causal, head_dim, true, false);
+    if (nwork <= 0) return hipSuccess;
+    const AttnVariant v = {causal, true, true, 0, q_dtype == DT_F16 ? 1 : 2, false};
+    if (head_dim == 128) return launch_attn_f8_kvlens<128>(p, v, nwork, o);
+    if (head_dim == 64) return launch_attn_f8_kvlens<64>(p, v, nwork, o);
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_attn_fused_qblock(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, bool pv_fp8, bool two_level,
                                    const AttnLaunchOpts &o)
 {

@@ -164,8 +164,16 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // hk = hk0 * kv_split + chunk runs keys p.kv_base + chunk * Lk .. + Lk - 1 of kv head hk0 (the operands of the UNSPLIT call, read in place), its
 // running maximum starts from the exclusive prefix maximum of pass 1's chunk maxima (p.seed_max) -- the maximum the unsplit call holds at the
 // chunk's first tile, so every P is the unsplit call's -- and it writes an FP32 normalised partial output [B, Hq * kv_split, Lq, D].
+// KVLEN (FP8 PV, fused per-thread Q, exact score form, dense: the kv_lens route, units sage_attn_d{128,64}_f8k.hip): sample b attends to keys
+// 0 .. len_b - 1 only, len_b = p.cu_k[b] clamped to [0, p.Lk] (a dense launch leaves cu_k free; here it is the caller's [B] lengths).  Lk becomes
+// len_b for everything that bounds, clamps or masks -- the work item then runs exactly what a call on the sample's first len_b keys runs --
+// while what describes the TENSORS (V images and k scale slots per head) stays derived from the padded p.Lk.  Key rows, scales and V images
+// from len_b on are never read.  A sample without keys requests no tile and runs no iteration (n_iters = 0); the epilogue then writes o = 0
+// (l = 0: the normalisation factor is 0, and the product is forced to zero so that a NaN in the sample's unused scale slots cannot reach it)
+// and lse = log2(0) + m = -inf.  (An exit of its own in front of the Q fragments -- a second way out of the item loop -- cost the D = 64
+// non-causal instantiations 5-8 spilled VGPRs under their three-waves limit wherever it was placed.)
 template <int D, bool PV_FP8, bool CAUSAL, bool KTHREAD, bool TWO_LEVEL, int NH, int MASK = 0, int QF = 0, bool SFOLD = true, bool CPERS = false,
-          bool VROWS = false, bool SEED = false>
+          bool VROWS = false, bool SEED = false, bool KVLEN = false>
 __global__ void __launch_bounds__(256, SAGE_MIN_WAVES(D, MASK))
 sage_attn_kernel(const AttnParams p_arg)
 {
@@ -193,6 +201,8 @@ sage_attn_kernel(const AttnParams p_arg)
     constexpr int NS = 2 * NH;                       // 32-key S^T sub-tiles per iteration
     static_assert(!SEED || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS),
                   "the seeded split: FP8 PV, fused per-thread Q, exact score form, dense");
+    static_assert(!KVLEN || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS && !SEED),
+                  "per-sample key lengths: FP8 PV, fused per-thread Q, exact score form, dense");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     // (wave index in an SGPR, lane index from v_mbcnt wherever it is needed: nothing derived from threadIdx.x has to stay in a VGPR across
@@ -387,10 +397,15 @@ sage_attn_kernel(const AttnParams p_arg)
         // split-KV (p.kv_split = S > 1): the key range is folded into the kv-head dimension, kv head hk = hk0 * S + chunk and query
         // head h = hk * group + g; the query rows are those of head hk0 * group + g (read in place, no per-chunk copy of Q)
         const int hq = p.kv_split > 1 ? (hk / p.kv_split) * p.group + (h - hk * p.group) : h;
+        if constexpr (KVLEN) {             // the sample's key count: wave-uniform index, one scalar load (as the packed route's prefix arrays)
+            typedef const __attribute__((address_space(4))) int *cint_p;
+            const int len = ((cint_p)p.cu_k)[__builtin_amdgcn_readfirstlane(b)];
+            Lk = len < 0 ? 0 : (len < p.Lk ? len : p.Lk);
+        }
         q_off = (long)b * p.q_sb + (long)hq * p.q_sh;
         k_off = (long)b * p.k_sb + (long)hk * p.k_sh;
         o_off = (long)b * p.o_sb + (long)h * p.o_sh;
-        const int ntk = (Lk + BLKK - 1) / BLKK;
+        const int ntk = ((KVLEN ? p.Lk : Lk) + BLKK - 1) / BLKK;      // (images per head of the tensor)
         v_tile0 = ((long)b * p.Hkv + hk) * ntk;
         v_tstride = 1;
         qs_ptr = p.q_scale + ((long)b * p.Hq + h) * p.nqs + (long)qblk * p.qs_per_blk;
@@ -1011,6 +1026,10 @@ sage_attn_kernel(const AttnParams p_arg)
     // every factor of the tile is requested before the first one is used: one exposed memory latency per workgroup
     // instead of one per 32-channel tile (the slot is idle for the co-resident workgroup's sake until this one retires)
     v4f sc4[C::DT][4], mn4[C::DT][4];
+    // (KVLEN) all ones, or zero for a sample without keys: a bit mask the compiler cannot see through -- as a select on Lk it moved the factor
+    // loads below behind a branch, 0.6 us per work item (profiles/kv_lens_trace_wan.txt)
+    [[maybe_unused]] unsigned keep = (!KVLEN || Lk > 0) ? ~0u : 0u;
+    if constexpr (KVLEN) asm volatile("" : "+v"(keep));
 #pragma unroll
     for (int dt = 0; dt < C::DT; dt++) {
 #pragma unroll
@@ -1036,6 +1055,7 @@ sage_attn_kernel(const AttnParams p_arg)
             for (int j = 0; j < 4; j++) {
                 x[j] = o[dt][4 * r4 + j] * inv;
                 if (PV_FP8) x[j] *= sc4[dt][r4][j];
+                if constexpr (KVLEN) x[j] = __uint_as_float(__float_as_uint(x[j]) & keep);      // (a sample without keys: +0 whatever its scale slots hold)
                 x[j] += mn4[dt][r4][j];
             }
             if constexpr (SEED) {      // FP32 partial rows straight from the registers: four channels per lane

@@ -174,4 +174,21 @@ hipError_t launch_attn_f8_seeded(const AttnParams &p, const AttnVariant &v, int 
     return hipErrorInvalidValue;
 }
 
+// Per-sample key lengths (sage_attn_kernel's KVLEN): the fused per-thread Q quantiser (qf 1 / 2), FP8 PV two-level, the exact score form, dense;
+// p.cu_k holds the [B] lengths: the units sage_attn_d{128,64}_f8k.hip.  Non-causal launches may take the ticket route as the plain kernels do
+// (samples of different lengths are items of different lengths: the tickets even them out); causal launches keep the hardware's dispatch.
+template <int D>
+hipError_t launch_attn_f8_kvlens(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
+{
+    using C = TileCfg<D, true, 1>;
+    if (p.cu_k == nullptr || p.cu_q != nullptr || p.kv_split > 1 || p.seed_max != nullptr || l.fp8_folded || !v.kthread || !v.two_level || v.vrows ||
+        v.mask_kind != 0)
+        return hipErrorInvalidValue;
+#define SAGE_F8K(C_, F_) if (v.causal == C_ && v.qf == F_) \
+    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, !C_);
+    SAGE_F8K(false, 1) SAGE_F8K(false, 2) SAGE_F8K(true, 1) SAGE_F8K(true, 2)
+#undef SAGE_F8K
+    return hipErrorInvalidValue;
+}
+
 }  // namespace sage

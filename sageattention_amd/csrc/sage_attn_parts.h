@@ -1,7 +1,7 @@
 // sage_attn_parts.h -- interface between the host-side dispatch of the attention launches (sage_attn.hip) and the instantiation units
 // sage_attn_d{128,64}_{f8,f8f,f16}.hip, each of which compiles the kernel family of sage_attn_kernel.h for one head size, one PV format and
 // (FP8) one score form, sage_attn_d{128,64}_f8v.hip (the packed FP8 route's fused-Q kernels) and sage_attn_d{128,64}_f8s.hip (the exact
-// split's seeded kernels).  The split exists for build time only: the units are independent and compile in parallel.
+// split's seeded kernels) and sage_attn_d{128,64}_f8k.hip (the kv_lens route's kernels).  The split exists for build time only: the units are independent and compile in parallel.
 #pragma once
 #include "sage_kernels.h"
 
@@ -39,5 +39,11 @@ template <int D>
 hipError_t launch_attn_f8_seeded(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l);
 extern template hipError_t launch_attn_f8_seeded<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_f8_seeded<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+
+// per-sample key lengths (AttnParams::cu_k = the [B] lengths): the fused per-thread Q FP8 kernels, dense: units sage_attn_d{128,64}_f8k.hip
+template <int D>
+hipError_t launch_attn_f8_kvlens(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l);
+extern template hipError_t launch_attn_f8_kvlens<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_f8_kvlens<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 
 }  // namespace sage

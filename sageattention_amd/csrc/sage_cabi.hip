@@ -182,13 +182,13 @@ SAGE_API int64_t sage_v_image_bytes(int head_dim, int fp8, int64_t n_kv_tiles_to
     return n_kv_tiles_total * (int64_t)head_dim * (fp8 ? 64 : 128);
 }
 
-SAGE_API int sage_quant_qk_int8(const void *x, const void *mean, int8_t *out, float *scale,
-                       int B, int H, int L, int D,
-                       int64_t x_sb, int64_t x_sh, int64_t x_sl,
-                       int64_t o_sb, int64_t o_sh, int64_t o_sl,
-                       int64_t mean_sb, int64_t mean_sh,
-                       int blk, int warp, int gran, int is_key, int style,
-                       float pre_scale, int dtype, void *stream)
+static int quant_common(const void *x, const void *mean, int8_t *out, float *scale,
+                        int B, int H, int L, int D,
+                        int64_t x_sb, int64_t x_sh, int64_t x_sl,
+                        int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                        int64_t mean_sb, int64_t mean_sh,
+                        int blk, int warp, int gran, int is_key, int style,
+                        float pre_scale, int dtype, void *stream, const int32_t *kv_lens)
 {
     SAGE_REQUIRE(x && out && scale, "null tensor pointer");
     SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
@@ -218,7 +218,34 @@ SAGE_API int sage_quant_qk_int8(const void *x, const void *mean, int8_t *out, fl
         SAGE_REQUIRE(slots <= 64, "too many scale groups per block (%d)", slots);
     } else return fail(SAGE_EINVAL, "bad qk_quant_gran %d", gran);
     p.nscale = ((L + blk - 1) / blk) * slots;
+    p.kv_lens = kv_lens;
     return check_launch(sage::launch_quant_int8(p, static_cast<hipStream_t>(stream)), "sage_quant_qk_int8 launch");
+}
+
+SAGE_API int sage_quant_qk_int8(const void *x, const void *mean, int8_t *out, float *scale,
+                       int B, int H, int L, int D,
+                       int64_t x_sb, int64_t x_sh, int64_t x_sl,
+                       int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                       int64_t mean_sb, int64_t mean_sh,
+                       int blk, int warp, int gran, int is_key, int style,
+                       float pre_scale, int dtype, void *stream)
+{
+    return quant_common(x, mean, out, scale, B, H, L, D, x_sb, x_sh, x_sl, o_sb, o_sh, o_sl, mean_sb, mean_sh, blk, warp, gran, is_key, style,
+                        pre_scale, dtype, stream, nullptr);
+}
+
+// keys of a dense, right-padded batch with a length per sample: per-thread groups of 64-key blocks (the FP8 entry point's K convention), the
+// mean (nullable) subtracted first.  Rows >= clamp(kv_lens[b], 0, L) are neither read nor written and take no part in any abs-max; the scale
+// slots [B, H, ceil(L / 64) * 4] of blocks wholly past the length stay unwritten.  No host read of kv_lens.
+SAGE_API int sage_quant_qk_int8_kvlens(const void *x, const void *mean, int8_t *out, float *scale, const int32_t *kv_lens,
+                                       int B, int H, int L, int D,
+                                       int64_t x_sb, int64_t x_sh, int64_t x_sl,
+                                       int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                                       int64_t mean_sb, int64_t mean_sh, int dtype, void *stream)
+{
+    SAGE_REQUIRE(kv_lens, "sage_quant_qk_int8_kvlens: null kv_lens");
+    return quant_common(x, mean, out, scale, B, H, L, D, x_sb, x_sh, x_sl, o_sb, o_sh, o_sl, mean_sb, mean_sh, 64, 64, SAGE_GRAN_PER_THREAD, 1,
+                        sage::QS_TRITON_THREAD, 1.0f, dtype, stream, kv_lens);
 }
 
 SAGE_API int sage_quant_qk_int8_varlen(const void *x, const void *mean, int8_t *out, float *scale,
@@ -300,7 +327,7 @@ SAGE_API int sage_debug_varlen_items(const int32_t *lq, const int32_t *lk, int n
 }
 
 static int stats_common(const void *x, void *mean_out, float *ws, float *stats, int B, int H, int L, int D,
-                        int64_t x_sb, int64_t x_sh, int64_t x_sl, int dtype, void *stream, const char *what)
+                        int64_t x_sb, int64_t x_sh, int64_t x_sl, int dtype, void *stream, const char *what, const int32_t *kv_lens = nullptr)
 {
     SAGE_REQUIRE(x && ws, "null tensor pointer");
     SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
@@ -312,12 +339,13 @@ static int stats_common(const void *x, void *mean_out, float *ws, float *stats, 
     p.x = x; p.ws = ws; p.stats = stats; p.mean_out = mean_out;
     p.B = B; p.H = H; p.L = L; p.D = D; p.nslab = (L + sage::kStatsSlab - 1) / sage::kStatsSlab;
     p.x_sb = x_sb; p.x_sh = x_sh; p.x_sl = x_sl; p.dtype = dtype;
+    p.kv_lens = kv_lens;
     return check_launch(sage::launch_stats(p, static_cast<hipStream_t>(stream)), what);
 }
 
 static int prep_v_common(const void *v, void *v_image, float *v_scale, float *v_mean_out, const float *v_mean_in,
                          const float *stats, const int32_t *cu, const int32_t *cu_tiles, int B, int H, int L, int D,
-                         int64_t v_sb, int64_t v_sh, int64_t v_sl, float scale_max, int dtype, int fp8, void *stream)
+                         int64_t v_sb, int64_t v_sh, int64_t v_sl, float scale_max, int dtype, int fp8, void *stream, const int32_t *kv_lens = nullptr)
 {
     SAGE_REQUIRE(v && v_image, "null tensor pointer");
     SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
@@ -330,6 +358,7 @@ static int prep_v_common(const void *v, void *v_image, float *v_scale, float *v_
     p.cu = cu; p.cu_tiles = cu_tiles;
     p.B = B; p.H = H; p.L = L; p.D = D; p.v_sb = v_sb; p.v_sh = v_sh; p.v_sl = v_sl;
     p.dtype = dtype; p.fp8 = fp8; p.scale_max = scale_max;
+    p.kv_lens = kv_lens;
     return check_launch(sage::launch_prep_v(p, static_cast<hipStream_t>(stream)), "sage_prep_v launch");
 }
 
@@ -344,6 +373,15 @@ SAGE_API int sage_channel_mean(const void *x, void *mean_out, float *ws, int B, 
 {
     SAGE_REQUIRE(mean_out, "null output pointer");
     return stats_common(x, mean_out, ws, nullptr, B, H, L, D, x_sb, x_sh, x_sl, dtype, stream, "sage_channel_mean launch");
+}
+
+// the mean of sample b over rows < clamp(kv_lens[b], 0, L) (0 for a sample without rows): the slabs and the order of sage_channel_mean, so it
+// is that entry's result on the first kv_lens[b] rows, bit for bit.  ws: sage_stats_ws_floats(B, H, L, D).  No host read of kv_lens.
+SAGE_API int sage_channel_mean_kvlens(const void *x, void *mean_out, float *ws, const int32_t *kv_lens, int B, int H, int L, int D,
+                                      int64_t x_sb, int64_t x_sh, int64_t x_sl, int dtype, void *stream)
+{
+    SAGE_REQUIRE(mean_out && kv_lens, "sage_channel_mean_kvlens: null output or kv_lens pointer");
+    return stats_common(x, mean_out, ws, nullptr, B, H, L, D, x_sb, x_sh, x_sl, dtype, stream, "sage_channel_mean_kvlens launch", kv_lens);
 }
 
 SAGE_API int sage_channel_mean_varlen(const void *x, void *mean_out, float *ws, const int32_t *cu_seqlens, const int32_t *slab_first,
@@ -375,6 +413,23 @@ SAGE_API int sage_prep_v_fp8(const void *v, void *v_image, float *v_scale, float
     if (rc != SAGE_OK) return rc;
     return prep_v_common(v, v_image, v_scale, v_mean, nullptr, stats, nullptr, nullptr, B, H, L, D, v_sb, v_sh, v_sl,
                          scale_max, dtype, 1, stream);
+}
+
+// FP8 V image of a dense, right-padded batch with a length per sample: statistics and scales over tokens < clamp(kv_lens[b], 0, L), the image
+// laid out as sage_prep_v_fp8's for L tokens ([B, H, ceil(L / 64)] tiles); in the tile that holds a sample's last token the positions past it
+// are zero, the tiles behind it stay unwritten, a sample without tokens gets scales of 0.  No smooth_v.  ws: sage_stats_ws_floats(B, H, L, D).
+SAGE_API int sage_prep_v_fp8_kvlens(const void *v, void *v_image, float *v_scale, float *ws, const int32_t *kv_lens,
+                                    int B, int H, int L, int D, int64_t v_sb, int64_t v_sh, int64_t v_sl,
+                                    float scale_max, int dtype, void *stream)
+{
+    SAGE_REQUIRE(v_scale && ws && kv_lens, "sage_prep_v_fp8_kvlens needs v_scale, the statistics workspace and kv_lens");
+    SAGE_REQUIRE(scale_max > 0.0f, "scale_max must be positive");
+    const int64_t nslab = (L + sage::kStatsSlab - 1) / sage::kStatsSlab;
+    float *stats = ws + (int64_t)B * H * nslab * 3 * D;
+    int rc = stats_common(v, nullptr, ws, stats, B, H, L, D, v_sb, v_sh, v_sl, dtype, stream, "sage_v_stats_kvlens launch", kv_lens);
+    if (rc != SAGE_OK) return rc;
+    return prep_v_common(v, v_image, v_scale, nullptr, nullptr, stats, nullptr, nullptr, B, H, L, D, v_sb, v_sh, v_sl,
+                         scale_max, dtype, 1, stream, kv_lens);
 }
 
 // per-sequence V statistics of a packed batch: the stage-1 partials (the slab map's layout [1,H,nslab_bound], or nslab_bound = 0: without a
@@ -734,10 +789,12 @@ static int fused_q_common(const void *q, const int8_t *k, const void *v_image, v
                           int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
                           int64_t o_sb, int64_t o_sh, int64_t o_sl,
                           int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, int kv_split, void *stream, const SageLaunchAttr *attr,
-                          bool pv_fp8 = true, const int64_t *v_strides = nullptr)
+                          bool pv_fp8 = true, const int64_t *v_strides = nullptr, const int32_t *kv_lens = nullptr)
 {
     LaunchAttr la;
     if (const int rc = read_attr(attr, stream, kv_split <= 1, la)) return rc;       // (split launches take no launch workspace)
+    SAGE_REQUIRE(kv_lens == nullptr || (pv_fp8 && kv_split <= 1 && v_strides == nullptr && !la.opts.fp8_folded),
+                 "kv_lens: FP8 PV, the exact score form (SAGE_ATTR_FP8_FOLDED_SCORES), no split");
     if (v_strides != nullptr) {        // V rows in place: fp16 q / k / v tensors of one call
         SAGE_REQUIRE(!pv_fp8 && kv_split <= 1 && q_dtype == SAGE_DTYPE_F16, "V rows in place: FP16 PV on fp16 inputs, no split");
         SAGE_REQUIRE(v_strides[0] % 8 == 0 && v_strides[1] % 8 == 0 && v_strides[2] % 8 == 0 && v_strides[2] >= D, "v strides must be multiples of 8 elements (16-byte rows)");
@@ -771,7 +828,23 @@ static int fused_q_common(const void *q, const int8_t *k, const void *v_image, v
     p.sm_scale_log2 = sm_scale_log2;
     p.kv_split = kv_split;
     if (v_strides != nullptr) { p.v_rows = 1; p.v_sb = v_strides[0]; p.v_sh = v_strides[1]; p.v_sl = v_strides[2]; }
+    if (kv_lens != nullptr) {
+        p.cu_k = kv_lens;
+        return check_launch(sage::launch_attn_fused_q_kvlens(p, D, is_causal != 0, q_dtype, la.opts), "sage_attn_fused_q_pv_f8_kvlens launch");
+    }
     return check_launch(sage::launch_attn_fused_q(p, D, is_causal != 0, q_dtype, pv_fp8, la.opts), "sage_attn_fused_q launch");
+}
+
+SAGE_API int sage_attn_fused_q_pv_f8_kvlens(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
+                                            const float *k_scale, const float *v_scale, const float *v_mean, const int32_t *kv_lens,
+                                            int B, int Hq, int Hkv, int Lq, int Lk, int D,
+                                            int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                            int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                                            int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
+{
+    SAGE_REQUIRE(kv_lens, "sage_attn_fused_q_pv_f8_kvlens: null kv_lens");
+    return fused_q_common(q, k, v_image, o, lse, k_scale, v_scale, v_mean, B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl,
+                          o_sb, o_sh, o_sl, is_causal, sm_scale_log2, q_dtype, out_dtype, 0, stream, attr, true, nullptr, kv_lens);
 }
 
 SAGE_API int sage_attn_fused_q_pv_f8(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,

@@ -26,7 +26,7 @@ struct AttnParams {
     const void *mask;         // attn_mask (bool bytes or fp16/bf16 additive), element strides below; null = none
     long m_sb, m_sh, m_sq, m_sk;
     const int32_t *cu_q;      // varlen only (null => dense)
-    const int32_t *cu_k;
+    const int32_t *cu_k;      // (dense launch_attn_fused_q_kvlens: the per-sample key lengths [B] instead, clamped to [0, Lk] by the kernel)
     const int32_t *cu_qs;     // prefix sums of ceil(Lq_i/128)
     const int32_t *cu_ks;     // prefix sums of ceil(Lk_i/64)
     const int32_t *seq_order; // varlen, nullable: permutation of sequence indices in processing order (legacy unit order, no work list)
@@ -78,6 +78,9 @@ hipError_t launch_attn_fused_q(const AttnParams &p, int head_dim, bool causal, i
 // the exact split's pass 2: q in fp16 / bf16, quantised per thread group in the prologue, FP8 PV two-level, exact score form, running maximum
 // seeded from p.seed_max, FP32 partial outputs (p.o) and log2-domain LSEs (p.lse) per chunk; p.kv_split >= 1 chunks of p.Lk keys from p.kv_base
 hipError_t launch_attn_fused_q_seeded(const AttnParams &p, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o);
+// per-sample key lengths (dense, FP8 PV two-level, exact score form): p.cu_k = int32 lengths [B] in device memory, sample b attends to keys
+// 0 .. clamp(cu_k[b], 0, p.Lk) - 1 of the padded tensors; k / its scales / the V image from sage_quant_qk_int8_kvlens / sage_prep_v_fp8_kvlens
+hipError_t launch_attn_fused_q_kvlens(const AttnParams &p, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o);
 // q in fp16 / bf16, quantised per 128-row block in the prologue after the multiplication by p.q_premul; per-block k scales.  FP16 PV in
 // the Triton kernels' form, dense or varlen (p.cu_q); FP8 PV (varlen only, the exact score form): two_level or single accumulation
 hipError_t launch_attn_fused_qblock(const AttnParams &p, int head_dim, bool causal, int q_dtype, bool pv_fp8, bool two_level,
@@ -107,6 +110,7 @@ struct QuantParams {
     int warp;                 // sub-group rows for GR_WARP / GR_THREAD_* (32, 16, 64)
     int gran, style, dtype;
     float pre_scale;
+    const int32_t *kv_lens;   // dense, nullable [B]: rows >= clamp(kv_lens[b], 0, L) of sample b are neither read nor written, their scale groups not formed
 };
 hipError_t launch_quant_int8(const QuantParams &p, hipStream_t stream);
 // packed batches: every index array of a varlen call from one launch (sage_varlen_plan.hip), nseq <= kVarlenPlanMaxSeq
@@ -151,6 +155,9 @@ struct StatsParams {
     // With the slab map above stage 1 is the map's launch (ws [1,H,nslab,3,D]); without it stage 1 runs over (slab of a sequence, head,
     // sequence), nslab = ceil(max L / 512) slabs per sequence (ws [nseq,H,nslab,3,D])
     int seq_stats;
+    // dense, nullable [B]: the statistics of sample b run over rows < clamp(kv_lens[b], 0, L) only (same slabs from row 0, same order: what a
+    // call on the first kv_lens[b] rows gives, bit for bit); the mean of a sample without rows is 0, its (max, min, sum) (-inf, +inf, 0)
+    const int32_t *kv_lens;
 };
 hipError_t launch_stats(const StatsParams &p, hipStream_t stream);
 
@@ -169,6 +176,8 @@ struct PrepVParams {
     int dtype;
     int fp8;                  // 1: e4m3 output, 0: fp16 output
     float scale_max;
+    const int32_t *kv_lens;   // dense fp8, nullable [B]: tokens >= clamp(kv_lens[b], 0, L) are zero in the tile that holds the last valid token, the
+                              // tiles behind it are not written; the scales of a sample without tokens are 0 (image layout as for L tokens)
 };
 hipError_t launch_prep_v(const PrepVParams &p, hipStream_t stream);
 

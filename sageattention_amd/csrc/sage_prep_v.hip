@@ -48,6 +48,14 @@ prep_v_kernel(const PrepVParams p)
     } else {
         voff = (long)b * p.v_sb + (long)h * p.v_sh;
         tile_idx = ((long)b * p.H + h) * ((L + BLKK - 1) / BLKK) + t;
+        if (p.kv_lens != nullptr) {      // (FP8) the sample's valid tokens; tiles wholly past them are left unwritten (never read)
+            const int len = p.kv_lens[b];
+            L = len < 0 ? 0 : (len < L ? len : L);
+            if (t * BLKK >= L) {
+                if (FP8 && L == 0 && t == 0 && tid < D) p.v_scale[((long)b * p.H + h) * D + tid] = 0.0f;      // no token: (max, min) are (-inf, +inf)
+                return;
+            }
+        }
     }
     const uint16_t *v = reinterpret_cast<const uint16_t *>(p.v) + voff;
 

@@ -43,6 +43,11 @@ quant_int8_kernel(const QuantParams p)
         ooff = (long)s0 * p.o_sl + (long)h * p.o_sh;
         sc_out = p.scale + ((long)p.cu_scale[b] + blk) * p.H + h;       // [sum nblk, H]
     } else {
+        if (p.kv_lens != nullptr) {      // rows past the sample's length take no part; blocks wholly past it are left unwritten (never read)
+            const int len = p.kv_lens[b];
+            L = len < 0 ? 0 : (len < L ? len : L);
+            if (blk * BLK >= L) return;
+        }
         xoff = (long)b * p.x_sb + (long)h * p.x_sh;
         ooff = (long)b * p.o_sb + (long)h * p.o_sh;
         sc_out = p.scale + ((long)b * p.H + h) * p.nscale + (long)blk * ngroups;

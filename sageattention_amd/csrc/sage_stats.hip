@@ -30,6 +30,10 @@ stats_partial_kernel(const StatsParams p)
     // rows [start, end) of the slab.  Packed batches (p.slab_seq): a slab is 512 tokens of ONE sequence -- the partition of the one-launch
     // varlen pre-pass (sage_prepass.hip), so that both routes sum in the same order and give the same mean bit for bit
     int start = slab * kStatsSlab, end = min(p.L, slab * kStatsSlab + kStatsSlab);
+    if (p.kv_lens != nullptr) {          // (dense) rows past the sample's length are not read: an empty slab leaves (-inf, +inf, 0)
+        const int len = p.kv_lens[b];
+        end = min(end, len < 0 ? 0 : len);
+    }
     if (p.slab_seq != nullptr) {
         if (slab >= p.hdr[4]) return;
         const int seg = p.slab_seq[slab];
@@ -85,7 +89,13 @@ __global__ void stats_final_kernel(const StatsParams p)
 {
     const int d = threadIdx.x, h = blockIdx.x, b = blockIdx.y;
     const float *ws = p.ws + ((long)b * p.H + h) * p.nslab * 3 * D;
-    const int nslab = p.slab_seq != nullptr ? p.hdr[4] : p.nslab;      // packed batches: p.nslab is the host-known bound (workspace stride)
+    int nslab = p.slab_seq != nullptr ? p.hdr[4] : p.nslab;      // packed batches: p.nslab is the host-known bound (workspace stride)
+    int rows = p.L;
+    if (p.kv_lens != nullptr) {          // (dense) the slabs that hold the sample's rows, and its row count as the mean's divisor
+        const int len = p.kv_lens[b];
+        rows = len < 0 ? 0 : (len < p.L ? len : p.L);
+        nslab = (rows + kStatsSlab - 1) / kStatsSlab;
+    }
     float a = -INFINITY, c = INFINITY, s = 0.0f;
     // slabs in index order (the summation order every route shares); sixteen slabs' loads are in flight together -- issued one by one
     // this loop is a chain of L2 round trips: 19 us for the 66 slabs of a C4 call
@@ -106,7 +116,7 @@ __global__ void stats_final_kernel(const StatsParams p)
         st[d] = a; st[D + d] = c; st[2 * D + d] = s;
     }
     if (p.mean_out != nullptr)      // k.mean(dim=seq) in the input dtype: fp32 sum / L, one rounding
-        reinterpret_cast<uint16_t *>(p.mean_out)[((long)b * p.H + h) * D + d] = st16<DT>(s / (float)p.L);
+        reinterpret_cast<uint16_t *>(p.mean_out)[((long)b * p.H + h) * D + d] = st16<DT>(rows > 0 ? s / (float)rows : 0.0f);
 }
 
 // Stage 2 of a packed batch, per sequence (p.seq_stats): grid (head, sequence).  The slabs of sequence s in index order -- its range of the

@@ -258,6 +258,65 @@ def channel_mean(x: torch.Tensor, tensor_layout: str = "HND") -> torch.Tensor:
     return out
 
 
+def _kv_lens_ok(kv_lens: torch.Tensor, x: torch.Tensor, B: int) -> None:
+    assert kv_lens.dtype == torch.int32 and kv_lens.shape == (B,) and kv_lens.is_contiguous() and kv_lens.device == x.device, \
+        "kv_lens must be a contiguous int32 [B] tensor on the operands' device"
+
+
+@_eager
+def channel_mean_kvlens(x: torch.Tensor, kv_lens: torch.Tensor, tensor_layout: str = "HND") -> torch.Tensor:
+    """:func:`channel_mean` of a right-padded batch: sample b's mean runs over its rows ``< kv_lens[b]`` (clamped to ``[0, L]`` on the
+    device; 0 for a sample without rows) -- bit for bit :func:`channel_mean` of ``x[b:b+1, :, :kv_lens[b]]``.  The padding is not read."""
+    x = _aligned(x, 8)
+    B, H, L, D, sb, sh, sl = _dims(x, tensor_layout)
+    _kv_lens_ok(kv_lens, x, B)
+    out = torch.empty((B, H, D), dtype=x.dtype, device=x.device)
+    ws = _stats_ws(B, H, L, D, x.device)
+    rc = _cabi.load().sage_channel_mean_kvlens(_p(x), _p(out), _p(ws), _p(kv_lens), B, H, L, D, sb, sh, sl, _dtype_code(x), _stream(x))
+    _cabi.check(rc, "sage_channel_mean_kvlens")
+    return out
+
+
+@_eager
+def per_thread_int8_k_kvlens(k: torch.Tensor, km: Optional[torch.Tensor], kv_lens: torch.Tensor, tensor_layout: str = "HND"):
+    """The K half of :func:`per_thread_int8` (64-key blocks, ``km`` [B, H, D] subtracted first) for a right-padded batch: rows
+    ``>= kv_lens[b]`` take no part in any scale group and are not written; INT8 rows and scale slots past a sample's last block hold
+    whatever the allocation held.  Returns ``(k_int8, k_scale [B, H, ceil(L / 64) * 4])`` in the layouts of the plain quantiser."""
+    k = _aligned(k, 8)
+    B, H, L, D, sb, sh, sl = _dims(k, tensor_layout)
+    _kv_lens_ok(kv_lens, k, B)
+    out = torch.empty((B, H, L, D), dtype=torch.int8, device=k.device)          # head-major storage, as _quant
+    if tensor_layout == "NHD":
+        out = out.permute(0, 2, 1, 3)
+    _, _, _, _, ob, oh, ol = _dims(out, tensor_layout)
+    scale = torch.empty((B, H, ((L + 63) // 64) * 4), dtype=torch.float32, device=k.device)
+    if km is not None:
+        assert km.dtype == k.dtype and km.shape == (B, H, D), "km must be [B, H, D] in the dtype of k"
+    rc = _cabi.load().sage_quant_qk_int8_kvlens(
+        _p(k), _p(km), _p(out), _p(scale), _p(kv_lens), B, H, L, D, sb, sh, sl, ob, oh, ol,
+        (H * D) if km is not None else 0, D if km is not None else 0, _dtype_code(k), _stream(k))
+    _cabi.check(rc, "sage_quant_qk_int8_kvlens")
+    return out, scale
+
+
+@_eager
+def per_channel_fp8_kvlens(v: torch.Tensor, kv_lens: torch.Tensor, tensor_layout: str = "HND", scale_max: float = 448.0
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`per_channel_fp8` (without ``smooth_v``) for a right-padded batch: sample b's statistics, scales and image come from its rows
+    ``< kv_lens[b]`` only.  The tile that holds the last valid row is zero behind it, the tiles past it are not written; the scales of a
+    sample without rows are 0.  Returns ``(v_image uint8 [B,H,ceil(L/64),D,64], v_scale fp32 [B,H,D])``."""
+    v = _aligned(v, 8)
+    B, H, L, D, sb, sh, sl = _dims(v, tensor_layout)
+    _kv_lens_ok(kv_lens, v, B)
+    v_image = torch.empty((B, H, (L + 63) // 64, D, 64), dtype=torch.uint8, device=v.device)
+    v_scale = torch.empty((B, H, D), dtype=torch.float32, device=v.device)
+    ws = _stats_ws(B, H, L, D, v.device)
+    rc = _cabi.load().sage_prep_v_fp8_kvlens(_p(v), _p(v_image), _p(v_scale), _p(ws), _p(kv_lens), B, H, L, D, sb, sh, sl,
+                                             float(scale_max), _dtype_code(v), _stream(v))
+    _cabi.check(rc, "sage_prep_v_fp8_kvlens")
+    return v_image, v_scale
+
+
 @_eager
 def channel_mean_packed(x: torch.Tensor, cu_seqlens: Optional[torch.Tensor] = None, plan: Optional["VarlenPlan"] = None) -> torch.Tensor:
     """Mean over ALL tokens of a packed ``[sum L, H, D]`` tensor -> ``[1, H, D]`` (core.py:432-434).  With the slab map of a

@@ -2,7 +2,9 @@
 """Per-workgroup phase times of ONE attention launch, from the 100 MHz stamps of a -DSAGE_ATTN_TRACE=1 build of the attention units
 (tools/build_variants.sh atrace:"-DSAGE_ATTN_TRACE=1"; run with SAGE_GFX950_LIB=variants/libsage_gfx950_atrace.so).  The stamps land in a
 caller-owned buffer handed over as a launch attribute (SageLaunchAttr.trace; an ordinary build ignores it and the tool sees only zeros).
-usage: attn_trace.py [c3|c2|c5|n1k|n2k|n4k|c4|c4nc]"""
+usage: attn_trace.py [c3|c2|c5|n1k|n2k|n4k|c4|c4nc|wan|wankv]
+(wan: the FP8 default kernel on a Wan-like cross-attention, B2 H40 Lq 32760 Lk 512 D128 bf16 non-causal; wankv: the same launch through the
+kv_lens route with every length equal to Lk -- the pair shows what the per-sample length costs a short work item)"""
 import ctypes
 import os
 import sys
@@ -27,6 +29,13 @@ if name in ("c4", "c4nc"):
     cu = torch.tensor([0] + list(torch.tensor(bench.C4_LENS).cumsum(0)), dtype=torch.int32, device=dev)
     st = core._varlen_prepare(q, k, v, cu, cu, max(bench.C4_LENS), max(bench.C4_LENS), name == "c4", None, True, {})
     step = lambda: core._varlen_attend(st)
+elif name in ("wan", "wankv"):
+    g = torch.Generator(device="cpu").manual_seed(11)
+    q = torch.randn(2, 40, 32760, 128, generator=g).to(torch.bfloat16).to(dev)
+    k, v = (torch.randn(2, 40, 512, 128, generator=g).to(torch.bfloat16).to(dev) for _ in range(2))
+    kl = torch.full((2,), 512, dtype=torch.int32, device=dev) if name == "wankv" else None
+    _, _, k8, ks, vimg, vs, _ = core._prepass_kv(q, k, v, "HND", "per_thread", 64, True, False, False, False, kv_lens=kl)
+    step = lambda: core._attn_fused_q(q, k8, vimg, vs, ks, "HND", False, core._sm_log2(128 ** -0.5), False, kv_lens=kl)
 else:
     cfg = bench.CONFIGS[name]
     q, k, v = bench.make_inputs(cfg, dev, 1234)
