@@ -6,7 +6,7 @@
 #include "sage_work_order.h"
 #include <cstdlib>
 
-#ifndef SAGE_ORDER_DEFAULT   // causal work order: -1 = grouped / folded (set_work_order), 0 = head-major heavy-first, n = groups of n heads
+#ifndef SAGE_ORDER_DEFAULT   // causal work order: -1 = grouped / folded (plan_grid), 0 = head-major heavy-first, n = groups of n heads
 #define SAGE_ORDER_DEFAULT -1
 #endif
 
@@ -26,7 +26,8 @@ int work_order()
 }
 void set_work_order_mode(int group) { g_work_order = group; }
 
-static int set_work_order(AttnParams &q, bool causal, int head_dim, bool pv_fp8, bool masked)
+// the work order of a launch (q.order_*); returns its grid size
+static int plan_grid(AttnParams &q, const AttnVariant &v)
 {
     q.order_group = 0;
     q.order_fold = 0;
@@ -36,105 +37,50 @@ static int set_work_order(AttnParams &q, bool causal, int head_dim, bool pv_fp8,
         return 8 * ((q.Hq & 7) * ((q.items_bound + 7) / 8) + (q.Hq >> 3) * q.items_bound);
     if (q.cu_q != nullptr) return ((q.B * q.Hkv + 7) / 8) * 8 * q.group * q.nqblk;   // varlen: whole rounds of 8 (sequence, kv-head) units
     const int forced = work_order();
-    if (!causal || masked || q.kv_split > 1 || q.nqblk <= 1 || forced == 0) return nheads * q.nqblk;
+    // the exact split's pass 2 (one chunk included): (batch, folded head, query block) in head-major order, like the inexact split's
+    if (!v.causal || v.mask_kind != 0 || v.seeded || q.kv_split > 1 || q.nqblk <= 1 || forced == 0) return nheads * q.nqblk;
+    // (per-sample key lengths: planned for the padded q.Lk -- the order is a permutation of the items whatever the lengths are, and nothing on the
+    // host depends on their values)
     WorkOrder w;
-    const int grid = plan_work_order(w, nheads, q.nqblk, q.Lk, head_dim, pv_fp8, forced);
+    const int grid = plan_work_order(w, nheads, q.nqblk, q.Lk, v.head_dim, v.pv_fp8, forced);
     q.order_group = w.group;
     q.order_fold = w.fold;
     q.order_left = w.left;
     return grid;
 }
 
-// the instantiation unit of (head_dim, PV format, FP8 score form)
-static hipError_t launch_unit(const AttnParams &p, int head_dim, bool pv_fp8, const AttnVariant &v, int nwork, const AttnLaunchOpts &o)
+// the routes that exist: what a variant asks of the parameter block and of its own fields beyond what the ladders of sage_attn_launch.h match on
+static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLaunchOpts &o)
 {
-    if (pv_fp8 && (v.qf == 3 || v.qf == 4)) {       // the packed FP8 route's per-block fused-Q kernels (exact score form only)
-        if (head_dim == 128) return launch_attn_f8_varlen<128>(p, v, nwork, o);
-        if (head_dim == 64) return launch_attn_f8_varlen<64>(p, v, nwork, o);
-        return hipErrorInvalidValue;
-    }
-    if (head_dim == 128) {
-        if (!pv_fp8) return launch_attn_part<128, false, true>(p, v, nwork, o);
-        return o.fp8_folded ? launch_attn_part<128, true, true>(p, v, nwork, o) : launch_attn_part<128, true, false>(p, v, nwork, o);
-    }
-    if (head_dim == 64) {
-        if (!pv_fp8) return launch_attn_part<64, false, true>(p, v, nwork, o);
-        return o.fp8_folded ? launch_attn_part<64, true, true>(p, v, nwork, o) : launch_attn_part<64, true, false>(p, v, nwork, o);
-    }
-    return hipErrorInvalidValue;
+    const bool varlen = p.cu_q != nullptr, per_thread = v.qf == 1 || v.qf == 2, per_block = v.qf == 3 || v.qf == 4;
+    if ((v.head_dim != 64 && v.head_dim != 128) || v.qf < 0 || v.qf > 4 || v.mask_kind < 0 || v.mask_kind > 3) return false;
+    // a mask: INT8 q, FP16 PV, per-block scales, non-causal, the Triton kernel form
+    if (v.mask_kind != 0 && (v.qf != 0 || v.pv_fp8 || v.causal || v.kthread || !v.two_level)) return false;
+    if (per_thread && (varlen || !v.kthread || v.two_level != v.pv_fp8)) return false;
+    // per-block Q: per-block k scales; FP16 PV in the Triton kernel form; FP8 PV over packed batches only, the exact score form
+    if (per_block && (v.kthread || (v.pv_fp8 ? (!varlen || o.fp8_folded) : !v.two_level))) return false;
+    if (p.v_rows != 0 && (v.pv_fp8 || v.mask_kind != 0 || varlen || p.kv_split > 1 || v.qf == 2 || v.qf == 4)) return false;     // (fp16 q only)
+    if ((v.seeded || v.kv_lens) && (!per_thread || !v.pv_fp8 || o.fp8_folded || (v.seeded && v.kv_lens))) return false;
+    if (v.seeded != (p.seed_max != nullptr) || (v.seeded && p.kv_split < 1)) return false;
+    if (v.kv_lens && (p.cu_k == nullptr || p.kv_split > 1)) return false;
+    return true;
 }
 
-// per-thread granularity, q in fp16 (q_dtype 0) / bf16 (1), quantised in the kernel prologue
-hipError_t launch_attn_fused_q(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, bool pv_fp8, const AttnLaunchOpts &o)
+hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const AttnLaunchOpts &o)
 {
     AttnParams p = p_in;
-    const int nwork = set_work_order(p, causal, head_dim, pv_fp8, false);
+    const int nwork = plan_grid(p, v);
     if (o.grid_out != nullptr) *o.grid_out = 0;
     if (nwork <= 0) return hipSuccess;
-    if (p.cu_q != nullptr || (q_dtype != DT_F16 && q_dtype != DT_BF16)) return hipErrorInvalidValue;
-    if (p.v_rows != 0 && (pv_fp8 || q_dtype != DT_F16 || p.kv_split > 1)) return hipErrorInvalidValue;
-    const AttnVariant v = {causal, true, pv_fp8, 0, q_dtype == DT_F16 ? 1 : 2, p.v_rows != 0};
-    return launch_unit(p, head_dim, pv_fp8, v, nwork, o);
-}
-
-// the exact split's pass 2: grid over (batch, folded head, query block) in head-major order, like the inexact split's
-hipError_t launch_attn_fused_q_seeded(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o)
-{
-    AttnParams p = p_in;
-    p.order_group = 0;
-    p.order_fold = 0;
-    p.order_left = 0;
-    p.sched = nullptr;
-    const int nwork = p.B * p.Hq * p.nqblk;
-    if (o.grid_out != nullptr) *o.grid_out = 0;
-    if (nwork <= 0) return hipSuccess;
-    if (p.cu_q != nullptr || p.v_rows != 0 || (q_dtype != DT_F16 && q_dtype != DT_BF16)) return hipErrorInvalidValue;
-    const AttnVariant v = {causal, true, true, 0, q_dtype == DT_F16 ? 1 : 2, false};
-    if (head_dim == 128) return launch_attn_f8_seeded<128>(p, v, nwork, o);
-    if (head_dim == 64) return launch_attn_f8_seeded<64>(p, v, nwork, o);
-    return hipErrorInvalidValue;
-}
-
-// per-sample key lengths (p.cu_k = the [B] lengths, device memory): the work order is planned for the padded p.Lk -- it is a permutation of the
-// items whatever the lengths are, and nothing on the host depends on their values
-hipError_t launch_attn_fused_q_kvlens(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o)
-{
-    AttnParams p = p_in;
-    if (o.grid_out != nullptr) *o.grid_out = 0;
-    if (p.cu_k == nullptr || p.cu_q != nullptr || p.v_rows != 0 || p.kv_split > 1 || (q_dtype != DT_F16 && q_dtype != DT_BF16)) return hipErrorInvalidValue;
-    const int nwork = set_work_order(p, causal, head_dim, true, false);
-    if (nwork <= 0) return hipSuccess;
-    const AttnVariant v = {causal, true, true, 0, q_dtype == DT_F16 ? 1 : 2, false};
-    if (head_dim == 128) return launch_attn_f8_kvlens<128>(p, v, nwork, o);
-    if (head_dim == 64) return launch_attn_f8_kvlens<64>(p, v, nwork, o);
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_attn_fused_qblock(const AttnParams &p_in, int head_dim, bool causal, int q_dtype, bool pv_fp8, bool two_level,
-                                   const AttnLaunchOpts &o)
-{
-    AttnParams p = p_in;
-    const int nwork = set_work_order(p, causal, head_dim, pv_fp8, false);
-    if (o.grid_out != nullptr) *o.grid_out = 0;
-    if (nwork <= 0) return hipSuccess;
-    if (q_dtype != DT_F16 && q_dtype != DT_BF16) return hipErrorInvalidValue;
-    if (p.v_rows != 0 && (pv_fp8 || q_dtype != DT_F16 || p.cu_q != nullptr)) return hipErrorInvalidValue;
-    if (pv_fp8 && p.cu_q == nullptr) return hipErrorInvalidValue;          // FP8 PV with the per-block Q quantiser: packed batches only
-    const AttnVariant v = {causal, false, pv_fp8 ? two_level : true, 0, q_dtype == DT_F16 ? 3 : 4, p.v_rows != 0};
-    return launch_unit(p, head_dim, pv_fp8, v, nwork, o);
-}
-
-hipError_t launch_attn(const AttnParams &p_in, int head_dim, bool pv_fp8, bool causal, bool kthread,
-                       bool two_level, int mask_kind, const AttnLaunchOpts &o)
-{
-    AttnParams p = p_in;
-    const int nwork = set_work_order(p, causal, head_dim, pv_fp8, mask_kind != 0);
-    if (o.grid_out != nullptr) *o.grid_out = 0;
-    if (nwork <= 0) return hipSuccess;
-    if (mask_kind != 0 && (pv_fp8 || causal || kthread || mask_kind < 1 || mask_kind > 3)) return hipErrorInvalidValue;
-    if (p.v_rows != 0 && (pv_fp8 || mask_kind != 0 || p.cu_q != nullptr || p.kv_split > 1)) return hipErrorInvalidValue;
-    const AttnVariant v = {causal, kthread, mask_kind != 0 ? true : two_level, mask_kind, 0, p.v_rows != 0};
-    return launch_unit(p, head_dim, pv_fp8, v, nwork, o);
+    if (!route_exists(p, v, o)) return hipErrorInvalidValue;
+    // the instantiation unit of (head_dim, PV format, FP8 score form, seeded / kv_lens / packed FP8 with the per-block Q quantiser)
+    const bool d128 = v.head_dim == 128;
+    if (v.seeded) return d128 ? launch_attn_f8_seeded<128>(p, v, nwork, o) : launch_attn_f8_seeded<64>(p, v, nwork, o);
+    if (v.kv_lens) return d128 ? launch_attn_f8_kvlens<128>(p, v, nwork, o) : launch_attn_f8_kvlens<64>(p, v, nwork, o);
+    if (v.pv_fp8 && v.qf >= 3) return d128 ? launch_attn_f8_varlen<128>(p, v, nwork, o) : launch_attn_f8_varlen<64>(p, v, nwork, o);
+    if (!v.pv_fp8) return d128 ? launch_attn_part<128, false, true>(p, v, nwork, o) : launch_attn_part<64, false, true>(p, v, nwork, o);
+    if (o.fp8_folded) return d128 ? launch_attn_part<128, true, true>(p, v, nwork, o) : launch_attn_part<64, true, true>(p, v, nwork, o);
+    return d128 ? launch_attn_part<128, true, false>(p, v, nwork, o) : launch_attn_part<64, true, false>(p, v, nwork, o);
 }
 
 }  // namespace sage

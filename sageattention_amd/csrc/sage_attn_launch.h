@@ -68,6 +68,8 @@ static hipError_t launch_kernel(int lds, const AttnParams &p, int nwork, const A
 // The members of the family one instantiation unit holds: INT8 q (8 of causal x k-scale groups x accumulation), the fused per-thread Q
 // quantiser (fp16 / bf16 q), and for FP16 PV the masked kernels and the fused per-block Q quantiser.
 // Keys per iteration: 64 (NH = 1).
+// These launchers are called by launch_attention (sage_attn.hip) alone, after its route_exists(): they match a variant to its instantiation
+// and refuse (hipErrorInvalidValue) only what no instantiation of the unit matches.
 template <int D, bool PV_FP8, bool SFOLD>
 hipError_t launch_attn_part(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
 {
@@ -81,16 +83,14 @@ hipError_t launch_attn_part(const AttnParams &p, const AttnVariant &v, int nwork
     if (v.mask_kind != 0) {       // Triton-named API: FP16 PV, per-block scales, non-causal, tile product folded into the FP32 output
         if constexpr (!PV_FP8) {
             using CM = TileCfg<D, false, 1>;
-            if (v.causal || v.kthread || v.qf != 0) return hipErrorInvalidValue;
             if (v.mask_kind == 1) return launch_kernel<sage_attn_kernel<D, false, false, false, true, 1, 1>>(CM::LDS_BYTES, p, nwork, l, false);
             if (v.mask_kind == 2) return launch_kernel<sage_attn_kernel<D, false, false, false, true, 1, 2>>(CM::LDS_BYTES, p, nwork, l, false);
             if (v.mask_kind == 3) return launch_kernel<sage_attn_kernel<D, false, false, false, true, 1, 3>>(CM::LDS_BYTES, p, nwork, l, false);
         }
         return hipErrorInvalidValue;
     }
-    if (v.vrows) {                     // V rows read in place (fp16 V, FP16 PV, dense): fused Q quantisation per thread group / per block, or INT8 q
+    if (p.v_rows != 0) {                   // V rows read in place (fp16 V, FP16 PV, dense): fused Q quantisation per thread group / per block, or INT8 q
         if constexpr (!PV_FP8) {
-            if (packed_list || p.cu_q != nullptr) return hipErrorInvalidValue;
 #define SAGE_VR(C_) \
             if (v.causal == C_ && v.qf == 1) return launch_kernel<sage_attn_kernel<D, false, C_, true, false, NH, 0, 1, true, false, true>>(C::LDS_BYTES, p, nwork, l, pers); \
             if (v.causal == C_ && v.qf == 3) return launch_kernel<sage_attn_kernel<D, false, C_, false, true, NH, 0, 3, true, false, true>>(C::LDS_BYTES, p, nwork, l, pers);
@@ -141,7 +141,6 @@ template <int D>
 hipError_t launch_attn_f8_varlen(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
 {
     using C = TileCfg<D, true, 1>;
-    if (p.cu_q == nullptr || l.fp8_folded || v.kthread || v.vrows || v.mask_kind != 0 || (v.qf != 3 && v.qf != 4)) return hipErrorInvalidValue;
     const bool pers = !v.causal;
     if (v.causal && p.work_items != nullptr) {
 #define SAGE_F8VP(F_, T_) if (v.qf == F_ && v.two_level == T_) \
@@ -165,8 +164,6 @@ template <int D>
 hipError_t launch_attn_f8_seeded(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
 {
     using C = TileCfg<D, true, 1>;
-    if (p.seed_max == nullptr || p.cu_q != nullptr || p.kv_split < 1 || l.fp8_folded || !v.kthread || !v.two_level || v.vrows || v.mask_kind != 0)
-        return hipErrorInvalidValue;
 #define SAGE_F8S(C_, F_) if (v.causal == C_ && v.qf == F_) \
     return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, false);
     SAGE_F8S(false, 1) SAGE_F8S(false, 2) SAGE_F8S(true, 1) SAGE_F8S(true, 2)
@@ -181,9 +178,6 @@ template <int D>
 hipError_t launch_attn_f8_kvlens(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
 {
     using C = TileCfg<D, true, 1>;
-    if (p.cu_k == nullptr || p.cu_q != nullptr || p.kv_split > 1 || p.seed_max != nullptr || l.fp8_folded || !v.kthread || !v.two_level || v.vrows ||
-        v.mask_kind != 0)
-        return hipErrorInvalidValue;
 #define SAGE_F8K(C_, F_) if (v.causal == C_ && v.qf == F_) \
     return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, !C_);
     SAGE_F8K(false, 1) SAGE_F8K(false, 2) SAGE_F8K(true, 1) SAGE_F8K(true, 2)

@@ -33,6 +33,16 @@ int check_launch(hipError_t e, const char *what)
 
 #define SAGE_REQUIRE(cond, ...) do { if (!(cond)) return fail(SAGE_EINVAL, __VA_ARGS__); } while (0)
 
+// the argument checks that come back in every entry point
+#define SAGE_REQUIRE_HEAD_DIM(D, hint) SAGE_REQUIRE((D) == 64 || (D) == 128, "head_dim must be 64 or 128 (got %d)" hint, D)
+#define SAGE_REQUIRE_DTYPE(t, name) SAGE_REQUIRE((t) == SAGE_DTYPE_F16 || (t) == SAGE_DTYPE_BF16, "bad " name " %d", t)
+inline bool multiples_of(int n, int64_t a, int64_t b, int64_t c = 0) { return a % n == 0 && b % n == 0 && c % n == 0; }
+// 16-byte aligned, strides in multiples of n elements
+inline bool aligned16_strides(const void *p, int n, int64_t a, int64_t b, int64_t c = 0) { return aligned16(p) && multiples_of(n, a, b, c); }
+inline int64_t stats_slabs(int64_t L) { return (L + sage::kStatsSlab - 1) / sage::kStatsSlab; }       // 512-token slabs of a sequence of L tokens
+
+struct Strides { int64_t sb, sh, sl; };         // element strides of a [batch, head, row, D] view (packed tensors: sb = 0)
+inline bool multiples_of(int n, const Strides &s) { return multiples_of(n, s.sb, s.sh, s.sl); }
 struct MaskArg { const void *ptr; int kind; int64_t sb, sh, sq, sk; };
 
 // SageLaunchAttr (nullable) -> the launch workspace and the launcher's options; the attributes are arguments of THIS call, nothing is kept
@@ -66,89 +76,151 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     return SAGE_OK;
 }
 
-int attn_common(bool fp8, bool varlen, const int8_t *q, const int8_t *k, const void *v_image, void *o, float *lse,
-                const float *q_scale, const float *k_scale, const float *v_scale, const float *v_mean,
-                const int32_t *cu_q, const int32_t *cu_k, const int32_t *cu_qs, const int32_t *cu_ks,
-                int B, int Hq, int Hkv, int Lq, int Lk, int D,
-                int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                int64_t o_sb, int64_t o_sh, int64_t o_sl,
-                int is_causal, int gran, int q_warp, float sm_scale_log2, int pv_accum, int out_dtype, void *stream, const SageLaunchAttr *attr,
-                const MaskArg *mask = nullptr, const int32_t *seq_order = nullptr,
-                const int32_t *work_items = nullptr, const int32_t *work_hdr = nullptr, int items_bound = 0, const int64_t *v_strides = nullptr,
-                int64_t lse_sh = 0)
-{
-    LaunchAttr la;
-    if (const int rc = read_attr(attr, stream, mask == nullptr, la)) return rc;
-    SAGE_REQUIRE(!(fp8 && varlen && la.opts.fp8_folded), "packed (varlen) FP8 attention has the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES)");
-    SAGE_REQUIRE(!varlen || lse == nullptr || lse_sh > 0, "varlen lse [Hq, sum Lq]: its head stride lse_sh must be positive (got %lld)", (long long)lse_sh);
-    if (v_strides != nullptr) {            // `v_image` is the caller's fp16 value tensor itself (rows), read in place
-        SAGE_REQUIRE(!fp8 && !varlen && mask == nullptr, "V rows in place: dense, unmasked FP16-PV calls");
-        SAGE_REQUIRE(v_strides[0] % 8 == 0 && v_strides[1] % 8 == 0 && v_strides[2] % 8 == 0 && v_strides[2] >= D, "v strides must be multiples of 8 elements (16-byte rows)");
-        SAGE_REQUIRE(((int64_t)(Lk - 1) * v_strides[2] + D) * 2 < (int64_t)1 << 31, "one head of v must span less than 2 GiB");
-    }
-    SAGE_REQUIRE(q && k && v_image && o && q_scale && k_scale, "null tensor pointer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d); pad on the host as core.py:260-271 does", D);
-    SAGE_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Lq > 0, "empty problem (B=%d Hq=%d Hkv=%d Lq=%d)", B, Hq, Hkv, Lq);
-    SAGE_REQUIRE(varlen || Lk > 0, "kv_len must be positive");
-    SAGE_REQUIRE(Hq % Hkv == 0, "num_qo_heads (%d) must be divisible by num_kv_heads (%d)", Hq, Hkv);
-    SAGE_REQUIRE(out_dtype == SAGE_DTYPE_F16 || out_dtype == SAGE_DTYPE_BF16, "bad out_dtype %d", out_dtype);
-    const bool k128 = (gran & SAGE_GRAN_KBLK128) != 0;       // k scale groups of 128 keys (sm90 configuration)
-    gran &= ~SAGE_GRAN_KBLK128;
-    SAGE_REQUIRE(gran >= SAGE_GRAN_PER_BLOCK && gran <= SAGE_GRAN_PER_THREAD, "bad qk_quant_gran %d", gran);
-    SAGE_REQUIRE(!k128 || (!varlen && mask == nullptr), "128-key k scale groups: dense, unmasked attention only");
-    SAGE_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v_image) && aligned16(o), "q/k/v/o must be 16-byte aligned");
-    SAGE_REQUIRE(q_sl % 16 == 0 && k_sl % 16 == 0 && q_sh % 16 == 0 && k_sh % 16 == 0 && q_sb % 16 == 0 && k_sb % 16 == 0,
-                 "int8 q/k strides must be multiples of 16");
-    SAGE_REQUIRE(o_sl % 8 == 0 && o_sh % 8 == 0 && o_sb % 8 == 0, "output strides must be multiples of 8 elements");
-    SAGE_REQUIRE(!fp8 || v_scale, "fp8 PV needs v_scale");
-    SAGE_REQUIRE(!varlen || (cu_q && cu_k && cu_qs && cu_ks), "varlen needs cu_seqlens arrays");
+// What an attention entry point received: it sets the fields it has by name, the rest stays zero / null.
+enum QForm {
+    Q_INT8,             // INT8 q with q_scale, groups by qk_quant_gran / q_warp; scores scaled by sm_scale_log2
+    Q_FUSED_THREAD,     // fp16 / bf16 q (q_dtype), quantised per thread group in the kernel prologue; per-thread k scales; dense
+    Q_FUSED_BLOCK,      // fp16 / bf16 q, multiplied by q_premul and quantised per 128-row block in the prologue; per-block k scales
+};
+struct AttnCall {
+    QForm q_form;
+    bool pv_fp8;                     // the PV format: FP8 (v_scale) or FP16
+    const void *q; const int8_t *k; const void *v; void *o; float *lse;
+    const float *q_scale, *k_scale, *v_scale, *v_mean;
+    int B, Hq, Hkv, Lq, Lk, D;       // varlen: B = nseq, Lq = max_seqlen_q, no Lk
+    Strides qs, ks, os;
+    const Strides *v_rows;           // `v` is the caller's fp16 value tensor itself (rows of these strides), read in place; null: the tile image
+    const MaskArg *mask;
+    bool varlen;                     // packed batch: the prefix arrays, and either the work list or (nullable) seq_order
+    const int32_t *cu_q, *cu_k, *cu_qs, *cu_ks, *seq_order, *work_items, *work_hdr;
+    int items_bound;
+    int64_t lse_sh;                  // varlen lse [Hq, sum Lq]: its head stride
+    const int32_t *kv_lens;          // per-sample key lengths [B] of a dense, right-padded batch
+    int kv_split;                    // > 1: the (inexact) split, the chunks folded into Hq / Hkv by the entry point
+    int is_causal, gran, q_warp, pv_accum, q_dtype, out_dtype;
+    float sm_scale_log2, q_premul;
+    void *stream; const SageLaunchAttr *attr;
+};
 
-    sage::AttnParams p{};
-    p.sched = la.ws; p.trace = la.trace; p.trace_wgs = la.trace_wgs;
-    p.q = q; p.k = k; p.v = v_image; p.o = o; p.lse = lse;
-    p.q_scale = q_scale; p.k_scale = k_scale; p.v_scale = v_scale; p.v_mean = v_mean;
-    p.cu_q = cu_q; p.cu_k = cu_k; p.cu_qs = cu_qs; p.cu_ks = cu_ks; p.seq_order = varlen ? seq_order : nullptr;
-    SAGE_REQUIRE((work_items == nullptr) == (work_hdr == nullptr) && (work_items == nullptr || (varlen && items_bound > 0)),
-                 "the work list comes as (work_items, work_hdr, items_bound > 0), varlen only");
-    p.work_items = work_items; p.work_hdr = work_hdr; p.items_bound = items_bound;
-    p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
-    p.Lq = Lq; p.Lk = Lk;
-    p.nqblk = (Lq + sage::BLKQ - 1) / sage::BLKQ;
-    p.q_sb = q_sb; p.q_sh = q_sh; p.q_sl = q_sl;
-    p.k_sb = k_sb; p.k_sh = k_sh; p.k_sl = k_sl;
-    p.o_sb = o_sb; p.o_sh = o_sh; p.o_sl = o_sl;
-    bool kthread = false;
+// What differs per Q form: the scale groups of q and k (p.q_gran, p.qs_per_blk, p.ks_shift; kthread: four k scales per 64 keys) and where
+// sm_scale * log2(e) goes
+int set_q_form(const AttnCall &c, sage::AttnParams &p, bool &kthread)
+{
+    kthread = c.q_form == Q_FUSED_THREAD;
+    p.sm_scale_log2 = c.sm_scale_log2;
+    if (c.q_form == Q_FUSED_THREAD) { p.q_gran = sage::QG_PER_THREAD; p.qs_per_blk = 32; }
+    if (c.q_form == Q_FUSED_BLOCK) {
+        p.q_gran = sage::QG_PER_BLOCK; p.qs_per_blk = 1;
+        p.sm_scale_log2 = 1.0f;                 // sm_scale * log2(e) is folded into the quantised q (q_premul), as the reference's quantiser does
+        p.q_premul = c.q_premul;
+    }
+    if (c.q_form != Q_INT8) return SAGE_OK;
+    const bool k128 = (c.gran & SAGE_GRAN_KBLK128) != 0;       // k scale groups of 128 keys (sm90 configuration)
+    const int gran = c.gran & ~SAGE_GRAN_KBLK128;
+    SAGE_REQUIRE(gran >= SAGE_GRAN_PER_BLOCK && gran <= SAGE_GRAN_PER_THREAD, "bad qk_quant_gran %d", gran);
+    SAGE_REQUIRE(!k128 || (!c.varlen && c.mask == nullptr), "128-key k scale groups: dense, unmasked attention only");
+    SAGE_REQUIRE(!c.varlen || gran == SAGE_GRAN_PER_BLOCK, "varlen supports per_block scales only");
+    p.ks_shift = k128 ? 1 : 0;
     if (gran == SAGE_GRAN_PER_BLOCK) { p.q_gran = sage::QG_PER_BLOCK; p.qs_per_blk = 1; }
     else if (gran == SAGE_GRAN_PER_WARP) {
-        SAGE_REQUIRE(q_warp == 32 || q_warp == 16, "per_warp q_warp must be 32 or 16 (got %d)", q_warp);
-        p.q_gran = q_warp == 32 ? sage::QG_PER_WARP32 : sage::QG_PER_WARP16;
-        p.qs_per_blk = sage::BLKQ / q_warp;
+        SAGE_REQUIRE(c.q_warp == 32 || c.q_warp == 16, "per_warp q_warp must be 32 or 16 (got %d)", c.q_warp);
+        p.q_gran = c.q_warp == 32 ? sage::QG_PER_WARP32 : sage::QG_PER_WARP16;
+        p.qs_per_blk = sage::BLKQ / c.q_warp;
     } else {
-        SAGE_REQUIRE(q_warp == 32 || q_warp == 16, "per_thread q_warp must be 32 or 16 (got %d)", q_warp);
-        p.q_gran = q_warp == 32 ? sage::QG_PER_THREAD : sage::QG_PER_THREAD16;
-        p.qs_per_blk = (sage::BLKQ / q_warp) * 8; kthread = true;
+        SAGE_REQUIRE(c.q_warp == 32 || c.q_warp == 16, "per_thread q_warp must be 32 or 16 (got %d)", c.q_warp);
+        p.q_gran = c.q_warp == 32 ? sage::QG_PER_THREAD : sage::QG_PER_THREAD16;
+        p.qs_per_blk = (sage::BLKQ / c.q_warp) * 8; kthread = true;
     }
-    SAGE_REQUIRE(!varlen || gran == SAGE_GRAN_PER_BLOCK, "varlen supports per_block scales only");
+    return SAGE_OK;
+}
+
+// the geometry of a call (after set_q_form): tensors, shape, strides, scale slots
+void fill_geometry(const AttnCall &c, bool kthread, sage::AttnParams &p)
+{
+    p.q = c.q; p.k = c.k; p.v = c.v; p.o = c.o; p.lse = c.lse;
+    p.q_scale = c.q_scale; p.k_scale = c.k_scale; p.v_scale = c.v_scale; p.v_mean = c.v_mean;
+    p.cu_q = c.cu_q; p.cu_k = c.cu_k; p.cu_qs = c.cu_qs; p.cu_ks = c.cu_ks; p.seq_order = c.seq_order;
+    p.work_items = c.work_items; p.work_hdr = c.work_hdr; p.items_bound = c.items_bound;
+    p.B = c.B; p.Hq = c.Hq; p.Hkv = c.Hkv; p.group = c.Hq / c.Hkv;
+    p.Lq = c.Lq; p.Lk = c.Lk;
+    p.nqblk = (c.Lq + sage::BLKQ - 1) / sage::BLKQ;
+    p.q_sb = c.qs.sb; p.q_sh = c.qs.sh; p.q_sl = c.qs.sl;
+    p.k_sb = c.ks.sb; p.k_sh = c.ks.sh; p.k_sl = c.ks.sl;
+    p.o_sb = c.os.sb; p.o_sh = c.os.sh; p.o_sl = c.os.sl;
     p.nqs = p.nqblk * p.qs_per_blk;
-    p.ks_shift = k128 ? 1 : 0;
-    p.nks = ((Lk + (sage::BLKK << p.ks_shift) - 1) / (sage::BLKK << p.ks_shift)) * (kthread ? 4 : 1);
-    p.out_dtype = out_dtype;
-    p.lse_sh = varlen ? lse_sh : 0;
-    p.sm_scale_log2 = sm_scale_log2;
-    if (v_strides != nullptr) { p.v_rows = 1; p.v_sb = v_strides[0]; p.v_sh = v_strides[1]; p.v_sl = v_strides[2]; }
-    int mask_kind = 0;
-    if (mask != nullptr) {
-        SAGE_REQUIRE(mask->ptr, "null attn_mask pointer");
-        SAGE_REQUIRE(mask->kind >= SAGE_MASK_BOOL && mask->kind <= SAGE_MASK_BF16, "bad mask_kind %d", mask->kind);
-        SAGE_REQUIRE(!is_causal, "Mask should be None for causal attention.");           // core.py:310
-        p.mask = mask->ptr; p.m_sb = mask->sb; p.m_sh = mask->sh; p.m_sq = mask->sq; p.m_sk = mask->sk;
-        mask_kind = mask->kind;
+    p.nks = ((c.Lk + (sage::BLKK << p.ks_shift) - 1) / (sage::BLKK << p.ks_shift)) * (kthread ? 4 : 1);
+    p.out_dtype = c.out_dtype;
+    p.lse_sh = c.lse_sh;
+    p.kv_split = c.kv_split;
+    if (c.v_rows != nullptr) { p.v_rows = 1; p.v_sb = c.v_rows->sb; p.v_sh = c.v_rows->sh; p.v_sl = c.v_rows->sl; }
+}
+
+// validates the call, fills the kernel parameter block, launches
+int attn_run(const AttnCall &c)
+{
+    const bool int8q = c.q_form == Q_INT8, per_thread = c.q_form == Q_FUSED_THREAD, per_block = c.q_form == Q_FUSED_BLOCK;
+    const bool fp8 = c.pv_fp8, varlen = c.varlen, split = c.kv_split > 1;
+    LaunchAttr la;
+    if (const int rc = read_attr(c.attr, c.stream, c.mask == nullptr && !split, la)) return rc;     // (masked and split launches take no launch workspace)
+    // ---- the routes a Q form admits
+    SAGE_REQUIRE(!(fp8 && varlen && la.opts.fp8_folded), "packed (varlen) FP8 attention has the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES)");
+    SAGE_REQUIRE(c.kv_lens == nullptr || (per_thread && fp8 && !split && c.v_rows == nullptr && !la.opts.fp8_folded),
+                 "kv_lens: FP8 PV, the exact score form (SAGE_ATTR_FP8_FOLDED_SCORES), no split");
+    SAGE_REQUIRE(!(per_block && varlen) || c.cu_q != nullptr, "varlen needs cu_seqlens_q");
+    SAGE_REQUIRE(!(per_block && fp8) || (varlen && c.v_rows == nullptr), "FP8 PV with the per-block Q quantiser: packed (varlen) batches only");
+    SAGE_REQUIRE(c.kv_split >= 0 && (!split || (per_thread && c.Hkv % c.kv_split == 0)), "kv_split (%d) must divide the folded kv-head count (%d)", c.kv_split, c.Hkv);
+    if (c.v_rows != nullptr) {
+        // (no entry point can violate the first line -- every *_vrows entry is dense, unmasked, FP16 PV, fp16 q, without a split: it guards
+        // against a misuse inside this file)
+        SAGE_REQUIRE(!fp8 && !varlen && c.mask == nullptr && !split && (int8q || c.q_dtype == SAGE_DTYPE_F16),
+                     "V rows in place: dense, unmasked FP16-PV calls on fp16 inputs, no split");
+        SAGE_REQUIRE(multiples_of(8, *c.v_rows) && c.v_rows->sl >= c.D, "v strides must be multiples of 8 elements (16-byte rows)");
+        SAGE_REQUIRE(((int64_t)(c.Lk - 1) * c.v_rows->sl + c.D) * 2 < (int64_t)1 << 31, "one head of v must span less than 2 GiB");
     }
-    SAGE_REQUIRE(pv_accum >= SAGE_PV_ACCUM_SINGLE && pv_accum <= SAGE_PV_ACCUM_TRITON && (!fp8 || pv_accum != SAGE_PV_ACCUM_TRITON),
-                 "bad pv_accum %d", pv_accum);
+    // ---- the same checks for every Q form; where the forms worded a message differently, each keeps its wording
+    SAGE_REQUIRE(c.q && c.k && c.v && c.o && c.k_scale && (!int8q || c.q_scale), "null tensor pointer");
+    SAGE_REQUIRE(!fp8 || c.v_scale, per_thread ? "null tensor pointer" : "fp8 PV needs v_scale");
+    SAGE_REQUIRE_HEAD_DIM(c.D, "; pad on the host as core.py:260-271 does");
+    SAGE_REQUIRE(c.B > 0 && c.Hq > 0 && c.Hkv > 0 && c.Lq > 0 && (int8q || varlen || c.Lk > 0),
+                 int8q ? "empty problem (B=%d Hq=%d Hkv=%d Lq=%d)" : "empty problem (B=%d Hq=%d Hkv=%d Lq=%d Lk=%d)", c.B, c.Hq, c.Hkv, c.Lq, c.Lk);
+    SAGE_REQUIRE(varlen || c.Lk > 0, "kv_len must be positive");
+    SAGE_REQUIRE(c.Hq % c.Hkv == 0, "num_qo_heads (%d) must be divisible by num_kv_heads (%d)", c.Hq, c.Hkv);
+    if (!int8q) SAGE_REQUIRE_DTYPE(c.q_dtype, "q_dtype");
+    SAGE_REQUIRE_DTYPE(c.out_dtype, "out_dtype");
+    SAGE_REQUIRE(aligned16(c.q) && aligned16(c.k) && aligned16(c.v) && aligned16(c.o), "q/k/v/o must be 16-byte aligned");
+    // q strides: 16 bytes of INT8, or 8 elements of fp16 / bf16
+    SAGE_REQUIRE(multiples_of(int8q ? 16 : 8, c.qs), int8q ? "int8 q/k strides must be multiples of 16" : "q strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(16, c.ks), int8q ? "int8 q/k strides must be multiples of 16" : "int8 k strides must be multiples of 16");
+    SAGE_REQUIRE(multiples_of(8, c.os), "output strides must be multiples of 8 elements");
+    SAGE_REQUIRE(c.pv_accum >= SAGE_PV_ACCUM_SINGLE && c.pv_accum <= SAGE_PV_ACCUM_TRITON && (!fp8 || c.pv_accum != SAGE_PV_ACCUM_TRITON),
+                 "bad pv_accum %d", c.pv_accum);
+    if (varlen) {
+        SAGE_REQUIRE(!int8q || (c.cu_q && c.cu_k && c.cu_qs && c.cu_ks), "varlen needs cu_seqlens arrays");
+        SAGE_REQUIRE(c.cu_k && c.cu_ks, "varlen needs cu_seqlens_k and the k scale prefix array");
+        SAGE_REQUIRE(fp8 || c.lse == nullptr, "varlen FP16 PV returns no lse");
+        SAGE_REQUIRE(c.lse == nullptr || c.lse_sh > 0, "varlen lse [Hq, sum Lq]: its head stride lse_sh must be positive (got %lld)", (long long)c.lse_sh);
+    }
+    SAGE_REQUIRE((c.work_items == nullptr) == (c.work_hdr == nullptr) && (c.work_items == nullptr || (varlen && c.items_bound > 0)),
+                 "the work list comes as (work_items, work_hdr, items_bound > 0), varlen only");
+    if (c.mask != nullptr) {
+        SAGE_REQUIRE(c.mask->ptr, "null attn_mask pointer");
+        SAGE_REQUIRE(c.mask->kind >= SAGE_MASK_BOOL && c.mask->kind <= SAGE_MASK_BF16, "bad mask_kind %d", c.mask->kind);
+        SAGE_REQUIRE(!c.is_causal, "Mask should be None for causal attention.");           // core.py:310
+    }
+
+    sage::AttnParams p{};
+    sage::AttnVariant v{};
+    if (const int rc = set_q_form(c, p, v.kthread)) return rc;
+    fill_geometry(c, v.kthread, p);
+    p.sched = la.ws; p.trace = la.trace; p.trace_wgs = la.trace_wgs;
+    if (c.mask != nullptr) { p.mask = c.mask->ptr; p.m_sb = c.mask->sb; p.m_sh = c.mask->sh; p.m_sq = c.mask->sq; p.m_sk = c.mask->sk; v.mask_kind = c.mask->kind; }
+    if (c.kv_lens != nullptr) { p.cu_k = c.kv_lens; v.kv_lens = true; }
+    v.head_dim = c.D; v.pv_fp8 = fp8; v.causal = c.is_causal != 0;
     // FP16 PV: the kernel's TWO_LEVEL parameter selects the Triton kernel form (true) or the CUDA kernel form (false)
-    const bool two_level = fp8 ? pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : pv_accum == SAGE_PV_ACCUM_TRITON;
-    return check_launch(sage::launch_attn(p, D, fp8, is_causal != 0, kthread, two_level, mask_kind, la.opts), "sage_attn launch");
+    v.two_level = fp8 ? c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : c.pv_accum == SAGE_PV_ACCUM_TRITON;
+    v.qf = int8q ? 0 : sage::attn_qf(per_block, c.q_dtype);
+    return check_launch(sage::launch_attention(p, v, la.opts), int8q ? "sage_attn launch" : per_block ? "sage_attn_fused_qblock launch" :
+                        c.kv_lens != nullptr ? "sage_attn_fused_q_pv_f8_kvlens launch" : "sage_attn_fused_q launch");
 }
 
 }  // namespace
@@ -191,15 +263,15 @@ static int quant_common(const void *x, const void *mean, int8_t *out, float *sca
                         float pre_scale, int dtype, void *stream, const int32_t *kv_lens)
 {
     SAGE_REQUIRE(x && out && scale, "null tensor pointer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
+    SAGE_REQUIRE_HEAD_DIM(D, "");
     SAGE_REQUIRE(blk == 64 || blk == 128, "blk must be 64 or 128 (got %d)", blk);
     SAGE_REQUIRE(B > 0 && H > 0 && L > 0, "empty tensor");
-    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
+    SAGE_REQUIRE_DTYPE(dtype, "dtype");
     SAGE_REQUIRE(style >= 0 && style <= 2, "bad style %d", style);
     SAGE_REQUIRE(aligned16(x) && aligned16(out) && (!mean || aligned16(mean)), "x/out/mean must be 16-byte aligned");
-    SAGE_REQUIRE(x_sl % 8 == 0 && x_sh % 8 == 0 && x_sb % 8 == 0, "input strides must be multiples of 8 elements");
-    SAGE_REQUIRE(o_sl % 16 == 0 && o_sh % 16 == 0 && o_sb % 16 == 0, "int8 output strides must be multiples of 16");
-    SAGE_REQUIRE(!mean || (mean_sb % 8 == 0 && mean_sh % 8 == 0), "mean strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(8, x_sl, x_sh, x_sb), "input strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(16, o_sl, o_sh, o_sb), "int8 output strides must be multiples of 16");
+    SAGE_REQUIRE(!mean || multiples_of(8, mean_sb, mean_sh), "mean strides must be multiples of 8 elements");
     sage::QuantParams p{};
     p.x = x; p.mean = mean; p.out = out; p.scale = scale; p.cu = nullptr; p.cu_scale = nullptr;
     p.B = B; p.H = H; p.L = L; p.D = D;
@@ -255,12 +327,12 @@ SAGE_API int sage_quant_qk_int8_varlen(const void *x, const void *mean, int8_t *
                               int blk, float pre_scale, int dtype, void *stream)
 {
     SAGE_REQUIRE(x && out && scale && cu_seqlens && cu_scale, "null tensor pointer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
+    SAGE_REQUIRE_HEAD_DIM(D, "");
     SAGE_REQUIRE(blk == 64 || blk == 128, "blk must be 64 or 128 (got %d)", blk);
     SAGE_REQUIRE(nseq > 0 && H > 0 && max_seqlen > 0, "empty batch");
-    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
+    SAGE_REQUIRE_DTYPE(dtype, "dtype");
     SAGE_REQUIRE(aligned16(x) && aligned16(out) && (!mean || aligned16(mean)), "x/out/mean must be 16-byte aligned");
-    SAGE_REQUIRE(x_sl % 8 == 0 && x_sh % 8 == 0 && o_sl % 16 == 0 && o_sh % 16 == 0, "bad strides");
+    SAGE_REQUIRE(multiples_of(8, x_sl, x_sh) && multiples_of(16, o_sl, o_sh), "bad strides");
     sage::QuantParams p{};
     p.x = x; p.mean = mean; p.out = out; p.scale = scale; p.cu = cu_seqlens; p.cu_scale = cu_scale;
     p.B = nseq; p.H = H; p.L = max_seqlen; p.D = D;
@@ -330,14 +402,14 @@ static int stats_common(const void *x, void *mean_out, float *ws, float *stats, 
                         int64_t x_sb, int64_t x_sh, int64_t x_sl, int dtype, void *stream, const char *what, const int32_t *kv_lens = nullptr)
 {
     SAGE_REQUIRE(x && ws, "null tensor pointer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
+    SAGE_REQUIRE_HEAD_DIM(D, "");
     SAGE_REQUIRE(B > 0 && H > 0 && L > 0, "empty tensor");
-    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
+    SAGE_REQUIRE_DTYPE(dtype, "dtype");
     SAGE_REQUIRE(aligned16(x), "input must be 16-byte aligned");
-    SAGE_REQUIRE(x_sl % 8 == 0 && x_sh % 8 == 0 && x_sb % 8 == 0, "strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(8, x_sl, x_sh, x_sb), "strides must be multiples of 8 elements");
     sage::StatsParams p{};
     p.x = x; p.ws = ws; p.stats = stats; p.mean_out = mean_out;
-    p.B = B; p.H = H; p.L = L; p.D = D; p.nslab = (L + sage::kStatsSlab - 1) / sage::kStatsSlab;
+    p.B = B; p.H = H; p.L = L; p.D = D; p.nslab = stats_slabs(L);
     p.x_sb = x_sb; p.x_sh = x_sh; p.x_sl = x_sl; p.dtype = dtype;
     p.kv_lens = kv_lens;
     return check_launch(sage::launch_stats(p, static_cast<hipStream_t>(stream)), what);
@@ -348,11 +420,11 @@ static int prep_v_common(const void *v, void *v_image, float *v_scale, float *v_
                          int64_t v_sb, int64_t v_sh, int64_t v_sl, float scale_max, int dtype, int fp8, void *stream, const int32_t *kv_lens = nullptr)
 {
     SAGE_REQUIRE(v && v_image, "null tensor pointer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
+    SAGE_REQUIRE_HEAD_DIM(D, "");
     SAGE_REQUIRE(B > 0 && H > 0 && L > 0, "empty tensor");
-    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
+    SAGE_REQUIRE_DTYPE(dtype, "dtype");
     SAGE_REQUIRE(aligned16(v) && aligned16(v_image), "v / v_image must be 16-byte aligned");
-    SAGE_REQUIRE(v_sl % 8 == 0 && v_sh % 8 == 0 && v_sb % 8 == 0, "v strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(8, v_sl, v_sh, v_sb), "v strides must be multiples of 8 elements");
     sage::PrepVParams p{};
     p.v = v; p.out = v_image; p.stats = stats; p.mean_in = v_mean_in; p.v_scale = v_scale; p.v_mean = v_mean_out;
     p.cu = cu; p.cu_tiles = cu_tiles;
@@ -364,7 +436,7 @@ static int prep_v_common(const void *v, void *v_image, float *v_scale, float *v_
 
 SAGE_API int64_t sage_stats_ws_floats(int B, int H, int L, int D)
 {
-    const int64_t nslab = (L + sage::kStatsSlab - 1) / sage::kStatsSlab;
+    const int64_t nslab = stats_slabs(L);
     return (int64_t)B * H * (nslab + 1) * 3 * D;
 }
 
@@ -389,10 +461,10 @@ SAGE_API int sage_channel_mean_varlen(const void *x, void *mean_out, float *ws, 
                                       int64_t x_sl, int64_t x_sh, int dtype, void *stream)
 {
     SAGE_REQUIRE(x && ws && mean_out && cu_seqlens && slab_first && slab_seq && hdr && nseq > 0, "null tensor pointer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
-    SAGE_REQUIRE(H > 0 && total_tokens > 0 && nslab_bound >= (total_tokens + sage::kStatsSlab - 1) / sage::kStatsSlab, "empty tensor or nslab_bound too small");
-    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
-    SAGE_REQUIRE(aligned16(x) && x_sl % 8 == 0 && x_sh % 8 == 0, "input must be 16-byte aligned with strides in multiples of 8 elements");
+    SAGE_REQUIRE_HEAD_DIM(D, "");
+    SAGE_REQUIRE(H > 0 && total_tokens > 0 && nslab_bound >= stats_slabs(total_tokens), "empty tensor or nslab_bound too small");
+    SAGE_REQUIRE_DTYPE(dtype, "dtype");
+    SAGE_REQUIRE(aligned16_strides(x, 8, x_sl, x_sh), "input must be 16-byte aligned with strides in multiples of 8 elements");
     sage::StatsParams p{};
     p.x = x; p.ws = ws; p.stats = nullptr; p.mean_out = mean_out;
     p.B = 1; p.H = H; p.L = total_tokens; p.D = D; p.nslab = nslab_bound;
@@ -401,18 +473,24 @@ SAGE_API int sage_channel_mean_varlen(const void *x, void *mean_out, float *ws, 
     return check_launch(sage::launch_stats(p, static_cast<hipStream_t>(stream)), "sage_channel_mean_varlen launch");
 }
 
+// the dense FP8 V pre-pass: statistics, then scales and image; kv_lens (nullable): over the valid tokens of each sample only
+static int prep_v_fp8_dense(const void *v, void *v_image, float *v_scale, float *v_mean, float *ws, const int32_t *kv_lens,
+                            int B, int H, int L, int D, int64_t v_sb, int64_t v_sh, int64_t v_sl, float scale_max, int dtype, void *stream)
+{
+    SAGE_REQUIRE(scale_max > 0.0f, "scale_max must be positive");
+    float *stats = ws + (int64_t)B * H * stats_slabs(L) * 3 * D;      // final block lives behind the partials
+    if (const int rc = stats_common(v, nullptr, ws, stats, B, H, L, D, v_sb, v_sh, v_sl, dtype, stream,
+                                    kv_lens ? "sage_v_stats_kvlens launch" : "sage_v_stats launch", kv_lens)) return rc;
+    return prep_v_common(v, v_image, v_scale, v_mean, nullptr, stats, nullptr, nullptr, B, H, L, D, v_sb, v_sh, v_sl,
+                         scale_max, dtype, 1, stream, kv_lens);
+}
+
 SAGE_API int sage_prep_v_fp8(const void *v, void *v_image, float *v_scale, float *v_mean, float *ws,
                     int B, int H, int L, int D, int64_t v_sb, int64_t v_sh, int64_t v_sl,
                     float scale_max, int dtype, void *stream)
 {
     SAGE_REQUIRE(v_scale && ws, "fp8 V pre-pass needs v_scale and the statistics workspace");
-    SAGE_REQUIRE(scale_max > 0.0f, "scale_max must be positive");
-    const int64_t nslab = (L + sage::kStatsSlab - 1) / sage::kStatsSlab;
-    float *stats = ws + (int64_t)B * H * nslab * 3 * D;      // final block lives behind the partials
-    int rc = stats_common(v, nullptr, ws, stats, B, H, L, D, v_sb, v_sh, v_sl, dtype, stream, "sage_v_stats launch");
-    if (rc != SAGE_OK) return rc;
-    return prep_v_common(v, v_image, v_scale, v_mean, nullptr, stats, nullptr, nullptr, B, H, L, D, v_sb, v_sh, v_sl,
-                         scale_max, dtype, 1, stream);
+    return prep_v_fp8_dense(v, v_image, v_scale, v_mean, ws, nullptr, B, H, L, D, v_sb, v_sh, v_sl, scale_max, dtype, stream);
 }
 
 // FP8 V image of a dense, right-padded batch with a length per sample: statistics and scales over tokens < clamp(kv_lens[b], 0, L), the image
@@ -423,13 +501,7 @@ SAGE_API int sage_prep_v_fp8_kvlens(const void *v, void *v_image, float *v_scale
                                     float scale_max, int dtype, void *stream)
 {
     SAGE_REQUIRE(v_scale && ws && kv_lens, "sage_prep_v_fp8_kvlens needs v_scale, the statistics workspace and kv_lens");
-    SAGE_REQUIRE(scale_max > 0.0f, "scale_max must be positive");
-    const int64_t nslab = (L + sage::kStatsSlab - 1) / sage::kStatsSlab;
-    float *stats = ws + (int64_t)B * H * nslab * 3 * D;
-    int rc = stats_common(v, nullptr, ws, stats, B, H, L, D, v_sb, v_sh, v_sl, dtype, stream, "sage_v_stats_kvlens launch", kv_lens);
-    if (rc != SAGE_OK) return rc;
-    return prep_v_common(v, v_image, v_scale, nullptr, nullptr, stats, nullptr, nullptr, B, H, L, D, v_sb, v_sh, v_sl,
-                         scale_max, dtype, 1, stream, kv_lens);
+    return prep_v_fp8_dense(v, v_image, v_scale, nullptr, ws, kv_lens, B, H, L, D, v_sb, v_sh, v_sl, scale_max, dtype, stream);
 }
 
 // per-sequence V statistics of a packed batch: the stage-1 partials (the slab map's layout [1,H,nslab_bound], or nslab_bound = 0: without a
@@ -437,7 +509,7 @@ SAGE_API int sage_prep_v_fp8_kvlens(const void *v, void *v_image, float *v_scale
 static int64_t prep_v_varlen_partials(int nseq, int H, int max_seqlen, int nslab_bound, int D)
 {
     if (nslab_bound > 0) return (int64_t)H * nslab_bound * 3 * D;
-    return (int64_t)nseq * H * ((max_seqlen + sage::kStatsSlab - 1) / sage::kStatsSlab) * 3 * D;
+    return (int64_t)nseq * H * stats_slabs(max_seqlen) * 3 * D;
 }
 
 SAGE_API int64_t sage_prep_v_fp8_varlen_ws_floats(int nseq, int H, int max_seqlen, int nslab_bound, int D)
@@ -452,23 +524,23 @@ SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale
                                     float scale_max, int dtype, void *stream)
 {
     SAGE_REQUIRE(v && v_image && v_scale && ws && cu_seqlens && cu_tiles, "null tensor pointer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
+    SAGE_REQUIRE_HEAD_DIM(D, "");
     SAGE_REQUIRE(nseq >= 1 && H > 0 && total_tokens > 0 && max_seqlen > 0, "empty problem (nseq=%d H=%d total_tokens=%d max_seqlen=%d)",
                  nseq, H, total_tokens, max_seqlen);
-    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
+    SAGE_REQUIRE_DTYPE(dtype, "dtype");
     SAGE_REQUIRE(aligned16(v) && aligned16(v_image), "v / v_image must be 16-byte aligned");
-    SAGE_REQUIRE(v_sl % 8 == 0 && v_sh % 8 == 0, "v strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(8, v_sl, v_sh), "v strides must be multiples of 8 elements");
     SAGE_REQUIRE(scale_max > 0.0f, "scale_max must be positive");
     const bool map = slab_seq != nullptr;
     SAGE_REQUIRE((slab_first != nullptr) == map && (hdr != nullptr) == map, "the slab map comes as (slab_first, slab_seq, hdr) together");
-    SAGE_REQUIRE(!map || (nseq <= sage::kVarlenPlanMaxSeq && nslab_bound >= (total_tokens + sage::kStatsSlab - 1) / sage::kStatsSlab),
+    SAGE_REQUIRE(!map || (nseq <= sage::kVarlenPlanMaxSeq && nslab_bound >= stats_slabs(total_tokens)),
                  "slab map: nseq <= %d and nslab_bound >= ceil(total_tokens / %d) (got nseq=%d nslab_bound=%d)", sage::kVarlenPlanMaxSeq,
                  sage::kStatsSlab, nseq, nslab_bound);
     SAGE_REQUIRE(map || nslab_bound == 0, "nslab_bound is the slab map's (0 without one)");
     sage::StatsParams st{};
     st.x = v; st.ws = ws; st.stats = ws + prep_v_varlen_partials(nseq, H, max_seqlen, nslab_bound, D); st.mean_out = nullptr;
     st.B = nseq; st.H = H; st.L = total_tokens; st.D = D;
-    st.nslab = map ? nslab_bound : (max_seqlen + sage::kStatsSlab - 1) / sage::kStatsSlab;
+    st.nslab = map ? nslab_bound : stats_slabs(max_seqlen);
     st.x_sb = 0; st.x_sh = v_sh; st.x_sl = v_sl; st.dtype = dtype;
     st.cu = cu_seqlens; st.slab_first = slab_first; st.slab_seq = slab_seq; st.hdr = hdr; st.nseq = nseq; st.seq_stats = 1;
     if (const int rc = check_launch(sage::launch_stats(st, static_cast<hipStream_t>(stream)), "sage_v_stats_varlen launch")) return rc;
@@ -478,7 +550,7 @@ SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale
 
 SAGE_API int64_t sage_prepass_ws_floats(int B, int H, int L, int D)
 {
-    const int64_t nslab = (L + sage::kStatsSlab - 1) / sage::kStatsSlab;
+    const int64_t nslab = stats_slabs(L);
     return 2 * (int64_t)B * H * nslab * 3 * D;
 }
 
@@ -504,6 +576,15 @@ static int stream_cu_count(hipStream_t stream, int dev)
     (void)hipGetLastError();
     return cus;
 }
+// the slabs that wait for each other inside a fused pre-pass launch must be co-resident: the compute units its stream may use
+static int prepass_stream_cus(void *stream, int &cus)
+{
+    int dev = 0;
+    SAGE_REQUIRE(hipGetDevice(&dev) == hipSuccess, "no current device");
+    cus = stream_cu_count(static_cast<hipStream_t>(stream), dev);
+    return SAGE_OK;
+}
+static int prepass_max_seqlen_of(int cus) { return (cus < sage::kPrepassMaxSlabs ? cus : sage::kPrepassMaxSlabs) * sage::kStatsSlab; }
 
 SAGE_API int sage_prepass_max_seqlen(void)
 {
@@ -513,8 +594,7 @@ SAGE_API int sage_prepass_max_seqlen(void)
     if (dev != cached_dev) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        const int slabs = cus < sage::kPrepassMaxSlabs ? cus : sage::kPrepassMaxSlabs;
-        cached_len = slabs * sage::kStatsSlab;
+        cached_len = prepass_max_seqlen_of(cus);
         cached_dev = dev;
     }
     return cached_len;
@@ -543,9 +623,7 @@ SAGE_API int sage_prepass_max_seqlen_stream(void *stream)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
-    const int cus = stream_cu_count(static_cast<hipStream_t>(stream), dev);
-    const int slabs = cus < sage::kPrepassMaxSlabs ? cus : sage::kPrepassMaxSlabs;
-    return slabs * sage::kStatsSlab;
+    return prepass_max_seqlen_of(stream_cu_count(static_cast<hipStream_t>(stream), dev));
 }
 
 SAGE_API int sage_prepass_failed_heads(const uint32_t *sync, int B, int H, void *stream)
@@ -573,29 +651,25 @@ SAGE_API int sage_prepass_kv(const void *k, const void *v, void *k_mean, int8_t 
 {
     SAGE_REQUIRE(k || v, "nothing to do: both k and v are null");
     SAGE_REQUIRE(ws && sync, "the fused pre-pass needs its workspace and its sync buffer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
+    SAGE_REQUIRE_HEAD_DIM(D, "");
     SAGE_REQUIRE(B > 0 && H > 0 && L > 0, "empty tensor");
     SAGE_REQUIRE(B <= 32767 && H <= 65535, "batch / head count too large for one launch (%d, %d)", B, H);
     SAGE_REQUIRE(L <= sage_prepass_max_seqlen(), "sequence too long for the in-launch head barrier (%d > %d): use the "
                  "sage_channel_mean / sage_quant_qk_int8 / sage_prep_v_fp8 sequence", L, sage_prepass_max_seqlen());
-    {   // the slabs of a head must be co-resident: a stream restricted to a CU mask has fewer compute units than the device
-        int dev = 0;
-        SAGE_REQUIRE(hipGetDevice(&dev) == hipSuccess, "no current device");
-        const int cus = stream_cu_count(static_cast<hipStream_t>(stream), dev);
-        const int nslab_ = (L + sage::kStatsSlab - 1) / sage::kStatsSlab;
-        SAGE_REQUIRE(nslab_ <= cus, "a head of %d slabs cannot be co-resident on the %d compute units this stream may use: use the "
-                     "sage_channel_mean / sage_quant_qk_int8 / sage_prep_v_fp8 sequence", nslab_, cus);
-    }
-    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
+    int cus = 0;            // the slabs of a head must be co-resident: a stream restricted to a CU mask has fewer compute units than the device
+    if (const int rc = prepass_stream_cus(stream, cus)) return rc;
+    SAGE_REQUIRE(stats_slabs(L) <= cus, "a head of %d slabs cannot be co-resident on the %d compute units this stream may use: use the "
+                 "sage_channel_mean / sage_quant_qk_int8 / sage_prep_v_fp8 sequence", (int)stats_slabs(L), cus);
+    SAGE_REQUIRE_DTYPE(dtype, "dtype");
     // rows of the last slab past L are read through the buffer range check: their 32-bit byte offsets must not wrap either
-    const int64_t lpad = ((int64_t)L + sage::kStatsSlab - 1) / sage::kStatsSlab * sage::kStatsSlab;
+    const int64_t lpad = stats_slabs(L) * sage::kStatsSlab;
     sage::PrepassParams p{};
     p.parts = (k ? 1 : 0) | (v ? 2 : 0);
     if (k) {
         SAGE_REQUIRE(k_int8 && k_scale, "K part needs k_int8 and k_scale");
         SAGE_REQUIRE(aligned16(k) && aligned16(k_int8), "k / k_int8 must be 16-byte aligned");
-        SAGE_REQUIRE(k_sl % 8 == 0 && k_sh % 8 == 0 && k_sb % 8 == 0, "input strides must be multiples of 8 elements");
-        SAGE_REQUIRE(ko_sl % 16 == 0 && ko_sh % 16 == 0 && ko_sb % 16 == 0, "int8 output strides must be multiples of 16");
+        SAGE_REQUIRE(multiples_of(8, k_sl, k_sh, k_sb), "input strides must be multiples of 8 elements");
+        SAGE_REQUIRE(multiples_of(16, ko_sl, ko_sh, ko_sb), "int8 output strides must be multiples of 16");
         SAGE_REQUIRE(((lpad - 1) * k_sl + D) * 2 < (int64_t)1 << 32 && (lpad - 1) * ko_sl + D < (int64_t)1 << 32,
                      "one head of k (rounded up to whole 512-row slabs) spans 4 GiB or more: the kernel addresses a head with 32-bit buffer offsets");
         SAGE_REQUIRE(k_blk == 64 || k_blk == 128, "k_blk must be 64 or 128 (got %d)", k_blk);
@@ -609,7 +683,7 @@ SAGE_API int sage_prepass_kv(const void *k, const void *v, void *k_mean, int8_t 
     if (v) {
         SAGE_REQUIRE(v_image && (v_scale || v_fp16), "V part needs v_image (and v_scale for the FP8 image)");
         SAGE_REQUIRE(aligned16(v) && aligned16(v_image), "v / v_image must be 16-byte aligned");
-        SAGE_REQUIRE(v_sl % 8 == 0 && v_sh % 8 == 0 && v_sb % 8 == 0, "input strides must be multiples of 8 elements");
+        SAGE_REQUIRE(multiples_of(8, v_sl, v_sh, v_sb), "input strides must be multiples of 8 elements");
         SAGE_REQUIRE(((lpad - 1) * v_sl + D) * 2 < (int64_t)1 << 32,
                      "one head of v (rounded up to whole 512-row slabs) spans 4 GiB or more: the kernel addresses a head with 32-bit buffer offsets");
         SAGE_REQUIRE(v_fp16 || scale_max > 0.0f, "scale_max must be positive");
@@ -617,7 +691,7 @@ SAGE_API int sage_prepass_kv(const void *k, const void *v, void *k_mean, int8_t 
     }
     p.k = k; p.v = v; p.k_mean = k_mean; p.k_out = k_int8; p.k_scale = k_scale;
     p.v_image = v_image; p.v_scale = v_scale; p.v_mean = v_mean; p.ws = ws; p.sync = sync;
-    p.B = B; p.H = H; p.L = L; p.D = D; p.nslab = (L + sage::kStatsSlab - 1) / sage::kStatsSlab;
+    p.B = B; p.H = H; p.L = L; p.D = D; p.nslab = stats_slabs(L);
     p.k_sb = k_sb; p.k_sh = k_sh; p.k_sl = k_sl; p.v_sb = v_sb; p.v_sh = v_sh; p.v_sl = v_sl;
     p.ko_sb = ko_sb; p.ko_sh = ko_sh; p.ko_sl = ko_sl;
     p.k_blk = k_blk; p.k_warp = k_blk; p.k_style = k_style; p.dtype = dtype; p.scale_max = scale_max; p.v_fp16 = v_fp16 ? 1 : 0;
@@ -640,23 +714,20 @@ SAGE_API int sage_prepass_kv_varlen(const void *k, const void *v, void *k_mean, 
     SAGE_REQUIRE(!v || v_image, "V part needs v_image");
     SAGE_REQUIRE(ws && sync, "the fused pre-pass needs its workspace and its sync buffer");
     SAGE_REQUIRE(cu_seqlens_k && cu_k_scale && slab_first && slab_seq && hdr, "the varlen pre-pass needs the index arrays of sage_varlen_plan");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d)", D);
+    SAGE_REQUIRE_HEAD_DIM(D, "");
     SAGE_REQUIRE(nseq > 0 && H > 0 && total_tokens > 0 && max_seqlen_k > 0 && nslab_bound > 0, "empty batch");
     SAGE_REQUIRE(H <= 65535, "head count too large for one launch (%d)", H);
-    SAGE_REQUIRE(nslab_bound >= (total_tokens + sage::kStatsSlab - 1) / sage::kStatsSlab, "nslab_bound (%d) is below ceil(total_tokens / %d)", nslab_bound, sage::kStatsSlab);
-    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
-    {   // every slab of a head (all sequences) waits for the others when the K mean is asked for: they must be co-resident
-        int dev = 0;
-        SAGE_REQUIRE(hipGetDevice(&dev) == hipSuccess, "no current device");
-        const int cus = stream_cu_count(static_cast<hipStream_t>(stream), dev);
-        SAGE_REQUIRE(k_mean == nullptr || (nslab_bound <= sage::kPrepassMaxSlabs && nslab_bound <= cus),
-                     "up to %d slabs per head cannot wait for each other inside one launch (limit %d, %d compute units on this stream): use the "
-                     "sage_channel_mean / sage_quant_qk_int8_varlen / sage_prep_v_f16_varlen sequence", nslab_bound, sage::kPrepassMaxSlabs, cus);
-    }
-    const int64_t lpad = ((int64_t)max_seqlen_k + sage::kStatsSlab - 1) / sage::kStatsSlab * sage::kStatsSlab;
+    SAGE_REQUIRE(nslab_bound >= stats_slabs(total_tokens), "nslab_bound (%d) is below ceil(total_tokens / %d)", nslab_bound, sage::kStatsSlab);
+    SAGE_REQUIRE_DTYPE(dtype, "dtype");
+    int cus = 0;            // every slab of a head (all sequences) waits for the others when the K mean is asked for: they must be co-resident
+    if (const int rc = prepass_stream_cus(stream, cus)) return rc;
+    SAGE_REQUIRE(k_mean == nullptr || (nslab_bound <= sage::kPrepassMaxSlabs && nslab_bound <= cus),
+                 "up to %d slabs per head cannot wait for each other inside one launch (limit %d, %d compute units on this stream): use the "
+                 "sage_channel_mean / sage_quant_qk_int8_varlen / sage_prep_v_f16_varlen sequence", nslab_bound, sage::kPrepassMaxSlabs, cus);
+    const int64_t lpad = stats_slabs(max_seqlen_k) * sage::kStatsSlab;
     SAGE_REQUIRE(aligned16(k) && aligned16(k_int8) && (!v || (aligned16(v) && aligned16(v_image))), "k / k_int8 / v / v_image must be 16-byte aligned");
-    SAGE_REQUIRE(k_sl % 8 == 0 && k_sh % 8 == 0 && (!v || (v_sl % 8 == 0 && v_sh % 8 == 0)), "input strides must be multiples of 8 elements");
-    SAGE_REQUIRE(ko_sl % 16 == 0 && ko_sh % 16 == 0, "int8 output strides must be multiples of 16");
+    SAGE_REQUIRE(multiples_of(8, k_sl, k_sh) && (!v || multiples_of(8, v_sl, v_sh)), "input strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(16, ko_sl, ko_sh), "int8 output strides must be multiples of 16");
     SAGE_REQUIRE(((lpad - 1) * k_sl + D) * 2 < (int64_t)1 << 32 && (lpad - 1) * ko_sl + D < (int64_t)1 << 32 &&
                  (!v || ((lpad - 1) * v_sl + D) * 2 < (int64_t)1 << 32),
                  "one sequence of one head (rounded up to whole 512-row slabs) spans 4 GiB or more: the kernel addresses it with 32-bit buffer offsets");
@@ -698,6 +769,8 @@ SAGE_API int sage_prep_v_f16_varlen(const void *v, void *v_image, const int32_t 
 }
 
 SAGE_API int64_t sage_attn_launch_ws_bytes(void) { return sage::kAttnSchedBytes; }
+
+// ---- INT8 q with its scales
 SAGE_API int sage_attn_qk_int8_pv_f8(const int8_t *q, const int8_t *k, const void *v_image, void *o, float *lse,
                             const float *q_scale, const float *k_scale, const float *v_scale, const float *v_mean,
                             int B, int Hq, int Hkv, int Lq, int Lk, int D,
@@ -706,9 +779,14 @@ SAGE_API int sage_attn_qk_int8_pv_f8(const int8_t *q, const int8_t *k, const voi
                             int is_causal, int qk_quant_gran, int q_warp,
                             float sm_scale_log2, int pv_accum, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    return attn_common(true, false, q, k, v_image, o, lse, q_scale, k_scale, v_scale, v_mean, nullptr, nullptr, nullptr, nullptr,
-                       B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl,
-                       is_causal, qk_quant_gran, q_warp, sm_scale_log2, pv_accum, out_dtype, stream, attr);
+    AttnCall c{};
+    c.q_form = Q_INT8; c.pv_fp8 = true;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.q_scale = q_scale; c.k_scale = k_scale; c.v_scale = v_scale; c.v_mean = v_mean;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.gran = qk_quant_gran; c.q_warp = q_warp; c.sm_scale_log2 = sm_scale_log2; c.pv_accum = pv_accum;
+    c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_qk_int8_pv_f16(const int8_t *q, const int8_t *k, const void *v_image, void *o, float *lse,
@@ -719,9 +797,14 @@ SAGE_API int sage_attn_qk_int8_pv_f16(const int8_t *q, const int8_t *k, const vo
                              int is_causal, int qk_quant_gran, int q_warp,
                              float sm_scale_log2, int pv_accum, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    return attn_common(false, false, q, k, v_image, o, lse, q_scale, k_scale, nullptr, v_mean, nullptr, nullptr, nullptr, nullptr,
-                       B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl,
-                       is_causal, qk_quant_gran, q_warp, sm_scale_log2, pv_accum, out_dtype, stream, attr);
+    AttnCall c{};
+    c.q_form = Q_INT8; c.pv_fp8 = false;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.q_scale = q_scale; c.k_scale = k_scale; c.v_mean = v_mean;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.gran = qk_quant_gran; c.q_warp = q_warp; c.sm_scale_log2 = sm_scale_log2; c.pv_accum = pv_accum;
+    c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_qk_int8_pv_f16_vrows(const int8_t *q, const int8_t *k, const void *v, void *o, float *lse,
@@ -732,10 +815,15 @@ SAGE_API int sage_attn_qk_int8_pv_f16_vrows(const int8_t *q, const int8_t *k, co
                                    int is_causal, int qk_quant_gran, int q_warp,
                                    float sm_scale_log2, int pv_accum, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    const int64_t vs[3] = {v_sb, v_sh, v_sl};
-    return attn_common(false, false, q, k, v, o, lse, q_scale, k_scale, nullptr, v_mean, nullptr, nullptr, nullptr, nullptr,
-                       B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl,
-                       is_causal, qk_quant_gran, q_warp, sm_scale_log2, pv_accum, out_dtype, stream, attr, nullptr, nullptr, nullptr, nullptr, 0, vs);
+    const Strides vs = {v_sb, v_sh, v_sl};
+    AttnCall c{};
+    c.q_form = Q_INT8; c.pv_fp8 = false;
+    c.q = q; c.k = k; c.v = v; c.v_rows = &vs; c.o = o; c.lse = lse; c.q_scale = q_scale; c.k_scale = k_scale; c.v_mean = v_mean;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.gran = qk_quant_gran; c.q_warp = q_warp; c.sm_scale_log2 = sm_scale_log2; c.pv_accum = pv_accum;
+    c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_qk_int8_pv_f16_masked(const int8_t *q, const int8_t *k, const void *v_image, void *o, float *lse,
@@ -746,9 +834,14 @@ SAGE_API int sage_attn_qk_int8_pv_f16_masked(const int8_t *q, const int8_t *k, c
                                     int64_t o_sb, int64_t o_sh, int64_t o_sl, float sm_scale_log2, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
     const MaskArg m{mask, mask_kind, m_sb, m_sh, m_sq, m_sk};
-    return attn_common(false, false, q, k, v_image, o, lse, q_scale, k_scale, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl,
-                       0, SAGE_GRAN_PER_BLOCK, 128, sm_scale_log2, SAGE_PV_ACCUM_TRITON, out_dtype, stream, attr, &m);
+    AttnCall c{};
+    c.q_form = Q_INT8; c.pv_fp8 = false;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.q_scale = q_scale; c.k_scale = k_scale; c.mask = &m;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = 0; c.gran = SAGE_GRAN_PER_BLOCK; c.q_warp = 128; c.sm_scale_log2 = sm_scale_log2; c.pv_accum = SAGE_PV_ACCUM_TRITON;
+    c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_qk_int8_pv_f16_varlen(const int8_t *q, const int8_t *k, const void *v_image, void *o,
@@ -760,11 +853,16 @@ SAGE_API int sage_attn_qk_int8_pv_f16_varlen(const int8_t *q, const int8_t *k, c
                                     int64_t q_sl, int64_t q_sh, int64_t k_sl, int64_t k_sh, int64_t o_sl, int64_t o_sh,
                                     int is_causal, float sm_scale_log2, int pv_accum, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    return attn_common(false, true, q, k, v_image, o, nullptr, q_scale, k_scale, nullptr, nullptr,
-                       cu_seqlens_q, cu_seqlens_k, cu_q_scale, cu_k_scale,
-                       nseq, Hq, Hkv, max_seqlen_q, 0, D, 0, q_sh, q_sl, 0, k_sh, k_sl, 0, o_sh, o_sl,
-                       is_causal, SAGE_GRAN_PER_BLOCK, 128, sm_scale_log2, pv_accum, out_dtype, stream, attr, nullptr, seq_order,
-                       work_items, work_hdr, items_bound);
+    AttnCall c{};
+    c.q_form = Q_INT8; c.pv_fp8 = false;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.q_scale = q_scale; c.k_scale = k_scale;
+    c.varlen = true; c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.cu_qs = cu_q_scale; c.cu_ks = cu_k_scale; c.seq_order = seq_order;
+    c.work_items = work_items; c.work_hdr = work_hdr; c.items_bound = items_bound;
+    c.B = nseq; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.D = D;
+    c.qs = {0, q_sh, q_sl}; c.ks = {0, k_sh, k_sl}; c.os = {0, o_sh, o_sl};
+    c.is_causal = is_causal; c.gran = SAGE_GRAN_PER_BLOCK; c.q_warp = 128; c.sm_scale_log2 = sm_scale_log2; c.pv_accum = pv_accum;
+    c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_qk_int8_pv_f8_varlen(const int8_t *q, const int8_t *k, const void *v_image, void *o, float *lse,
@@ -776,63 +874,34 @@ SAGE_API int sage_attn_qk_int8_pv_f8_varlen(const int8_t *q, const int8_t *k, co
                                             int64_t q_sl, int64_t q_sh, int64_t k_sl, int64_t k_sh, int64_t o_sl, int64_t o_sh, int64_t lse_sh,
                                             int is_causal, float sm_scale_log2, int pv_accum, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    return attn_common(true, true, q, k, v_image, o, lse, q_scale, k_scale, v_scale, nullptr,
-                       cu_seqlens_q, cu_seqlens_k, cu_q_scale, cu_k_scale,
-                       nseq, Hq, Hkv, max_seqlen_q, 0, D, 0, q_sh, q_sl, 0, k_sh, k_sl, 0, o_sh, o_sl,
-                       is_causal, SAGE_GRAN_PER_BLOCK, 128, sm_scale_log2, pv_accum, out_dtype, stream, attr, nullptr, seq_order,
-                       work_items, work_hdr, items_bound, nullptr, lse_sh);
+    AttnCall c{};
+    c.q_form = Q_INT8; c.pv_fp8 = true;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.lse_sh = lse_sh; c.q_scale = q_scale; c.k_scale = k_scale; c.v_scale = v_scale;
+    c.varlen = true; c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.cu_qs = cu_q_scale; c.cu_ks = cu_k_scale; c.seq_order = seq_order;
+    c.work_items = work_items; c.work_hdr = work_hdr; c.items_bound = items_bound;
+    c.B = nseq; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.D = D;
+    c.qs = {0, q_sh, q_sl}; c.ks = {0, k_sh, k_sl}; c.os = {0, o_sh, o_sl};
+    c.is_causal = is_causal; c.gran = SAGE_GRAN_PER_BLOCK; c.q_warp = 128; c.sm_scale_log2 = sm_scale_log2; c.pv_accum = pv_accum;
+    c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
-static int fused_q_common(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
-                          const float *k_scale, const float *v_scale, const float *v_mean,
-                          int B, int Hq, int Hkv, int Lq, int Lk, int D,
-                          int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                          int64_t o_sb, int64_t o_sh, int64_t o_sl,
-                          int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, int kv_split, void *stream, const SageLaunchAttr *attr,
-                          bool pv_fp8 = true, const int64_t *v_strides = nullptr, const int32_t *kv_lens = nullptr)
+// ---- q in fp16 / bf16, quantised per thread group in the kernel prologue; dense.  FP8 PV: two-level accumulation; FP16 PV: straight FP32
+// accumulation, the CUDA kernel form
+SAGE_API int sage_attn_fused_q_pv_f8(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
+                                     const float *k_scale, const float *v_scale, const float *v_mean,
+                                     int B, int Hq, int Hkv, int Lq, int Lk, int D,
+                                     int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                     int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                                     int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    LaunchAttr la;
-    if (const int rc = read_attr(attr, stream, kv_split <= 1, la)) return rc;       // (split launches take no launch workspace)
-    SAGE_REQUIRE(kv_lens == nullptr || (pv_fp8 && kv_split <= 1 && v_strides == nullptr && !la.opts.fp8_folded),
-                 "kv_lens: FP8 PV, the exact score form (SAGE_ATTR_FP8_FOLDED_SCORES), no split");
-    if (v_strides != nullptr) {        // V rows in place: fp16 q / k / v tensors of one call
-        SAGE_REQUIRE(!pv_fp8 && kv_split <= 1 && q_dtype == SAGE_DTYPE_F16, "V rows in place: FP16 PV on fp16 inputs, no split");
-        SAGE_REQUIRE(v_strides[0] % 8 == 0 && v_strides[1] % 8 == 0 && v_strides[2] % 8 == 0 && v_strides[2] >= D, "v strides must be multiples of 8 elements (16-byte rows)");
-        SAGE_REQUIRE(((int64_t)(Lk - 1) * v_strides[2] + D) * 2 < (int64_t)1 << 31, "one head of v must span less than 2 GiB");
-    }
-    SAGE_REQUIRE(q && k && v_image && o && k_scale && (v_scale || !pv_fp8), "null tensor pointer");
-    SAGE_REQUIRE(kv_split >= 0 && (kv_split <= 1 || Hkv % kv_split == 0), "kv_split (%d) must divide the folded kv-head count (%d)", kv_split, Hkv);
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d); pad on the host as core.py:260-271 does", D);
-    SAGE_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Lq > 0 && Lk > 0, "empty problem (B=%d Hq=%d Hkv=%d Lq=%d Lk=%d)", B, Hq, Hkv, Lq, Lk);
-    SAGE_REQUIRE(Hq % Hkv == 0, "num_qo_heads (%d) must be divisible by num_kv_heads (%d)", Hq, Hkv);
-    SAGE_REQUIRE(q_dtype == SAGE_DTYPE_F16 || q_dtype == SAGE_DTYPE_BF16, "bad q_dtype %d", q_dtype);
-    SAGE_REQUIRE(out_dtype == SAGE_DTYPE_F16 || out_dtype == SAGE_DTYPE_BF16, "bad out_dtype %d", out_dtype);
-    SAGE_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v_image) && aligned16(o), "q/k/v/o must be 16-byte aligned");
-    SAGE_REQUIRE(q_sl % 8 == 0 && q_sh % 8 == 0 && q_sb % 8 == 0, "q strides must be multiples of 8 elements");
-    SAGE_REQUIRE(k_sl % 16 == 0 && k_sh % 16 == 0 && k_sb % 16 == 0, "int8 k strides must be multiples of 16");
-    SAGE_REQUIRE(o_sl % 8 == 0 && o_sh % 8 == 0 && o_sb % 8 == 0, "output strides must be multiples of 8 elements");
-    sage::AttnParams p{};
-    p.sched = la.ws; p.trace = la.trace; p.trace_wgs = la.trace_wgs;
-    p.q = q; p.k = k; p.v = v_image; p.o = o; p.lse = lse;
-    p.k_scale = k_scale; p.v_scale = v_scale; p.v_mean = v_mean;
-    p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
-    p.Lq = Lq; p.Lk = Lk;
-    p.nqblk = (Lq + sage::BLKQ - 1) / sage::BLKQ;
-    p.q_sb = q_sb; p.q_sh = q_sh; p.q_sl = q_sl;
-    p.k_sb = k_sb; p.k_sh = k_sh; p.k_sl = k_sl;
-    p.o_sb = o_sb; p.o_sh = o_sh; p.o_sl = o_sl;
-    p.q_gran = sage::QG_PER_THREAD; p.qs_per_blk = 32;
-    p.nqs = p.nqblk * p.qs_per_blk;
-    p.nks = ((Lk + sage::BLKK - 1) / sage::BLKK) * 4;
-    p.out_dtype = out_dtype;
-    p.sm_scale_log2 = sm_scale_log2;
-    p.kv_split = kv_split;
-    if (v_strides != nullptr) { p.v_rows = 1; p.v_sb = v_strides[0]; p.v_sh = v_strides[1]; p.v_sl = v_strides[2]; }
-    if (kv_lens != nullptr) {
-        p.cu_k = kv_lens;
-        return check_launch(sage::launch_attn_fused_q_kvlens(p, D, is_causal != 0, q_dtype, la.opts), "sage_attn_fused_q_pv_f8_kvlens launch");
-    }
-    return check_launch(sage::launch_attn_fused_q(p, D, is_causal != 0, q_dtype, pv_fp8, la.opts), "sage_attn_fused_q launch");
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.v_mean = v_mean;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_fused_q_pv_f8_kvlens(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
@@ -843,19 +912,13 @@ SAGE_API int sage_attn_fused_q_pv_f8_kvlens(const void *q, const int8_t *k, cons
                                             int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
     SAGE_REQUIRE(kv_lens, "sage_attn_fused_q_pv_f8_kvlens: null kv_lens");
-    return fused_q_common(q, k, v_image, o, lse, k_scale, v_scale, v_mean, B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl,
-                          o_sb, o_sh, o_sl, is_causal, sm_scale_log2, q_dtype, out_dtype, 0, stream, attr, true, nullptr, kv_lens);
-}
-
-SAGE_API int sage_attn_fused_q_pv_f8(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
-                                     const float *k_scale, const float *v_scale, const float *v_mean,
-                                     int B, int Hq, int Hkv, int Lq, int Lk, int D,
-                                     int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                                     int64_t o_sb, int64_t o_sh, int64_t o_sl,
-                                     int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
-{
-    return fused_q_common(q, k, v_image, o, lse, k_scale, v_scale, v_mean, B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl,
-                          o_sb, o_sh, o_sl, is_causal, sm_scale_log2, q_dtype, out_dtype, 0, stream, attr);
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.v_mean = v_mean; c.kv_lens = kv_lens;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_fused_q_pv_f16(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
@@ -865,8 +928,13 @@ SAGE_API int sage_attn_fused_q_pv_f16(const void *q, const int8_t *k, const void
                                       int64_t o_sb, int64_t o_sh, int64_t o_sl,
                                       int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    return fused_q_common(q, k, v_image, o, lse, k_scale, nullptr, v_mean, B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl,
-                          o_sb, o_sh, o_sl, is_causal, sm_scale_log2, q_dtype, out_dtype, 0, stream, attr, false);
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = false; c.pv_accum = SAGE_PV_ACCUM_SINGLE;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_mean = v_mean;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_fused_q_pv_f16_vrows(const void *q, const int8_t *k, const void *v, void *o, float *lse, const float *k_scale,
@@ -875,84 +943,74 @@ SAGE_API int sage_attn_fused_q_pv_f16_vrows(const void *q, const int8_t *k, cons
                                             int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t o_sb, int64_t o_sh, int64_t o_sl,
                                             int is_causal, float sm_scale_log2, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    const int64_t vs[3] = {v_sb, v_sh, v_sl};
-    return fused_q_common(q, k, v, o, lse, k_scale, nullptr, nullptr, B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl,
-                          o_sb, o_sh, o_sl, is_causal, sm_scale_log2, SAGE_DTYPE_F16, out_dtype, 0, stream, attr, false, vs);
+    const Strides vs = {v_sb, v_sh, v_sl};
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = false; c.pv_accum = SAGE_PV_ACCUM_SINGLE;
+    c.q = q; c.k = k; c.v = v; c.v_rows = &vs; c.o = o; c.lse = lse; c.k_scale = k_scale;       // fp16 q / k / v tensors of one call
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = SAGE_DTYPE_F16; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
-// q in fp16 / bf16, quantised per 128-row block in the kernel prologue (dense: cu_q == nullptr; varlen: packed tensors, B = nseq)
-// FP8 PV (fp8 = true, ABI 22): packed batches only, v_scale [nseq,Hkv,D], pv_accum single / two-level, lse nullable [Hq, lse_sh] by packed row
-static int fused_qblock_common(const void *q, const int8_t *k, const void *v_image, void *o, float *lse, const float *k_scale,
-                               const int32_t *cu_q, const int32_t *cu_k, const int32_t *cu_ks, const int32_t *seq_order,
-                               const int32_t *work_items, const int32_t *work_hdr, int items_bound,
-                               int B, int Hq, int Hkv, int Lq, int Lk, int D,
-                               int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                               int64_t o_sb, int64_t o_sh, int64_t o_sl,
-                               int is_causal, float q_premul, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr,
-                               const int64_t *v_strides = nullptr, bool fp8 = false, const float *v_scale = nullptr,
-                               int pv_accum = SAGE_PV_ACCUM_TRITON, int64_t lse_sh = 0)
+// the (inexact) split: kv_split >= 2 chunks of Lk_chunk keys each, folded into the kv-head dimension; partial outputs and LSEs per chunk
+static int split_check(int kv_split, const void *o_part, const float *lse_part, int Lk_chunk)
 {
-    LaunchAttr la;
-    if (const int rc = read_attr(attr, stream, true, la)) return rc;
-    const bool varlen = cu_q != nullptr;
-    if (fp8) {
-        SAGE_REQUIRE(varlen && v_strides == nullptr, "FP8 PV with the per-block Q quantiser: packed (varlen) batches only");
-        SAGE_REQUIRE(v_scale, "fp8 PV needs v_scale");
-        SAGE_REQUIRE(pv_accum == SAGE_PV_ACCUM_SINGLE || pv_accum == SAGE_PV_ACCUM_TWO_LEVEL, "bad pv_accum %d", pv_accum);
-        SAGE_REQUIRE(!la.opts.fp8_folded, "packed (varlen) FP8 attention has the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES)");
-        SAGE_REQUIRE(lse == nullptr || lse_sh > 0, "varlen lse [Hq, sum Lq]: its head stride lse_sh must be positive (got %lld)", (long long)lse_sh);
-    }
-    if (v_strides != nullptr) {
-        SAGE_REQUIRE(!varlen && q_dtype == SAGE_DTYPE_F16, "V rows in place: dense calls on fp16 inputs");
-        SAGE_REQUIRE(v_strides[0] % 8 == 0 && v_strides[1] % 8 == 0 && v_strides[2] % 8 == 0 && v_strides[2] >= D, "v strides must be multiples of 8 elements (16-byte rows)");
-        SAGE_REQUIRE(((int64_t)(Lk - 1) * v_strides[2] + D) * 2 < (int64_t)1 << 31, "one head of v must span less than 2 GiB");
-    }
-    SAGE_REQUIRE(q && k && v_image && o && k_scale, "null tensor pointer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d); pad on the host as core.py:260-271 does", D);
-    SAGE_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Lq > 0 && (varlen || Lk > 0), "empty problem (B=%d Hq=%d Hkv=%d Lq=%d Lk=%d)", B, Hq, Hkv, Lq, Lk);
-    SAGE_REQUIRE(Hq % Hkv == 0, "num_qo_heads (%d) must be divisible by num_kv_heads (%d)", Hq, Hkv);
-    SAGE_REQUIRE(q_dtype == SAGE_DTYPE_F16 || q_dtype == SAGE_DTYPE_BF16, "bad q_dtype %d", q_dtype);
-    SAGE_REQUIRE(out_dtype == SAGE_DTYPE_F16 || out_dtype == SAGE_DTYPE_BF16, "bad out_dtype %d", out_dtype);
-    SAGE_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v_image) && aligned16(o), "q/k/v/o must be 16-byte aligned");
-    SAGE_REQUIRE(q_sl % 8 == 0 && q_sh % 8 == 0 && q_sb % 8 == 0, "q strides must be multiples of 8 elements");
-    SAGE_REQUIRE(k_sl % 16 == 0 && k_sh % 16 == 0 && k_sb % 16 == 0, "int8 k strides must be multiples of 16");
-    SAGE_REQUIRE(o_sl % 8 == 0 && o_sh % 8 == 0 && o_sb % 8 == 0, "output strides must be multiples of 8 elements");
-    SAGE_REQUIRE(!varlen || (cu_k && cu_ks), "varlen needs cu_seqlens_k and the k scale prefix array");
-    SAGE_REQUIRE(!varlen || fp8 || lse == nullptr, "varlen FP16 PV returns no lse");
-    sage::AttnParams p{};
-    p.sched = la.ws; p.trace = la.trace; p.trace_wgs = la.trace_wgs;
-    p.q = q; p.k = k; p.v = v_image; p.o = o; p.lse = lse;
-    p.k_scale = k_scale; p.v_scale = fp8 ? v_scale : nullptr;
-    p.lse_sh = varlen ? lse_sh : 0;
-    p.cu_q = cu_q; p.cu_k = cu_k; p.cu_qs = nullptr; p.cu_ks = cu_ks; p.seq_order = varlen ? seq_order : nullptr;
-    SAGE_REQUIRE((work_items == nullptr) == (work_hdr == nullptr) && (work_items == nullptr || (varlen && items_bound > 0)),
-                 "the work list comes as (work_items, work_hdr, items_bound > 0), varlen only");
-    p.work_items = work_items; p.work_hdr = work_hdr; p.items_bound = items_bound;
-    p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.group = Hq / Hkv;
-    p.Lq = Lq; p.Lk = Lk;
-    p.nqblk = (Lq + sage::BLKQ - 1) / sage::BLKQ;
-    p.q_sb = q_sb; p.q_sh = q_sh; p.q_sl = q_sl;
-    p.k_sb = k_sb; p.k_sh = k_sh; p.k_sl = k_sl;
-    p.o_sb = o_sb; p.o_sh = o_sh; p.o_sl = o_sl;
-    p.q_gran = sage::QG_PER_BLOCK; p.qs_per_blk = 1;
-    p.nqs = p.nqblk;
-    p.nks = (Lk + sage::BLKK - 1) / sage::BLKK;
-    p.out_dtype = out_dtype;
-    p.sm_scale_log2 = 1.0f;                 // sm_scale * log2(e) is folded into the quantised q (q_premul), as the reference's quantiser does
-    p.q_premul = q_premul;
-    if (v_strides != nullptr) { p.v_rows = 1; p.v_sb = v_strides[0]; p.v_sh = v_strides[1]; p.v_sl = v_strides[2]; }
-    return check_launch(sage::launch_attn_fused_qblock(p, D, is_causal != 0, q_dtype, fp8, pv_accum == SAGE_PV_ACCUM_TWO_LEVEL, la.opts),
-                        "sage_attn_fused_qblock launch");
+    SAGE_REQUIRE(kv_split >= 2, "kv_split must be at least 2 (got %d)", kv_split);
+    SAGE_REQUIRE(o_part && lse_part, "split-KV needs the partial output and log-sum-exp buffers");
+    SAGE_REQUIRE(Lk_chunk % 64 == 0, "split-KV chunks are whole numbers of 64-key tiles (got %d keys)", Lk_chunk);
+    return SAGE_OK;
 }
 
+SAGE_API int sage_attn_fused_q_pv_f8_split(const void *q, const int8_t *k, const void *v_image, void *o_part, float *lse_part,
+                                           const float *k_scale, const float *v_scale, const float *v_mean,
+                                           int B, int Hq, int Hkv, int kv_split, int Lq, int Lk_chunk, int D,
+                                           int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                           int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                                           int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
+{
+    if (const int rc = split_check(kv_split, o_part, lse_part, Lk_chunk)) return rc;
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
+    c.q = q; c.k = k; c.v = v_image; c.o = o_part; c.lse = lse_part; c.k_scale = k_scale; c.v_scale = v_scale; c.v_mean = v_mean;
+    c.B = B; c.Hq = Hq * kv_split; c.Hkv = Hkv * kv_split; c.kv_split = kv_split; c.Lq = Lq; c.Lk = Lk_chunk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
+}
+
+SAGE_API int sage_attn_fused_q_pv_f16_split(const void *q, const int8_t *k, const void *v_image, void *o_part, float *lse_part,
+                                            const float *k_scale, const float *v_mean,
+                                            int B, int Hq, int Hkv, int kv_split, int Lq, int Lk_chunk, int D,
+                                            int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                            int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                                            int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
+{
+    if (const int rc = split_check(kv_split, o_part, lse_part, Lk_chunk)) return rc;
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = false; c.pv_accum = SAGE_PV_ACCUM_SINGLE;
+    c.q = q; c.k = k; c.v = v_image; c.o = o_part; c.lse = lse_part; c.k_scale = k_scale; c.v_mean = v_mean;
+    c.B = B; c.Hq = Hq * kv_split; c.Hkv = Hkv * kv_split; c.kv_split = kv_split; c.Lq = Lq; c.Lk = Lk_chunk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
+}
+
+// ---- q in fp16 / bf16, quantised per 128-row block in the kernel prologue.  FP16 PV in the Triton kernel form, dense or packed; FP8 PV (ABI 22):
+// packed batches only, v_scale [nseq,Hkv,D], pv_accum single / two-level, lse nullable [Hq, lse_sh] by packed row
 SAGE_API int sage_attn_fused_qblock_pv_f16(const void *q, const int8_t *k, const void *v_image, void *o, float *lse, const float *k_scale,
                                            int B, int Hq, int Hkv, int Lq, int Lk, int D,
                                            int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
                                            int64_t o_sb, int64_t o_sh, int64_t o_sl,
                                            int is_causal, float q_premul, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    return fused_qblock_common(q, k, v_image, o, lse, k_scale, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, Hq, Hkv, Lq, Lk, D,
-                               q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl, is_causal, q_premul, q_dtype, out_dtype, stream, attr);
+    AttnCall c{};
+    c.q_form = Q_FUSED_BLOCK; c.pv_fp8 = false; c.pv_accum = SAGE_PV_ACCUM_TRITON;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.q_premul = q_premul; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_fused_qblock_pv_f16_vrows(const void *q, const int8_t *k, const void *v, void *o, float *lse, const float *k_scale,
@@ -961,9 +1019,14 @@ SAGE_API int sage_attn_fused_qblock_pv_f16_vrows(const void *q, const int8_t *k,
                                                  int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t o_sb, int64_t o_sh, int64_t o_sl,
                                                  int is_causal, float q_premul, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    const int64_t vs[3] = {v_sb, v_sh, v_sl};
-    return fused_qblock_common(q, k, v, o, lse, k_scale, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, Hq, Hkv, Lq, Lk, D,
-                               q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl, is_causal, q_premul, SAGE_DTYPE_F16, out_dtype, stream, attr, vs);
+    const Strides vs = {v_sb, v_sh, v_sl};
+    AttnCall c{};
+    c.q_form = Q_FUSED_BLOCK; c.pv_fp8 = false; c.pv_accum = SAGE_PV_ACCUM_TRITON;
+    c.q = q; c.k = k; c.v = v; c.v_rows = &vs; c.o = o; c.lse = lse; c.k_scale = k_scale;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.q_premul = q_premul; c.q_dtype = SAGE_DTYPE_F16; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_fused_qblock_pv_f16_varlen(const void *q, const int8_t *k, const void *v_image, void *o, const float *k_scale,
@@ -973,10 +1036,15 @@ SAGE_API int sage_attn_fused_qblock_pv_f16_varlen(const void *q, const int8_t *k
                                                   int64_t q_sl, int64_t q_sh, int64_t k_sl, int64_t k_sh, int64_t o_sl, int64_t o_sh,
                                                   int is_causal, float q_premul, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
 {
-    SAGE_REQUIRE(cu_seqlens_q != nullptr, "varlen needs cu_seqlens_q");
-    return fused_qblock_common(q, k, v_image, o, nullptr, k_scale, cu_seqlens_q, cu_seqlens_k, cu_k_scale, seq_order,
-                               work_items, work_hdr, items_bound, nseq, Hq, Hkv, max_seqlen_q, 0, D, 0, q_sh, q_sl, 0, k_sh, k_sl, 0, o_sh, o_sl,
-                               is_causal, q_premul, q_dtype, out_dtype, stream, attr);
+    AttnCall c{};
+    c.q_form = Q_FUSED_BLOCK; c.pv_fp8 = false; c.pv_accum = SAGE_PV_ACCUM_TRITON;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.k_scale = k_scale;
+    c.varlen = true; c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.cu_ks = cu_k_scale; c.seq_order = seq_order;
+    c.work_items = work_items; c.work_hdr = work_hdr; c.items_bound = items_bound;
+    c.B = nseq; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.D = D;
+    c.qs = {0, q_sh, q_sl}; c.ks = {0, k_sh, k_sl}; c.os = {0, o_sh, o_sl};
+    c.is_causal = is_causal; c.q_premul = q_premul; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 SAGE_API int sage_attn_fused_qblock_pv_f8_varlen(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
@@ -988,39 +1056,15 @@ SAGE_API int sage_attn_fused_qblock_pv_f8_varlen(const void *q, const int8_t *k,
                                                  int is_causal, float q_premul, int pv_accum, int q_dtype, int out_dtype, void *stream,
                                                  const SageLaunchAttr *attr)
 {
-    SAGE_REQUIRE(cu_seqlens_q != nullptr, "varlen needs cu_seqlens_q");
-    return fused_qblock_common(q, k, v_image, o, lse, k_scale, cu_seqlens_q, cu_seqlens_k, cu_k_scale, seq_order,
-                               work_items, work_hdr, items_bound, nseq, Hq, Hkv, max_seqlen_q, 0, D, 0, q_sh, q_sl, 0, k_sh, k_sl, 0, o_sh, o_sl,
-                               is_causal, q_premul, q_dtype, out_dtype, stream, attr, nullptr, true, v_scale, pv_accum, lse_sh);
-}
-
-SAGE_API int sage_attn_fused_q_pv_f8_split(const void *q, const int8_t *k, const void *v_image, void *o_part, float *lse_part,
-                                           const float *k_scale, const float *v_scale, const float *v_mean,
-                                           int B, int Hq, int Hkv, int kv_split, int Lq, int Lk_chunk, int D,
-                                           int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                                           int64_t o_sb, int64_t o_sh, int64_t o_sl,
-                                           int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
-{
-    SAGE_REQUIRE(kv_split >= 2, "kv_split must be at least 2 (got %d)", kv_split);
-    SAGE_REQUIRE(o_part && lse_part, "split-KV needs the partial output and log-sum-exp buffers");
-    SAGE_REQUIRE(Lk_chunk % 64 == 0, "split-KV chunks are whole numbers of 64-key tiles (got %d keys)", Lk_chunk);
-    return fused_q_common(q, k, v_image, o_part, lse_part, k_scale, v_scale, v_mean, B, Hq * kv_split, Hkv * kv_split, Lq, Lk_chunk, D,
-                          q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl, is_causal, sm_scale_log2, q_dtype, out_dtype, kv_split, stream, attr);
-}
-
-SAGE_API int sage_attn_fused_q_pv_f16_split(const void *q, const int8_t *k, const void *v_image, void *o_part, float *lse_part,
-                                            const float *k_scale, const float *v_mean,
-                                            int B, int Hq, int Hkv, int kv_split, int Lq, int Lk_chunk, int D,
-                                            int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-                                            int64_t o_sb, int64_t o_sh, int64_t o_sl,
-                                            int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
-{
-    SAGE_REQUIRE(kv_split >= 2, "kv_split must be at least 2 (got %d)", kv_split);
-    SAGE_REQUIRE(o_part && lse_part, "split-KV needs the partial output and log-sum-exp buffers");
-    SAGE_REQUIRE(Lk_chunk % 64 == 0, "split-KV chunks are whole numbers of 64-key tiles (got %d keys)", Lk_chunk);
-    return fused_q_common(q, k, v_image, o_part, lse_part, k_scale, nullptr, v_mean, B, Hq * kv_split, Hkv * kv_split, Lq, Lk_chunk, D,
-                          q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl, is_causal, sm_scale_log2, q_dtype, out_dtype, kv_split, stream,
-                          attr, false);
+    AttnCall c{};
+    c.q_form = Q_FUSED_BLOCK; c.pv_fp8 = true; c.pv_accum = pv_accum;
+    c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.lse_sh = lse_sh; c.k_scale = k_scale; c.v_scale = v_scale;
+    c.varlen = true; c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.cu_ks = cu_k_scale; c.seq_order = seq_order;
+    c.work_items = work_items; c.work_hdr = work_hdr; c.items_bound = items_bound;
+    c.B = nseq; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.D = D;
+    c.qs = {0, q_sh, q_sl}; c.ks = {0, k_sh, k_sl}; c.os = {0, o_sh, o_sl};
+    c.is_causal = is_causal; c.q_premul = q_premul; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
 }
 
 // the exact split (pass 1 / pass 2): the checks the two entries share
@@ -1028,16 +1072,16 @@ static int split_exact_check(const void *q, const int8_t *k, const float *k_scal
                              int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl, int q_dtype)
 {
     SAGE_REQUIRE(q && k && k_scale, "null tensor pointer");
-    SAGE_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128 (got %d); pad on the host as core.py:260-271 does", D);
+    SAGE_REQUIRE_HEAD_DIM(D, "; pad on the host as core.py:260-271 does");
     SAGE_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Lq > 0 && Lk > 0, "empty problem (B=%d Hq=%d Hkv=%d Lq=%d Lk=%d)", B, Hq, Hkv, Lq, Lk);
     SAGE_REQUIRE(Hq % Hkv == 0, "num_qo_heads (%d) must be divisible by num_kv_heads (%d)", Hq, Hkv);
     SAGE_REQUIRE(kv_split >= 1 && Lk / 64 >= kv_split && (Lk / 64) % kv_split == 0,
                  "kv_split (%d) must divide the number of whole 64-key tiles (%d keys: %d tiles)", kv_split, Lk, Lk / 64);
     SAGE_REQUIRE((int64_t)B * Hq * kv_split * ((Lq + 127) / 128) < ((int64_t)1 << 31), "grid too large");
-    SAGE_REQUIRE(q_dtype == SAGE_DTYPE_F16 || q_dtype == SAGE_DTYPE_BF16, "bad q_dtype %d", q_dtype);
+    SAGE_REQUIRE_DTYPE(q_dtype, "q_dtype");
     SAGE_REQUIRE(aligned16(q) && aligned16(k), "q/k must be 16-byte aligned");
-    SAGE_REQUIRE(q_sl % 8 == 0 && q_sh % 8 == 0 && q_sb % 8 == 0, "q strides must be multiples of 8 elements");
-    SAGE_REQUIRE(k_sl % 16 == 0 && k_sh % 16 == 0 && k_sb % 16 == 0, "int8 k strides must be multiples of 16");
+    SAGE_REQUIRE(multiples_of(8, q_sl, q_sh, q_sb), "q strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(16, k_sl, k_sh, k_sb), "int8 k strides must be multiples of 16");
     return SAGE_OK;
 }
 
@@ -1072,25 +1116,24 @@ SAGE_API int sage_attn_fused_q_pv_f8_split_exact(const void *q, const int8_t *k,
     SAGE_REQUIRE(tail == 0 || tail == 1, "tail must be 0 (the whole chunks) or 1 (the ragged tail), got %d", tail);
     SAGE_REQUIRE(tail == 0 || Lk % 64 != 0, "tail = 1 needs a ragged key range (Lk = %d is a multiple of 64)", Lk);
     SAGE_REQUIRE(aligned16(v_image) && aligned16(o_part), "v_image / o_part must be 16-byte aligned");
-    const int nch = tail ? 1 : kv_split;                // chunks of this launch
+    const int nch = tail ? 1 : kv_split;                // chunks of this launch, folded into the kv-head dimension
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true;
+    c.q = q; c.k = k; c.v = v_image; c.o = o_part; c.lse = lse_part; c.k_scale = k_scale; c.v_scale = v_scale; c.v_mean = v_mean;
+    c.B = B; c.Hq = Hq * nch; c.Hkv = Hkv * nch; c.kv_split = nch; c.Lq = Lq; c.D = D;
+    c.Lk = tail ? Lk % 64 : (Lk / 64 / kv_split) * 64;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl};
+    c.os = {(int64_t)c.Hq * Lq * D, (int64_t)Lq * D, D};      // FP32 partials [B, Hq * nch, Lq, D], contiguous
+    c.sm_scale_log2 = sm_scale_log2; c.out_dtype = SAGE_DTYPE_F16;        // (unused: FP32 partials)
     sage::AttnParams p{};
-    p.q = q; p.k = k; p.v = v_image; p.o = o_part; p.lse = lse_part;
-    p.k_scale = k_scale; p.v_scale = v_scale; p.v_mean = v_mean;
-    p.B = B; p.Hq = Hq * nch; p.Hkv = Hkv * nch; p.group = Hq / Hkv;
-    p.Lq = Lq;
-    p.Lk = tail ? Lk % 64 : (Lk / 64 / kv_split) * 64;
-    p.nqblk = (Lq + sage::BLKQ - 1) / sage::BLKQ;
-    p.q_sb = q_sb; p.q_sh = q_sh; p.q_sl = q_sl;
-    p.k_sb = k_sb; p.k_sh = k_sh; p.k_sl = k_sl;
-    p.o_sl = D; p.o_sh = (int64_t)Lq * D; p.o_sb = (int64_t)p.Hq * Lq * D;      // FP32 partials [B, Hq * nch, Lq, D], contiguous
-    p.q_gran = sage::QG_PER_THREAD; p.qs_per_blk = 32;
-    p.nks = ((Lk + 63) / 64) * 4;
-    p.out_dtype = SAGE_DTYPE_F16;        // (unused: FP32 partials)
-    p.sm_scale_log2 = sm_scale_log2;
-    p.kv_split = nch;
+    sage::AttnVariant v{};
+    if (const int rc = set_q_form(c, p, v.kthread)) return rc;
+    fill_geometry(c, v.kthread, p);       // (also sets p.nqs, which only kernels with q scales -- INT8 q -- read)
+    p.nks = ((Lk + 63) / 64) * 4;        // the chunks read the unsplit operands in place: k scale slots per head of the unsplit call
     p.kv_base = tail ? (Lk / 64) * 64 : 0;
     p.seed_max = chunk_max; p.seed_chunks = kv_split; p.seed_first = tail ? kv_split : 0;
-    return check_launch(sage::launch_attn_fused_q_seeded(p, D, is_causal != 0, q_dtype, la.opts), "sage_attn_fused_q_pv_f8_split_exact launch");
+    v.head_dim = D; v.pv_fp8 = true; v.causal = is_causal != 0; v.two_level = true; v.qf = sage::attn_qf(false, q_dtype); v.seeded = true;
+    return check_launch(sage::launch_attention(p, v, la.opts), "sage_attn_fused_q_pv_f8_split_exact launch");
 }
 
 SAGE_API int sage_merge_states(float *o_acc, float *lse_acc, const void *o_new, const float *lse_new, void *o_out,
@@ -1100,21 +1143,20 @@ SAGE_API int sage_merge_states(float *o_acc, float *lse_acc, const void *o_new, 
     SAGE_REQUIRE(o_acc && lse_acc && o_new && lse_new, "null tensor pointer");
     SAGE_REQUIRE(B > 0 && H > 0 && L > 0, "empty problem (B=%d H=%d L=%d)", B, H, L);
     SAGE_REQUIRE(D > 0 && D % 8 == 0 && D <= 512, "head_dim must be a positive multiple of 8, at most 512 (got %d)", D);
-    SAGE_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "bad dtype %d", dtype);
+    SAGE_REQUIRE_DTYPE(dtype, "dtype");
     SAGE_REQUIRE(aligned16(o_acc) && aligned16(o_new) && (o_out == nullptr || aligned16(o_out)), "o tensors must be 16-byte aligned");
-    SAGE_REQUIRE(n_sb % 8 == 0 && n_sh % 8 == 0 && n_sl % 8 == 0, "o_new strides must be multiples of 8 elements");
-    SAGE_REQUIRE(o_out == nullptr || (o_sb % 8 == 0 && o_sh % 8 == 0 && o_sl % 8 == 0), "o_out strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(8, n_sb, n_sh, n_sl), "o_new strides must be multiples of 8 elements");
+    SAGE_REQUIRE(o_out == nullptr || multiples_of(8, o_sb, o_sh, o_sl), "o_out strides must be multiples of 8 elements");
     sage::MergeParams p{};
     p.o_acc = o_acc; p.lse_acc = lse_acc; p.o_new = o_new; p.lse_new = lse_new; p.o_out = o_out;
     p.B = B; p.H = H; p.L = L; p.D = D;
     p.n_sb = n_sb; p.n_sh = n_sh; p.n_sl = n_sl; p.o_sb = o_sb; p.o_sh = o_sh; p.o_sl = o_sl;
     p.dtype = dtype; p.first = first != 0;
-    const hipError_t e = sage::launch_merge_states(p, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(SAGE_ELAUNCH, "sage_merge_states launch: %s", hipGetErrorString(e));
-    return SAGE_OK;
+    return check_launch(sage::launch_merge_states(p, reinterpret_cast<hipStream_t>(stream)), "sage_merge_states launch");
 }
 
-SAGE_API int sage_merge_split(const void *o_part, const float *lse_part, const void *o_tail, const float *lse_tail,
+// the split-KV merge over fp16 partials (sage_merge_split) or over the exact split's FP32 partials (sage_merge_split_f32)
+static int merge_split_common(bool f32, const void *o_part, const float *lse_part, const void *o_tail, const float *lse_tail,
                               void *o_out, float *lse_out, int B, int S, int H, int group, int L, int D,
                               int64_t o_sb, int64_t o_sh, int64_t o_sl, int out_dtype, void *stream)
 {
@@ -1123,35 +1165,28 @@ SAGE_API int sage_merge_split(const void *o_part, const float *lse_part, const v
     SAGE_REQUIRE((o_tail == nullptr) == (lse_tail == nullptr), "o_tail and lse_tail come together");
     SAGE_REQUIRE(B > 0 && S > 0 && H > 0 && L > 0, "empty problem (B=%d S=%d H=%d L=%d)", B, S, H, L);
     SAGE_REQUIRE(D > 0 && D % 8 == 0 && D <= 512, "head_dim must be a positive multiple of 8, at most 512 (got %d)", D);
-    SAGE_REQUIRE(out_dtype == SAGE_DTYPE_F16 || out_dtype == SAGE_DTYPE_BF16, "bad out_dtype %d", out_dtype);
+    SAGE_REQUIRE_DTYPE(out_dtype, "out_dtype");
     SAGE_REQUIRE(aligned16(o_part) && aligned16(o_out) && (o_tail == nullptr || aligned16(o_tail)), "o tensors must be 16-byte aligned");
-    SAGE_REQUIRE(o_sb % 8 == 0 && o_sh % 8 == 0 && o_sl % 8 == 0, "o_out strides must be multiples of 8 elements");
+    SAGE_REQUIRE(multiples_of(8, o_sb, o_sh, o_sl), "o_out strides must be multiples of 8 elements");
     sage::SplitMergeParams p{};
     p.o_part = o_part; p.lse_part = lse_part; p.o_tail = o_tail; p.lse_tail = lse_tail; p.o_out = o_out; p.lse_out = lse_out;
     p.B = B; p.S = S; p.H = H; p.L = L; p.D = D; p.group = group; p.o_sb = o_sb; p.o_sh = o_sh; p.o_sl = o_sl; p.dtype = out_dtype;
-    const hipError_t e = sage::launch_merge_split(p, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(SAGE_ELAUNCH, "sage_merge_split launch: %s", hipGetErrorString(e));
-    return SAGE_OK;
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return f32 ? check_launch(sage::launch_merge_split_f32(p, s), "sage_merge_split_f32 launch") : check_launch(sage::launch_merge_split(p, s), "sage_merge_split launch");
+}
+
+SAGE_API int sage_merge_split(const void *o_part, const float *lse_part, const void *o_tail, const float *lse_tail,
+                              void *o_out, float *lse_out, int B, int S, int H, int group, int L, int D,
+                              int64_t o_sb, int64_t o_sh, int64_t o_sl, int out_dtype, void *stream)
+{
+    return merge_split_common(false, o_part, lse_part, o_tail, lse_tail, o_out, lse_out, B, S, H, group, L, D, o_sb, o_sh, o_sl, out_dtype, stream);
 }
 
 SAGE_API int sage_merge_split_f32(const float *o_part, const float *lse_part, const float *o_tail, const float *lse_tail,
                                   void *o_out, float *lse_out, int B, int S, int H, int group, int L, int D,
                                   int64_t o_sb, int64_t o_sh, int64_t o_sl, int out_dtype, void *stream)
 {
-    SAGE_REQUIRE(group > 0 && H % group == 0, "num heads (%d) must be divisible by the GQA group size (%d)", H, group);
-    SAGE_REQUIRE(o_part && lse_part && o_out, "null tensor pointer");
-    SAGE_REQUIRE((o_tail == nullptr) == (lse_tail == nullptr), "o_tail and lse_tail come together");
-    SAGE_REQUIRE(B > 0 && S > 0 && H > 0 && L > 0, "empty problem (B=%d S=%d H=%d L=%d)", B, S, H, L);
-    SAGE_REQUIRE(D > 0 && D % 8 == 0 && D <= 512, "head_dim must be a positive multiple of 8, at most 512 (got %d)", D);
-    SAGE_REQUIRE(out_dtype == SAGE_DTYPE_F16 || out_dtype == SAGE_DTYPE_BF16, "bad out_dtype %d", out_dtype);
-    SAGE_REQUIRE(aligned16(o_part) && aligned16(o_out) && (o_tail == nullptr || aligned16(o_tail)), "o tensors must be 16-byte aligned");
-    SAGE_REQUIRE(o_sb % 8 == 0 && o_sh % 8 == 0 && o_sl % 8 == 0, "o_out strides must be multiples of 8 elements");
-    sage::SplitMergeParams p{};
-    p.o_part = o_part; p.lse_part = lse_part; p.o_tail = o_tail; p.lse_tail = lse_tail; p.o_out = o_out; p.lse_out = lse_out;
-    p.B = B; p.S = S; p.H = H; p.L = L; p.D = D; p.group = group; p.o_sb = o_sb; p.o_sh = o_sh; p.o_sl = o_sl; p.dtype = out_dtype;
-    const hipError_t e = sage::launch_merge_split_f32(p, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(SAGE_ELAUNCH, "sage_merge_split_f32 launch: %s", hipGetErrorString(e));
-    return SAGE_OK;
+    return merge_split_common(true, o_part, lse_part, o_tail, lse_tail, o_out, lse_out, B, S, H, group, L, D, o_sb, o_sh, o_sl, out_dtype, stream);
 }
 
 }  // extern "C"

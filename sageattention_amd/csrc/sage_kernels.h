@@ -26,7 +26,7 @@ struct AttnParams {
     const void *mask;         // attn_mask (bool bytes or fp16/bf16 additive), element strides below; null = none
     long m_sb, m_sh, m_sq, m_sk;
     const int32_t *cu_q;      // varlen only (null => dense)
-    const int32_t *cu_k;      // (dense launch_attn_fused_q_kvlens: the per-sample key lengths [B] instead, clamped to [0, Lk] by the kernel)
+    const int32_t *cu_k;      // (AttnVariant::kv_lens: the per-sample key lengths [B] instead, clamped to [0, Lk] by the kernel)
     const int32_t *cu_qs;     // prefix sums of ceil(Lq_i/128)
     const int32_t *cu_ks;     // prefix sums of ceil(Lk_i/64)
     const int32_t *seq_order; // varlen, nullable: permutation of sequence indices in processing order (legacy unit order, no work list)
@@ -49,13 +49,13 @@ struct AttnParams {
     int out_dtype;            // DT_F16 / DT_BF16
     long lse_sh;              // varlen lse head stride (unused for dense)
     float sm_scale_log2;      // multiplier taking dequantised scores to the log2 domain
-    float q_premul;           // fused per-block Q quantisation (launch_attn_fused_qblock): q is multiplied by this before its abs-max
-    int order_group;          // set by the launchers (sage_attn.hip set_work_order): causal dense work order, heads per group; 0 = head-major
+    float q_premul;           // fused per-block Q quantisation (AttnVariant::qf 3 / 4): q is multiplied by this before its abs-max
+    int order_group;          // set by the launcher (sage_attn.hip plan_grid): causal dense work order, heads per group; 0 = head-major
     int order_fold;           // 1: single-round grid, pair the i-th longest with the i-th shortest block on a CU
     int order_left;           // (B * Hq) % 8 heads whose query blocks are dealt to all eight XCDs
     unsigned *trace;          // -DSAGE_ATTN_TRACE=1 builds (tools/attn_trace.py): 16 words per logical workgroup, nullable; ignored otherwise
     int trace_wgs;
-    // the exact split's pass 2 (launch_attn_fused_q_seeded; zero / null for every other launch): kv_split chunks of Lk keys from key kv_base on,
+    // the exact split's pass 2 (AttnVariant::seeded; zero / null for every other launch): kv_split chunks of Lk keys from key kv_base on,
     // folded into the kv-head dimension as above but reading the unsplit operands in place (nks: k scale slots per head of the unsplit call);
     // seed_max: pass 1's chunk maxima [B, Hkv, seed_chunks, group, Lq], seed_first: the pass-1 chunks in front of this launch's chunk 0
     const float *seed_max;
@@ -70,21 +70,31 @@ struct AttnLaunchOpts {
     bool force_persistent;   // take the ticket queues whatever the number of rounds (tests; AttnParams::sched must be set)
     int *grid_out;           // nullable (host): receives the number of workgroups launched
 };
-// mask_kind: 0 none, 1 bool, 2 additive fp16, 3 additive bf16 (FP16-PV, per-block scales, non-causal only)
-hipError_t launch_attn(const AttnParams &p, int head_dim, bool pv_fp8, bool causal, bool kthread,
-                       bool two_level, int mask_kind, const AttnLaunchOpts &o);
-// q in fp16 / bf16, quantised per-thread in the kernel prologue; dense only.  FP8 PV: two-level accumulation; FP16 PV: FP32 accumulation
-hipError_t launch_attn_fused_q(const AttnParams &p, int head_dim, bool causal, int q_dtype, bool pv_fp8, const AttnLaunchOpts &o);
-// the exact split's pass 2: q in fp16 / bf16, quantised per thread group in the prologue, FP8 PV two-level, exact score form, running maximum
-// seeded from p.seed_max, FP32 partial outputs (p.o) and log2-domain LSEs (p.lse) per chunk; p.kv_split >= 1 chunks of p.Lk keys from p.kv_base
-hipError_t launch_attn_fused_q_seeded(const AttnParams &p, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o);
-// per-sample key lengths (dense, FP8 PV two-level, exact score form): p.cu_k = int32 lengths [B] in device memory, sample b attends to keys
-// 0 .. clamp(cu_k[b], 0, p.Lk) - 1 of the padded tensors; k / its scales / the V image from sage_quant_qk_int8_kvlens / sage_prep_v_fp8_kvlens
-hipError_t launch_attn_fused_q_kvlens(const AttnParams &p, int head_dim, bool causal, int q_dtype, const AttnLaunchOpts &o);
-// q in fp16 / bf16, quantised per 128-row block in the prologue after the multiplication by p.q_premul; per-block k scales.  FP16 PV in
-// the Triton kernels' form, dense or varlen (p.cu_q); FP8 PV (varlen only, the exact score form): two_level or single accumulation
-hipError_t launch_attn_fused_qblock(const AttnParams &p, int head_dim, bool causal, int q_dtype, bool pv_fp8, bool two_level,
-                                   const AttnLaunchOpts &o);
+// Which member of the kernel family a launch takes: the instantiation unit (head_dim, pv_fp8, AttnLaunchOpts::fp8_folded, seeded, kv_lens; the
+// per-block fused Q quantiser with FP8 PV has units of its own) and everything else the template arguments of sage_attn_kernel encode.
+//   INT8 q (qf 0)            every field below; a mask: FP16 PV, per-block scales, non-causal, the Triton kernel form
+//   fused per-thread Q (1/2) dense; kthread, two_level = pv_fp8 (FP16 PV: straight FP32 accumulation)
+//   fused per-block Q (3/4)  per-block k scales after the multiplication by AttnParams::q_premul; FP16 PV in the Triton kernel form, dense or
+//                            varlen (AttnParams::cu_q); FP8 PV varlen only, the exact score form, two_level or single accumulation
+struct AttnVariant {
+    int head_dim;       // 64 / 128
+    bool pv_fp8;
+    bool causal;
+    bool kthread;       // per-thread k scale groups (4 per 64 keys)
+    bool two_level;     // FP8 PV: tile product from a zero accumulator; FP16 PV: the Triton kernel form (SAGE_PV_ACCUM_TRITON)
+    int mask_kind;      // 0 none, 1 bool, 2 additive fp16, 3 additive bf16
+    int qf;             // 0: INT8 q + q_scale; attn_qf(): fp16 / bf16 q quantised in the prologue per thread group (1 / 2) or per 128-row block (3 / 4)
+    bool seeded;        // the exact split's pass 2 (fused per-thread Q, FP8 PV two-level, exact score form): the running maximum is seeded from
+                        // AttnParams::seed_max, p.o takes FP32 partial outputs and p.lse log2-domain LSEs per chunk; p.kv_split >= 1 chunks of p.Lk
+                        // keys from p.kv_base; head-major grid, no launch workspace
+    bool kv_lens;       // per-sample key lengths (same kernels otherwise, dense): AttnParams::cu_k = int32 lengths [B] in device memory, sample b
+                        // attends to keys 0 .. clamp(cu_k[b], 0, p.Lk) - 1 of the padded tensors; k / its scales / the V image from
+                        // sage_quant_qk_int8_kvlens / sage_prep_v_fp8_kvlens
+};
+constexpr int attn_qf(bool per_block, int q_dtype) { return (per_block ? 3 : 1) + (q_dtype == 0 ? 0 : 1); }   // q_dtype: DT_F16 (0) / DT_BF16
+// the one attention launcher: plans the work order, checks that the route exists (hipErrorInvalidValue) and launches the variant's kernel.
+// V rows in place (AttnParams::v_rows): FP16 PV, qf 0 / 1 / 3, dense, unmasked, no split
+hipError_t launch_attention(const AttnParams &p, const AttnVariant &v, const AttnLaunchOpts &o);
 
 // causal dense work order of the 128-row kernels: -1 grouped / folded by grid size, 0 head-major, n groups of n heads (SAGE_ORDER_GROUP)
 int work_order();

@@ -12,13 +12,54 @@ from sageattention_amd import _cabi
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sage_gfx950.h")
 
 
+def header_text():
+    """include/sage_gfx950.h without its comments"""
+    return re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+
+
+def prototypes():
+    """name -> (return type, [(parameter type, parameter name), ...]) of every SAGE_API prototype, types as written (`const void *`, `int64_t`)"""
+    out = {}
+    for ret, name, args in re.findall(r"SAGE_API\s+([\w\s\*]+?)\b(sage_\w+)\s*\(([^)]*)\)\s*;", header_text()):
+        params = []
+        for a in ([] if args.strip() == "void" else args.split(",")):
+            ctype, pname = re.fullmatch(r"\s*(.*?)(\w+)\s*", a, flags=re.S).groups()
+            params.append((" ".join(ctype.split()), pname))
+        assert name not in out, f"{name} declared twice"
+        out[name] = (" ".join(ret.split()), params)
+    return out
+
+
 def declared_symbols():
-    txt = open(HEADER).read()
-    return sorted(set(re.findall(r"SAGE_API\s+[\w\s\*]+?\b(sage_\w+)\s*\(", txt)))
+    return sorted(prototypes())
+
+
+def ctype_of(ctype):
+    """the ctypes type the binding must use for a C type of the header"""
+    if ctype == "const char *":
+        return ctypes.c_char_p
+    if ctype.endswith("*"):
+        return ctypes.c_void_p
+    return {"void": None, "int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}[ctype]
 
 
 def test_binding_covers_header():
-    assert declared_symbols() == sorted(_cabi.SYMBOLS)
+    """_cabi.SYMBOLS is the header, prototype by prototype: the same names, and for each the return type and the kind of every parameter in
+    order (ctypes takes a wrong count or width without a word and corrupts the call); the constants _cabi mirrors have the header's values."""
+    protos = prototypes()
+    assert len(protos) == 56          # a deliberate tripwire: ABI 22 has 56 entry points, a new one comes with a look at this file and the header's log
+    assert sorted(protos) == sorted(_cabi.SYMBOLS)
+    for name, (ret, params) in protos.items():
+        res, argtypes = _cabi.SYMBOLS[name]
+        assert res is ctype_of(ret), f"{name}: returns {ret}, bound as {res}"
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters declared, {len(argtypes)} bound"
+        for i, ((ctype, pname), bound) in enumerate(zip(params, argtypes)):
+            assert bound is ctype_of(ctype), f"{name}: parameter {i} ({ctype} {pname}) bound as {bound}"
+    defines = {n: int(v.rstrip("u"), 0) for n, v in re.findall(r"#define\s+SAGE_(\w+)\s+\(?(-?(?:0x[0-9a-fA-F]+|\d+)u?)\)?\s*$", header_text(), flags=re.M)}
+    families = ("ABI_VERSION", "DTYPE_", "GRAN_", "QSTYLE_", "PV_ACCUM_", "MASK_", "ATTR_")
+    mirrored = {n: getattr(_cabi, n) for n in dir(_cabi) if n.startswith(families)}
+    assert mirrored == {n: v for n, v in defines.items() if n.startswith(families)}
+    assert {f for f in families if any(n.startswith(f) for n in mirrored)} == set(families)
 
 
 def test_library_exports_every_symbol():
