@@ -315,6 +315,17 @@ SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale
  *  launch_ws_bytes  size of that block (checked)
  *  grid_out         nullable HOST pointer: receives the number of workgroups launched (a persistent launch has fewer than work items)
  *  trace, trace_wgs debug: read by -DSAGE_ATTN_TRACE=1 builds only (tools/attn_trace.py); 16 words per logical workgroup
+ *  q_start          nullable, appended under ABI 22 (a caller whose struct_bytes ends before it passes none): int32 [B] in DEVICE memory, the
+ *                   position of query row 0 of each sample on the key axis (Python: q_start= / causal_align=).  Honoured by
+ *                   sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 alone: row i of sample b attends to key j iff j <= q_start[b] + i and
+ *                   j < len_b, len_b = clamp(kv_lens[b], 0, Lk).  0 is the top-left causal mask of that entry, len_b - Lq the bottom-right
+ *                   one (chunked prefill, speculative verification, a prompt continued against a cached prefix).  Read by the kernel only
+ *                   and clamped there to [-Lq, Lk]: no host read, no synchronisation, grid and work order follow from the shapes, a captured
+ *                   graph follows the array's contents.  A row with q_start[b] + i < 0, and every row of a sample with len_b = 0, sees
+ *                   nothing: o = +0, lse = -inf, never NaN.  Key rows from len_b on are never read.  A multiple of 64 keeps the pipelined
+ *                   diagonal tiles; any other offset runs the diagonal of a query block as three general tiles (correct, slower).  Every
+ *                   other sage_attn_* entry point, and that one with is_causal = 0 or SAGE_ATTR_FP8_FOLDED_SCORES, refuses a non-null
+ *                   q_start (SAGE_EINVAL).  The reference has no counterpart (its causal mask is top-left, qk_int_sv_f8_cuda_sm89.cuh:237-241).
  */
 typedef struct SageLaunchAttr {
     uint32_t struct_bytes;
@@ -325,6 +336,7 @@ typedef struct SageLaunchAttr {
     uint32_t *trace;
     int32_t trace_wgs;
     int32_t reserved;
+    const int32_t *q_start;
 } SageLaunchAttr;
 /* The softmax argument of a score is fma(s, c, -m) with s the INT32 dot product, c the dequantisation scale in the log2 domain and m the
  * running row maximum (attn_utils.cuh:445-449).  The kernels read the accumulator's bit pattern as the float bias + s * 2^-26

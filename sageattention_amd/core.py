@@ -151,11 +151,12 @@ def _v_rows_wanted(q, k, v, tensor_layout: str, is_causal: bool, override) -> bo
 
 @torch.compiler.disable
 def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, sm_scale_log2, return_lse, v_mean=None, folded_scores=False,
-                  v_rows=False, kv_lens=None):
+                  v_rows=False, kv_lens=None, q_start=None):
     """FP8-PV two-level attention with the per-thread Q quantisation done in the kernel prologue
     (``sage_attn_fused_q_pv_f8``): bit-identical to ``per_thread_int8`` + the attention op, one launch and
     3 B/element of HBM traffic less.  ``v_rows`` (FP16 PV): ``v_image`` is the fp16 V tensor itself, read in place.
-    ``kv_lens`` (FP8 PV, int32 [B] on the device): a key length per sample (``sage_attn_fused_q_pv_f8_kvlens``)."""
+    ``kv_lens`` (FP8 PV, int32 [B] on the device): a key length per sample (``sage_attn_fused_q_pv_f8_kvlens``); ``q_start`` (with
+    ``kv_lens``, causal; int32 [B] on the device): a query offset per sample (``SageLaunchAttr.q_start``)."""
     B, Hq, Lq, D, q_sb, q_sh, q_sl = _dims(q, tensor_layout)
     _, Hkv, Lk, _, k_sb, k_sh, k_sl = _dims(k_int8, tensor_layout)
     assert Hq % Hkv == 0, "num_qo_heads must be divisible by num_kv_heads"
@@ -164,7 +165,8 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
     lse = torch.empty((B, Hq, Lq), dtype=torch.float32, device=q.device) if return_lse else None
     code = _cabi.DTYPE_F16 if q.dtype == torch.float16 else _cabi.DTYPE_BF16
     # (a large non-causal call: persistent launch; FP8 PV: the score form)
-    attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None)
+    assert q_start is None or (kv_lens is not None and is_causal)
+    attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None, q_start=q_start)
     if v_rows:                     # FP16 PV on fp16 inputs: V rows in place, no tile image (sage_attn_fused_q_pv_f16_vrows)
         assert v_scale is None and v_mean is None
         _, _, _, _, v_sb, v_sh, v_sl = _dims(v_image, tensor_layout)
@@ -379,6 +381,58 @@ def _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran: str, pv_accum_dtype:
     return True
 
 
+def _q_start_args(q_start, causal_align: str, is_causal: bool, q, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs) -> bool:
+    """Whether ``q_start`` / ``causal_align`` ask for per-sample query offsets; their argument errors (checked before any work, on any
+    device).  The offsets ride on the ``kv_lens`` route, so its restrictions hold (:func:`_kv_lens_args`), worded for these keywords."""
+    if causal_align not in ("top_left", "bottom_right"):
+        raise ValueError(f"causal_align must be 'top_left' or 'bottom_right' (got {causal_align!r})")
+    if q_start is None and causal_align == "top_left":
+        return False
+    what = "q_start" if q_start is not None else "causal_align='bottom_right'"
+    if q_start is not None and causal_align != "top_left":
+        raise ValueError("pass either q_start or causal_align='bottom_right' (which is q_start = clamp(kv_lens, 0, kv_len) - qo_len), not both")
+    if not is_causal:
+        raise ValueError(f"{what} needs is_causal=True (it places the causal diagonal)")
+    B = q.shape[0]
+    if q_start is not None and not (isinstance(q_start, int) and not isinstance(q_start, bool)):
+        if not isinstance(q_start, torch.Tensor) or q_start.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"q_start must be an int or an int32 / int64 tensor (got {getattr(q_start, 'dtype', type(q_start).__name__)})")
+        if q_start.dim() != 1 or q_start.shape[0] != B:
+            raise ValueError(f"q_start must have shape [B] = [{B}] (got {tuple(q_start.shape)})")
+        if q_start.device != q.device:
+            raise ValueError(f"q_start must be on q's device {q.device} (got {q_start.device})")
+    if qk_quant_gran != "per_thread":
+        raise ValueError(f"{what} needs qk_quant_gran='per_thread' (got {qk_quant_gran!r})")
+    if not kwargs.get("fuse_q_quant", True):
+        raise ValueError(f"{what} needs the fused Q quantiser (fuse_q_quant=False given)")
+    if pv_accum_dtype == "fp32":
+        raise ValueError(f"{what} needs pv_accum_dtype 'fp32+fp32' or 'fp32+fp16' (two-level accumulation)")
+    if ops.fp8_folded(kwargs.get("fp8_scores")):
+        raise ValueError(f"{what} takes the exact score form only (fp8_scores='folded' given)")
+    if smooth_v:
+        raise ValueError(f"{what} does not support smooth_v=True")
+    split = kwargs.get("split_kv")
+    if split is not None and not (split == 0 and not isinstance(split, bool)):
+        raise ValueError(f"{what} cannot be combined with split_kv={split!r} (None or 0 only)")
+    if kwargs.get("split_kv_exact", False):
+        raise ValueError(f"{what} cannot be combined with split_kv_exact=True")
+    return True
+
+
+def _q_start_tensor(q_start, kv_lens, B: int, Lq: int, Lk: int, device) -> torch.Tensor:
+    """The int32 ``[B]`` offsets of the attention call, formed on the device (no host read): the caller's tensor, an int broadcast to the
+    batch, or -- ``q_start`` None: ``causal_align='bottom_right'`` -- ``clamp(kv_lens, 0, Lk) - Lq``."""
+    if q_start is None:
+        if kv_lens is None:
+            return torch.full((B,), Lk - Lq, dtype=torch.int32, device=device)
+        return (kv_lens.clamp(0, Lk) - Lq).to(torch.int32).contiguous()
+    if isinstance(q_start, int):
+        return torch.full((B,), max(-2 ** 31, min(2 ** 31 - 1, q_start)), dtype=torch.int32, device=device)
+    if q_start.dtype == torch.int64:       # (offsets outside int32 are far outside [-Lq, Lk] either way: clamp before narrowing)
+        q_start = q_start.clamp(-2 ** 31, 2 ** 31 - 1)
+    return q_start.to(torch.int32).contiguous()
+
+
 @torch.compiler.disable
 def _attn_fused_q_split_exact(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, sm_scale_log2, S, return_lse, v_mean=None):
     """Exact split-KV route of the fused-Q FP8 attention: pass 1 (``sage_split_exact_chunk_max``) computes every chunk's row maxima with
@@ -453,17 +507,21 @@ def _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
 
 # ------------------------------------------------------------------------------------------------
 def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND", is_causal: bool = False,
-             sm_scale: Optional[float] = None, return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, **kwargs: Any):
+             sm_scale: Optional[float] = None, return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, q_start=None,
+             causal_align: str = "top_left", **kwargs: Any):
     """Select the implementation for the device, as the reference does per compute capability
     (core.py:143-157).  On gfx950 that is INT8 QK^T + FP8 PV with two-level FP32 accumulation
     (the reference's sm90 choice, ``pv_accum_dtype="fp32+fp32"``).  Extra SDPA-style kwargs
     (``attn_mask=``, ``dropout_p=``, ``scale=`` ...) are accepted and ignored exactly as the
     reference ignores them.  ``kv_lens`` (gfx950 extension, int32 / int64 ``[B]`` on q's device): a key length per sample of a right-padded
-    batch, see :func:`sageattn_qk_int8_pv_fp8_cuda`."""
+    batch; ``q_start`` (int, or int32 / int64 ``[B]``) / ``causal_align="bottom_right"``: where the causal diagonal of each sample lies -- row i
+    attends to key j iff ``j <= q_start[b] + i`` and ``j < len_b``.  See :func:`sageattn_qk_int8_pv_fp8_cuda`."""
     _check_shapes(q, k, v, tensor_layout)      # (again in the entry point called below: this one is in front of the device query)
     if torch.compiler.is_compiling():      # the device query is not traceable; the opaque op checks the device when it runs
         if kv_lens is not None:            # (the compiled op has no such argument: a compiled call that ignored the lengths would be a trap)
             raise ValueError("kv_lens is not supported under torch.compile")
+        if q_start is not None or causal_align != "top_left":
+            raise ValueError("q_start / causal_align are not supported under torch.compile")
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32")
     arch = get_gcn_arch(q.device) if q.is_cuda else "cpu"
@@ -471,7 +529,8 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32", split_kv=kwargs.get("split_kv"),
                                             fused_prepass=kwargs.get("fused_prepass"), fp8_scores=kwargs.get("fp8_scores"),
-                                            split_kv_exact=kwargs.get("split_kv_exact", False), kv_lens=kv_lens)
+                                            split_kv_exact=kwargs.get("split_kv_exact", False), kv_lens=kv_lens,
+                                            q_start=q_start, causal_align=causal_align)
     raise ValueError(f"Unsupported architecture: {arch} (sageattention_amd targets gfx950 / MI355X only)")
 
 
@@ -863,7 +922,8 @@ def sageattn_qk_int8_pv_fp16_cuda(q, k, v, tensor_layout: str = "HND", is_causal
 def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal: bool = False,
                                  qk_quant_gran: str = "per_thread", sm_scale: Optional[float] = None,
                                  pv_accum_dtype: str = "fp32+fp16", smooth_k: bool = True, smooth_v: bool = False,
-                                 return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, **kwargs: Any):
+                                 return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, q_start=None,
+                                 causal_align: str = "top_left", **kwargs: Any):
     """INT8 QK^T + FP8 (e4m3) PV (reference core.py:636-826).  "fp32+fp32" and "fp32+fp16" both
     run the two-level kernel with an FP32 tile buffer (gfx950's FP8 MFMA only writes FP32, so V
     keeps the full ``scale_max=448``; the reference's 2.25 is an FP16-accumulator artefact,
@@ -882,13 +942,33 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     uninitialised).  The lengths are clamped to ``[0, kv_len]`` on the device and never read by the host, so the call can be captured in a
     HIP graph and replayed with other lengths in the same tensor; ``kv_lens[b] == 0`` gives ``o[b] = 0`` and ``lse[b] = -inf``.  The default
     path only: per-thread granularity with the fused Q quantiser, two-level accumulation, the exact score form, no ``smooth_v``, no
-    split-KV, not under torch.compile; anything else raises ValueError."""
+    split-KV, not under torch.compile; anything else raises ValueError.
+
+    ``q_start`` / ``causal_align`` (gfx950 extension, ``is_causal=True`` only): where the causal diagonal of each sample lies.  ``q_start[b]``
+    -- an int32 / int64 tensor ``[B]`` on q's device, or a Python int for the whole batch -- is the position of query row 0 of sample b on
+    the key axis: row i attends to key j iff ``j <= q_start[b] + i`` and ``j < len_b``, ``len_b = clamp(kv_lens[b], 0, kv_len)`` (``kv_len``
+    without ``kv_lens``).  ``q_start == 0`` is the top-left mask above; ``q_start[b] = len_b - qo_len`` is the bottom-right one (torch's
+    ``causal_lower_right``, FlashAttention >= 2.1), what a caller who continues a sequence needs -- chunked prefill, speculative-decode
+    verification, a prompt continued against a cached prefix: ``qo_len`` new rows against ``len_b`` cached-plus-new keys.
+    ``causal_align="bottom_right"`` is that choice spelled out: ``clamp(kv_lens, 0, kv_len) - qo_len`` formed on the device, the constant
+    ``kv_len - qo_len`` without ``kv_lens``; giving both keywords raises ValueError.  The offsets are clamped to ``[-qo_len, kv_len]`` on the
+    device and never read by the host: no synchronisation, grids and allocations follow from the shapes, the call captures into a HIP graph
+    and a replay computes with what ``q_start`` / ``kv_lens`` hold then.  A row with ``q_start[b] + i < 0``, and every row of a sample with
+    ``len_b == 0``, sees nothing: ``o = +0``, ``lse = -inf``, never NaN.  Key rows from ``len_b`` on are never read.  Offsets that are
+    multiples of 64 keep the pipelined diagonal tiles; any other offset runs the diagonal of each 128-row query block as three general
+    tiles -- correct, slower.  The route is ``kv_lens``'s (without ``kv_lens`` the attention entry gets lengths filled with
+    ``kv_len`` and the plain pre-pass runs, the one-launch route included), so its restrictions hold and raise ValueError: per-thread
+    granularity with the fused Q quantiser, two-level accumulation, the exact score form, no ``smooth_v``, no split-KV (a decode-shaped
+    call of ``qo_len <= 128`` therefore launches ``B * Hq`` workgroups), not under torch.compile."""
     if torch.compiler.is_compiling():
         if kv_lens is not None:
             raise ValueError("kv_lens is not supported under torch.compile (the compiled op takes the default routes)")
+        if q_start is not None or causal_align != "top_left":
+            raise ValueError("q_start / causal_align are not supported under torch.compile (the compiled op takes the default routes)")
         return _compiled_call("fp8", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse, kwargs)
     _check_shapes(q, k, v, tensor_layout)
     with_lens = _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
+    with_start = _q_start_args(q_start, causal_align, is_causal, q, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     exact = _split_exact_args(kwargs, qk_quant_gran, pv_accum_dtype, _dims(k, tensor_layout)[2])
     dtype = q.dtype
     _check_inputs(q, k, v)
@@ -910,10 +990,24 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
         # per-sample key lengths: the length-aware kernel sequence (mean -> K quantiser -> V statistics -> V image), then the KVLEN kernels;
         # nothing here reads the lengths on the host (int64 is converted on the device)
         lens = kv_lens.to(torch.int32).contiguous()
+        B_, _, Lq_ = _dims(q, tensor_layout)[:3]
+        start = _q_start_tensor(q_start, kv_lens, B_, Lq_, _dims(k, tensor_layout)[2], q.device) if with_start else None
         lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
                                                                               return_lse, False, kv_lens=lens)
         o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens)
+                               kv_lens=lens, q_start=start)
+        return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
+    if with_start:
+        # query offsets without key lengths: the plain pre-pass (the one-launch route included) and the same attention entry with lengths
+        # filled with kv_len -- full lengths give the plain call's bits
+        B_, _, Lq_ = _dims(q, tensor_layout)[:3]
+        Lk_ = _dims(k, tensor_layout)[2]
+        start = _q_start_tensor(q_start, None, B_, Lq_, Lk_, q.device)
+        lens = torch.full((B_,), Lk_, dtype=torch.int32, device=q.device)
+        lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
+                                                                              return_lse, fused)
+        o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
+                               kv_lens=lens, q_start=start)
         return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
     if fuse_q:
         # default route: Q is quantised inside the attention kernel (same bits, no INT8 copy of Q in HBM).

@@ -172,8 +172,17 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // (l = 0: the normalisation factor is 0, and the product is forced to zero so that a NaN in the sample's unused scale slots cannot reach it)
 // and lse = log2(0) + m = -inf.  (An exit of its own in front of the Q fragments -- a second way out of the item loop -- cost the D = 64
 // non-causal instantiations 5-8 spilled VGPRs under their three-waves limit wherever it was placed.)
+// (QSTART stands in front of KVLEN in the parameter list, which therefore still ends with the KVLEN flag.)
+// QSTART (a CAUSAL KVLEN kernel, units sage_attn_d{128,64}_f8q.hip): query row 0 of sample b stands at key position s_b = p.cu_qs[b] clamped to
+// [-p.Lq, p.Lk] (cu_qs is as free in a dense launch as cu_k), so row i attends to key j iff j <= s_b + i and j < len_b: s_b = 0 is the top-left
+// mask, s_b = len_b - Lq the bottom-right one.  It is the split routes' shift of the causal mask into a chunk's key coordinates with
+// kchunk0 = -s_b; loop bounds, the steady tiles and every mask follow from that value.  An offset that is a multiple of 64 keeps the pipelined
+// last-tile bodies on the diagonal; any other puts the diagonal of a query block across three tiles, which run as general iterations
+// (correct, slower).  A row with s_b + i < 0 sees nothing: every score of it is masked in every tile its wave runs, its maximum stays at
+// kNegBig and its l at 0, and the epilogue gives it o = +0, lse = -inf as it does for a chunk of the inexact causal split that lies wholly
+// behind a row's diagonal.
 template <int D, bool PV_FP8, bool CAUSAL, bool KTHREAD, bool TWO_LEVEL, int NH, int MASK = 0, int QF = 0, bool SFOLD = true, bool CPERS = false,
-          bool VROWS = false, bool SEED = false, bool KVLEN = false>
+          bool VROWS = false, bool SEED = false, bool QSTART = false, bool KVLEN = false>
 __global__ void __launch_bounds__(256, SAGE_MIN_WAVES(D, MASK))
 sage_attn_kernel(const AttnParams p_arg)
 {
@@ -203,6 +212,7 @@ sage_attn_kernel(const AttnParams p_arg)
                   "the seeded split: FP8 PV, fused per-thread Q, exact score form, dense");
     static_assert(!KVLEN || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS && !SEED),
                   "per-sample key lengths: FP8 PV, fused per-thread Q, exact score form, dense");
+    static_assert(!QSTART || (KVLEN && CAUSAL), "per-sample query offsets: the causal kv_lens kernels");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     // (wave index in an SGPR, lane index from v_mbcnt wherever it is needed: nothing derived from threadIdx.x has to stay in a VGPR across
@@ -357,6 +367,7 @@ sage_attn_kernel(const AttnParams p_arg)
 
     // ---- per-sequence geometry ---------------------------------------------------------------
     int Lq = p.Lq, Lk = p.Lk;
+    [[maybe_unused]] int qstart = 0;      // (QSTART) the position of the sample's query row 0 on the key axis
     long q_off, k_off, o_off;
     long v_tile0, v_tstride;              // V image index = v_tile0 + t * v_tstride
     const float *qs_ptr, *ks_ptr;
@@ -401,6 +412,10 @@ sage_attn_kernel(const AttnParams p_arg)
             typedef const __attribute__((address_space(4))) int *cint_p;
             const int len = ((cint_p)p.cu_k)[__builtin_amdgcn_readfirstlane(b)];
             Lk = len < 0 ? 0 : (len < p.Lk ? len : p.Lk);
+            if constexpr (QSTART) {        // the sample's query offset, requested with the length: p.cu_qs is as free in a dense launch as p.cu_k
+                const int s = ((cint_p)p.cu_qs)[__builtin_amdgcn_readfirstlane(b)];
+                qstart = s < -p.Lq ? -p.Lq : (s < p.Lk ? s : p.Lk);
+            }
         }
         q_off = (long)b * p.q_sb + (long)hq * p.q_sh;
         k_off = (long)b * p.k_sb + (long)hk * p.k_sh;
@@ -419,7 +434,10 @@ sage_attn_kernel(const AttnParams p_arg)
     int my_row = row0 + n;                           // (re-derived behind the pipelined loops, see there)
     // causal mask in the chunk's key coordinates (split-KV: this workgroup sees keys kchunk0 .. kchunk0 + Lk - 1 as 0 .. Lk - 1):
     // key <= row  <=>  local key <= row - kchunk0
-    const int kchunk0 = SEED ? (CAUSAL ? p.kv_base + (hk % p.kv_split) * Lk : 0)
+    // (QSTART: row i sees key <= i + qstart -- the same shift with kchunk0 = -qstart, in [-p.Lk, p.Lq].  Every bound below is formed from
+    //  it in signed arithmetic: a division that truncates a negative numerator towards zero yields a value the following clamp to 0 replaces)
+    const int kchunk0 = QSTART ? -qstart
+                      : SEED ? (CAUSAL ? p.kv_base + (hk % p.kv_split) * Lk : 0)
                              : ((CAUSAL && p.kv_split > 1 && p.cu_q == nullptr) ? (hk % p.kv_split) * Lk : 0);
     const int crow0 = row0 - kchunk0;
     int cmy_row = my_row - kchunk0;
@@ -971,7 +989,11 @@ sage_attn_kernel(const AttnParams p_arg)
         // (FP16 PV: only behind at least one steady tile -- its first body is a form of its own -- and at D = 128: the D = 64 instantiations spill
         //  5-10 VGPRs under their three-waves limit with the two extra bodies)
         constexpr bool DIAG_PIPE = CAUSAL && SAGE_DIAG_PIPE && (PV_FP8 || D == 128);
-        const bool diag_ok = DIAG_PIPE && (n_steady > 0 ? n_iters - n_steady == 2 : (PV_FP8 && n_iters == 2 && Lk >= 2 * KT));
+        // (QSTART: with an offset that is no multiple of 64 the diagonal crosses three tiles of a query block and rows in front of key 0 see
+        //  nothing at all -- which the last-tile bodies, whose masked scores still set a row maximum, do not provide for: general iterations.
+        //  With a multiple of 64 every row of a block that runs these bodies sees key 0: they need n_iters >= 2, i.e. 128 qblk + 128 - kchunk0 > 64,
+        //  so crow0 of wave 0 is > -64, hence >= 0; the one negative case, crow0 = -64, has lim = 1 and runs no pipelined body)
+        const bool diag_ok = DIAG_PIPE && (!QSTART || (kchunk0 & (KT - 1)) == 0) && (n_steady > 0 ? n_iters - n_steady == 2 : (PV_FP8 && n_iters == 2 && Lk >= 2 * KT));
         // TAIL_PIPE (non-causal FP8 PV): the two whole tiles the steady loop leaves (it looks two tiles ahead) and a ragged last one behind them take the
         // pipelined body as well -- keys past Lk masked like keys behind the diagonal, the ragged tile requested in the general (clamped) form
         // (FP16 PV, D = 128: the two whole tiles of a call whose Lk is a multiple of 64, behind at least one steady tile -- kinds 1 and 2 as they are)

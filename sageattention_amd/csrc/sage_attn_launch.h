@@ -179,9 +179,22 @@ hipError_t launch_attn_f8_kvlens(const AttnParams &p, const AttnVariant &v, int 
 {
     using C = TileCfg<D, true, 1>;
 #define SAGE_F8K(C_, F_) if (v.causal == C_ && v.qf == F_) \
-    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, !C_);
+    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, !C_);
     SAGE_F8K(false, 1) SAGE_F8K(false, 2) SAGE_F8K(true, 1) SAGE_F8K(true, 2)
 #undef SAGE_F8K
+    return hipErrorInvalidValue;
+}
+
+// Per-sample query offsets on top of the key lengths (sage_attn_kernel's QSTART): the causal kv_lens kernels with p.cu_qs = the [B] offsets:
+// the units sage_attn_d{128,64}_f8q.hip.  The hardware's dispatch over the work order planned for the padded shapes, as every dense causal launch.
+template <int D>
+hipError_t launch_attn_f8_qstart(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
+{
+    using C = TileCfg<D, true, 1>;
+#define SAGE_F8Q(F_) if (v.causal && v.qf == F_) \
+    return launch_kernel<sage_attn_kernel<D, true, true, true, true, 1, 0, F_, false, false, false, false, true, true>>(C::LDS_BYTES, p, nwork, l, false);
+    SAGE_F8Q(1) SAGE_F8Q(2)
+#undef SAGE_F8Q
     return hipErrorInvalidValue;
 }
 

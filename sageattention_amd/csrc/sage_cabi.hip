@@ -6,6 +6,7 @@
 #include "sage_work_order.h"
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,13 +47,14 @@ inline bool multiples_of(int n, const Strides &s) { return multiples_of(n, s.sb,
 struct MaskArg { const void *ptr; int kind; int64_t sb, sh, sq, sk; };
 
 // SageLaunchAttr (nullable) -> the launch workspace and the launcher's options; the attributes are arguments of THIS call, nothing is kept
-struct LaunchAttr { unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; };
+struct LaunchAttr { unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; const int32_t *q_start; };
 int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAttr &out)
 {
     out.ws = nullptr;
     out.opts = sage::AttnLaunchOpts{static_cast<hipStream_t>(stream), false, false, nullptr};
     out.trace = nullptr;
     out.trace_wgs = 0;
+    out.q_start = nullptr;
     if (attr == nullptr) return SAGE_OK;
     SageLaunchAttr a{};
     // struct_bytes is what the CALLER's struct holds: fewer bytes than ours (an older caller) are read as far as they go, more (a newer
@@ -60,6 +62,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     SAGE_REQUIRE(attr->struct_bytes >= 8, "SageLaunchAttr.struct_bytes = %u: set it to sizeof(SageLaunchAttr) (at least the 8-byte header)", attr->struct_bytes);
     const size_t n = attr->struct_bytes > sizeof(SageLaunchAttr) ? sizeof(SageLaunchAttr) : attr->struct_bytes;
     memcpy(&a, attr, n);
+    if (n < offsetof(SageLaunchAttr, q_start) + sizeof(a.q_start)) a.q_start = nullptr;      // (a struct that ends inside the field does not have it)
     SAGE_REQUIRE((a.flags & ~(SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES | SAGE_ATTR_FORCE_PERSISTENT)) == 0, "unknown SageLaunchAttr.flags 0x%x", a.flags);
     SAGE_REQUIRE((a.flags & (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES)) != (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES),
                  "SageLaunchAttr.flags asks for both FP8 score forms");
@@ -73,6 +76,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     out.opts.grid_out = a.grid_out;
     out.trace = a.trace;
     out.trace_wgs = a.trace != nullptr ? a.trace_wgs : 0;
+    out.q_start = a.q_start;
     return SAGE_OK;
 }
 
@@ -95,7 +99,9 @@ struct AttnCall {
     const int32_t *cu_q, *cu_k, *cu_qs, *cu_ks, *seq_order, *work_items, *work_hdr;
     int items_bound;
     int64_t lse_sh;                  // varlen lse [Hq, sum Lq]: its head stride
-    const int32_t *kv_lens;          // per-sample key lengths [B] of a dense, right-padded batch
+    const int32_t *kv_lens;          // per-sample key lengths [B] of a dense, right-padded batch.  Also the mark of the ONE entry point
+                                     // (sage_attn_fused_q_pv_f8_kvlens) that takes per-sample query offsets: those arrive in the attributes
+                                     // (SageLaunchAttr::q_start, read by attn_run), so they have no field here
     int kv_split;                    // > 1: the (inexact) split, the chunks folded into Hq / Hkv by the entry point
     int is_causal, gran, q_warp, pv_accum, q_dtype, out_dtype;
     float sm_scale_log2, q_premul;
@@ -164,6 +170,9 @@ int attn_run(const AttnCall &c)
     if (const int rc = read_attr(c.attr, c.stream, c.mask == nullptr && !split, la)) return rc;     // (masked and split launches take no launch workspace)
     // ---- the routes a Q form admits
     SAGE_REQUIRE(!(fp8 && varlen && la.opts.fp8_folded), "packed (varlen) FP8 attention has the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES)");
+    // (per-sample query offsets travel in the attributes; kv_lens marks the one entry point that takes them)
+    SAGE_REQUIRE(la.q_start == nullptr || (c.kv_lens != nullptr && c.is_causal && !la.opts.fp8_folded),
+                 "SageLaunchAttr.q_start: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
     SAGE_REQUIRE(c.kv_lens == nullptr || (per_thread && fp8 && !split && c.v_rows == nullptr && !la.opts.fp8_folded),
                  "kv_lens: FP8 PV, the exact score form (SAGE_ATTR_FP8_FOLDED_SCORES), no split");
     SAGE_REQUIRE(!(per_block && varlen) || c.cu_q != nullptr, "varlen needs cu_seqlens_q");
@@ -215,6 +224,7 @@ int attn_run(const AttnCall &c)
     p.sched = la.ws; p.trace = la.trace; p.trace_wgs = la.trace_wgs;
     if (c.mask != nullptr) { p.mask = c.mask->ptr; p.m_sb = c.mask->sb; p.m_sh = c.mask->sh; p.m_sq = c.mask->sq; p.m_sk = c.mask->sk; v.mask_kind = c.mask->kind; }
     if (c.kv_lens != nullptr) { p.cu_k = c.kv_lens; v.kv_lens = true; }
+    if (la.q_start != nullptr) { p.cu_qs = la.q_start; v.q_start = true; }
     v.head_dim = c.D; v.pv_fp8 = fp8; v.causal = c.is_causal != 0;
     // FP16 PV: the kernel's TWO_LEVEL parameter selects the Triton kernel form (true) or the CUDA kernel form (false)
     v.two_level = fp8 ? c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : c.pv_accum == SAGE_PV_ACCUM_TRITON;
@@ -1111,6 +1121,7 @@ SAGE_API int sage_attn_fused_q_pv_f8_split_exact(const void *q, const int8_t *k,
     LaunchAttr la;
     if (const int rc = read_attr(attr, stream, false, la)) return rc;
     SAGE_REQUIRE(!la.opts.fp8_folded, "the exact split takes the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES given)");
+    SAGE_REQUIRE(la.q_start == nullptr, "SageLaunchAttr.q_start: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
     if (const int rc = split_exact_check(q, k, k_scale, B, Hq, Hkv, kv_split, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, q_dtype)) return rc;
     SAGE_REQUIRE(v_image && v_scale && o_part && lse_part && chunk_max, "null tensor pointer");
     SAGE_REQUIRE(tail == 0 || tail == 1, "tail must be 0 (the whole chunks) or 1 (the ragged tail), got %d", tail);

@@ -27,7 +27,7 @@ struct AttnParams {
     long m_sb, m_sh, m_sq, m_sk;
     const int32_t *cu_q;      // varlen only (null => dense)
     const int32_t *cu_k;      // (AttnVariant::kv_lens: the per-sample key lengths [B] instead, clamped to [0, Lk] by the kernel)
-    const int32_t *cu_qs;     // prefix sums of ceil(Lq_i/128)
+    const int32_t *cu_qs;     // prefix sums of ceil(Lq_i/128)  (dense AttnVariant::q_start: the per-sample query offsets [B] instead)
     const int32_t *cu_ks;     // prefix sums of ceil(Lk_i/64)
     const int32_t *seq_order; // varlen, nullable: permutation of sequence indices in processing order (legacy unit order, no work list)
     const int32_t *work_items;// varlen, nullable: the device-built work list of sage_varlen_plan ((sequence, query block), heaviest first)
@@ -70,7 +70,7 @@ struct AttnLaunchOpts {
     bool force_persistent;   // take the ticket queues whatever the number of rounds (tests; AttnParams::sched must be set)
     int *grid_out;           // nullable (host): receives the number of workgroups launched
 };
-// Which member of the kernel family a launch takes: the instantiation unit (head_dim, pv_fp8, AttnLaunchOpts::fp8_folded, seeded, kv_lens; the
+// Which member of the kernel family a launch takes: the instantiation unit (head_dim, pv_fp8, AttnLaunchOpts::fp8_folded, seeded, kv_lens, q_start; the
 // per-block fused Q quantiser with FP8 PV has units of its own) and everything else the template arguments of sage_attn_kernel encode.
 //   INT8 q (qf 0)            every field below; a mask: FP16 PV, per-block scales, non-causal, the Triton kernel form
 //   fused per-thread Q (1/2) dense; kthread, two_level = pv_fp8 (FP16 PV: straight FP32 accumulation)
@@ -90,6 +90,8 @@ struct AttnVariant {
     bool kv_lens;       // per-sample key lengths (same kernels otherwise, dense): AttnParams::cu_k = int32 lengths [B] in device memory, sample b
                         // attends to keys 0 .. clamp(cu_k[b], 0, p.Lk) - 1 of the padded tensors; k / its scales / the V image from
                         // sage_quant_qk_int8_kvlens / sage_prep_v_fp8_kvlens
+    bool q_start;       // per-sample query offsets (kv_lens and causal): AttnParams::cu_qs = int32 offsets [B] in device memory, row i of sample b
+                        // attends to key j iff j <= clamp(cu_qs[b], -p.Lq, p.Lk) + i and j < its length
 };
 constexpr int attn_qf(bool per_block, int q_dtype) { return (per_block ? 3 : 1) + (q_dtype == 0 ? 0 : 1); }   // q_dtype: DT_F16 (0) / DT_BF16
 // the one attention launcher: plans the work order, checks that the route exists (hipErrorInvalidValue) and launches the variant's kernel.
