@@ -35,7 +35,8 @@ extern "C" {
 /* Changes (newest first):
  *   22  FP8 PV for packed (varlen) batches: sage_prep_v_fp8_varlen (+ _ws_floats), sage_attn_qk_int8_pv_f8_varlen,
  *       sage_attn_fused_qblock_pv_f8_varlen.  Nothing else changed.
- *       (added since, no existing entry changed: the exact split-KV entries; the per-sample key lengths entries sage_*_kvlens)
+ *       (added since, no existing entry changed: the exact split-KV entries; the per-sample key lengths entries sage_*_kvlens;
+ *        SageLaunchAttr.q_start appended; SageLaunchAttr.window -- the struct's former `reserved` word at offset 44, 0 = what every caller passed)
  *   21  sage_attn_qk_int8_pv_f16_vrows (INT8 q / k, V read in place).
  *   20  the exact FP8 score form is the default; SageLaunchAttr.struct_bytes = 0 is refused; launch workspaces re-arm themselves;
  *       sage_attn_fused_q*_pv_f16_vrows. */
@@ -326,6 +327,18 @@ SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale
  *                   diagonal tiles; any other offset runs the diagonal of a query block as three general tiles (correct, slower).  Every
  *                   other sage_attn_* entry point, and that one with is_causal = 0 or SAGE_ATTR_FP8_FOLDED_SCORES, refuses a non-null
  *                   q_start (SAGE_EINVAL).  The reference has no counterpart (its causal mask is top-left, qk_int_sv_f8_cuda_sm89.cuh:237-241).
+ *  window           the struct's former `reserved` word (offset 44, in front of q_start), given its meaning under ABI 22: the number of keys a row
+ *                   sees up to and including its diagonal (Python: window_size=; a sliding window of left + 1 keys).  0 = unbounded -- what every
+ *                   existing caller passes and what a struct_bytes that ends before the field reads as; a negative value is SAGE_EINVAL.
+ *                   Honoured by sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 alone: row i of sample b attends to key j iff
+ *                   q_start[b] + i - window < j <= q_start[b] + i and 0 <= j < len_b (q_start may be null there: offsets 0).  A host int, the
+ *                   same for every sample: a constant of a captured graph.  The kernel clamps it to [1, 2^30] and the offsets to
+ *                   [-Lq, Lk + window] (a clamp to Lk would move the left edge of an offset that lies beyond the keys); Lq + Lk <= 2^29.  A
+ *                   work item starts at the 64-key tile of the first key its rows see: key rows, k scales and V images in front of it are
+ *                   never read, as those from len_b on are not.  A row whose window holds no key -- in front of key 0, or wholly behind
+ *                   len_b -- gives o = +0, lse = -inf, never NaN.  A window that cuts no row (window >= Lk + Lq) gives the bits of the call
+ *                   without it.  Every other sage_attn_* entry point, and that one with is_causal = 0 or SAGE_ATTR_FP8_FOLDED_SCORES, refuses
+ *                   a non-zero window (SAGE_EINVAL).  The reference has no counterpart.
  */
 typedef struct SageLaunchAttr {
     uint32_t struct_bytes;
@@ -335,7 +348,7 @@ typedef struct SageLaunchAttr {
     int32_t *grid_out;
     uint32_t *trace;
     int32_t trace_wgs;
-    int32_t reserved;
+    int32_t window;
     const int32_t *q_start;
 } SageLaunchAttr;
 /* The softmax argument of a score is fma(s, c, -m) with s the INT32 dot product, c the dequantisation scale in the log2 domain and m the

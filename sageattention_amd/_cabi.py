@@ -28,17 +28,18 @@ ATTR_FP8_EXACT_SCORES, ATTR_FORCE_PERSISTENT, ATTR_FP8_FOLDED_SCORES = 1, 2, 4
 class SageLaunchAttr(ctypes.Structure):
     """``SageLaunchAttr`` of include/sage_gfx950.h: the launch attributes an attention entry point takes as its last argument."""
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("launch_ws", c_void_p), ("launch_ws_bytes", c_int64),
-                ("grid_out", c_void_p), ("trace", c_void_p), ("trace_wgs", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("grid_out", c_void_p), ("trace", c_void_p), ("trace_wgs", ctypes.c_int32), ("window", ctypes.c_int32),
                 ("q_start", c_void_p)]
 
 
 def launch_attr(launch_ws=None, folded_scores: bool = False, force_persistent: bool = False, grid_out=None, trace=None, trace_wgs: int = 0,
-                q_start=None):
+                q_start=None, window: int = 0):
     """A ``SageLaunchAttr`` (or None when every field is at its default).  ``launch_ws``: a zeroed int32 CUDA tensor of
     ``sage_attn_launch_ws_bytes()`` bytes; the caller keeps it (and the returned struct) alive until the C call has returned.
     ``grid_out``: a ``ctypes.c_int32`` that receives the number of workgroups launched.  ``q_start``: an int32 CUDA tensor ``[B]``, the
-    per-sample query offsets of a causal ``sage_attn_fused_q_pv_f8_kvlens`` call."""
-    if launch_ws is None and not folded_scores and grid_out is None and trace is None and q_start is None:
+    per-sample query offsets of a causal ``sage_attn_fused_q_pv_f8_kvlens`` call; ``window``: the number of keys a row of such a call sees up
+    to and including its diagonal (0: unbounded)."""
+    if launch_ws is None and not folded_scores and grid_out is None and trace is None and q_start is None and not window:
         return None
     a = SageLaunchAttr()
     a.struct_bytes = ctypes.sizeof(SageLaunchAttr)
@@ -53,6 +54,7 @@ def launch_attr(launch_ws=None, folded_scores: bool = False, force_persistent: b
         a.trace_wgs = int(trace_wgs)
     if q_start is not None:
         a.q_start = q_start.data_ptr()
+    a.window = int(window)
     a._keep = (launch_ws, grid_out, trace, q_start)      # (the struct holds raw addresses)
     return a
 

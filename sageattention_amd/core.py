@@ -151,12 +151,13 @@ def _v_rows_wanted(q, k, v, tensor_layout: str, is_causal: bool, override) -> bo
 
 @torch.compiler.disable
 def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, sm_scale_log2, return_lse, v_mean=None, folded_scores=False,
-                  v_rows=False, kv_lens=None, q_start=None):
+                  v_rows=False, kv_lens=None, q_start=None, window=0):
     """FP8-PV two-level attention with the per-thread Q quantisation done in the kernel prologue
     (``sage_attn_fused_q_pv_f8``): bit-identical to ``per_thread_int8`` + the attention op, one launch and
     3 B/element of HBM traffic less.  ``v_rows`` (FP16 PV): ``v_image`` is the fp16 V tensor itself, read in place.
     ``kv_lens`` (FP8 PV, int32 [B] on the device): a key length per sample (``sage_attn_fused_q_pv_f8_kvlens``); ``q_start`` (with
-    ``kv_lens``, causal; int32 [B] on the device): a query offset per sample (``SageLaunchAttr.q_start``)."""
+    ``kv_lens``, causal; int32 [B] on the device): a query offset per sample (``SageLaunchAttr.q_start``); ``window`` (with ``kv_lens``,
+    causal; a Python int): the number of keys a row sees up to and including its diagonal, 0 = unbounded (``SageLaunchAttr.window``)."""
     B, Hq, Lq, D, q_sb, q_sh, q_sl = _dims(q, tensor_layout)
     _, Hkv, Lk, _, k_sb, k_sh, k_sl = _dims(k_int8, tensor_layout)
     assert Hq % Hkv == 0, "num_qo_heads must be divisible by num_kv_heads"
@@ -165,8 +166,8 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
     lse = torch.empty((B, Hq, Lq), dtype=torch.float32, device=q.device) if return_lse else None
     code = _cabi.DTYPE_F16 if q.dtype == torch.float16 else _cabi.DTYPE_BF16
     # (a large non-causal call: persistent launch; FP8 PV: the score form)
-    assert q_start is None or (kv_lens is not None and is_causal)
-    attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None, q_start=q_start)
+    assert (q_start is None and not window) or (kv_lens is not None and is_causal)
+    attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None, q_start=q_start, window=window)
     if v_rows:                     # FP16 PV on fp16 inputs: V rows in place, no tile image (sage_attn_fused_q_pv_f16_vrows)
         assert v_scale is None and v_mean is None
         _, _, _, _, v_sb, v_sh, v_sl = _dims(v_image, tensor_layout)
@@ -381,6 +382,49 @@ def _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran: str, pv_accum_dtype:
     return True
 
 
+def _window_args(window_size, is_causal: bool, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs):
+    """``window_size=(left, right)`` (FlashAttention's convention, -1 = unbounded on that side) as ``(W, r)``: a row sees ``W`` keys up to and
+    including its diagonal (0: unbounded), the diagonal shifted right by ``r`` keys; None when there is no window.  Its argument errors are
+    checked before any work, on any device.  A window rides on the ``q_start`` route, so that route's restrictions hold, worded for this
+    keyword.  With ``is_causal=False`` and ``right >= 0`` the call runs the causal kernels with the diagonal ``right`` keys further right."""
+    if window_size is None:
+        return None
+    ok_int = lambda x: isinstance(x, int) and not isinstance(x, bool)
+    if not isinstance(window_size, (tuple, list)) or len(window_size) != 2 or not all(ok_int(x) for x in window_size):
+        raise ValueError(f"window_size must be a pair of ints (left, right), -1 = unbounded on that side (got {window_size!r})")
+    left, right = window_size
+    if left < -1 or right < -1:
+        raise ValueError(f"window_size=({left}, {right}): a side is -1 (unbounded) or a number of keys >= 0")
+    if is_causal and right not in (0, -1):
+        raise ValueError(f"window_size=({left}, {right}) with is_causal=True: right must be 0 or -1 (a causal row sees no key behind its diagonal)")
+    if left == -1 and (is_causal or right == -1):
+        return None                        # unbounded: the call without the keyword
+    if not is_causal and right == -1:
+        raise ValueError(f"window_size=({left}, -1) with is_causal=False: a bounded look-back needs right >= 0 (or is_causal=True)")
+    _offset_route_restrictions("window_size", qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
+    r = 0 if is_causal else right
+    return (0 if left == -1 else min(left + r + 1, 2 ** 30), r)
+
+
+def _offset_route_restrictions(what: str, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs) -> None:
+    """What the ``kv_lens`` route asks of a call (:func:`_kv_lens_args`), worded for the keyword ``what`` that rides on it."""
+    if qk_quant_gran != "per_thread":
+        raise ValueError(f"{what} needs qk_quant_gran='per_thread' (got {qk_quant_gran!r})")
+    if not kwargs.get("fuse_q_quant", True):
+        raise ValueError(f"{what} needs the fused Q quantiser (fuse_q_quant=False given)")
+    if pv_accum_dtype == "fp32":
+        raise ValueError(f"{what} needs pv_accum_dtype 'fp32+fp32' or 'fp32+fp16' (two-level accumulation)")
+    if ops.fp8_folded(kwargs.get("fp8_scores")):
+        raise ValueError(f"{what} takes the exact score form only (fp8_scores='folded' given)")
+    if smooth_v:
+        raise ValueError(f"{what} does not support smooth_v=True")
+    split = kwargs.get("split_kv")
+    if split is not None and not (split == 0 and not isinstance(split, bool)):
+        raise ValueError(f"{what} cannot be combined with split_kv={split!r} (None or 0 only)")
+    if kwargs.get("split_kv_exact", False):
+        raise ValueError(f"{what} cannot be combined with split_kv_exact=True")
+
+
 def _q_start_args(q_start, causal_align: str, is_causal: bool, q, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs) -> bool:
     """Whether ``q_start`` / ``causal_align`` ask for per-sample query offsets; their argument errors (checked before any work, on any
     device).  The offsets ride on the ``kv_lens`` route, so its restrictions hold (:func:`_kv_lens_args`), worded for these keywords."""
@@ -401,27 +445,17 @@ def _q_start_args(q_start, causal_align: str, is_causal: bool, q, qk_quant_gran:
             raise ValueError(f"q_start must have shape [B] = [{B}] (got {tuple(q_start.shape)})")
         if q_start.device != q.device:
             raise ValueError(f"q_start must be on q's device {q.device} (got {q_start.device})")
-    if qk_quant_gran != "per_thread":
-        raise ValueError(f"{what} needs qk_quant_gran='per_thread' (got {qk_quant_gran!r})")
-    if not kwargs.get("fuse_q_quant", True):
-        raise ValueError(f"{what} needs the fused Q quantiser (fuse_q_quant=False given)")
-    if pv_accum_dtype == "fp32":
-        raise ValueError(f"{what} needs pv_accum_dtype 'fp32+fp32' or 'fp32+fp16' (two-level accumulation)")
-    if ops.fp8_folded(kwargs.get("fp8_scores")):
-        raise ValueError(f"{what} takes the exact score form only (fp8_scores='folded' given)")
-    if smooth_v:
-        raise ValueError(f"{what} does not support smooth_v=True")
-    split = kwargs.get("split_kv")
-    if split is not None and not (split == 0 and not isinstance(split, bool)):
-        raise ValueError(f"{what} cannot be combined with split_kv={split!r} (None or 0 only)")
-    if kwargs.get("split_kv_exact", False):
-        raise ValueError(f"{what} cannot be combined with split_kv_exact=True")
+    _offset_route_restrictions(what, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     return True
 
 
-def _q_start_tensor(q_start, kv_lens, B: int, Lq: int, Lk: int, device) -> torch.Tensor:
+def _q_start_tensor(q_start, kv_lens, B: int, Lq: int, Lk: int, device, shift: int = 0) -> torch.Tensor:
     """The int32 ``[B]`` offsets of the attention call, formed on the device (no host read): the caller's tensor, an int broadcast to the
-    batch, or -- ``q_start`` None: ``causal_align='bottom_right'`` -- ``clamp(kv_lens, 0, Lk) - Lq``."""
+    batch, or -- ``q_start`` None: ``causal_align='bottom_right'`` -- ``clamp(kv_lens, 0, Lk) - Lq``.  ``shift`` (``window_size``'s ``right``
+    of a non-causal call: the diagonal moved right) is added to them, saturating at int32's end."""
+    if shift:
+        s = _q_start_tensor(q_start, kv_lens, B, Lq, Lk, device)
+        return (s.to(torch.int64) + int(shift)).clamp(max=2 ** 31 - 1).to(torch.int32)
     if q_start is None:
         if kv_lens is None:
             return torch.full((B,), Lk - Lq, dtype=torch.int32, device=device)
@@ -508,20 +542,23 @@ def _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
 # ------------------------------------------------------------------------------------------------
 def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND", is_causal: bool = False,
              sm_scale: Optional[float] = None, return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, q_start=None,
-             causal_align: str = "top_left", **kwargs: Any):
+             causal_align: str = "top_left", window_size=None, **kwargs: Any):
     """Select the implementation for the device, as the reference does per compute capability
     (core.py:143-157).  On gfx950 that is INT8 QK^T + FP8 PV with two-level FP32 accumulation
     (the reference's sm90 choice, ``pv_accum_dtype="fp32+fp32"``).  Extra SDPA-style kwargs
     (``attn_mask=``, ``dropout_p=``, ``scale=`` ...) are accepted and ignored exactly as the
     reference ignores them.  ``kv_lens`` (gfx950 extension, int32 / int64 ``[B]`` on q's device): a key length per sample of a right-padded
     batch; ``q_start`` (int, or int32 / int64 ``[B]``) / ``causal_align="bottom_right"``: where the causal diagonal of each sample lies -- row i
-    attends to key j iff ``j <= q_start[b] + i`` and ``j < len_b``.  See :func:`sageattn_qk_int8_pv_fp8_cuda`."""
+    attends to key j iff ``j <= q_start[b] + i`` and ``j < len_b``; ``window_size=(left, right)``: a sliding window in FlashAttention's
+    convention.  See :func:`sageattn_qk_int8_pv_fp8_cuda`."""
     _check_shapes(q, k, v, tensor_layout)      # (again in the entry point called below: this one is in front of the device query)
     if torch.compiler.is_compiling():      # the device query is not traceable; the opaque op checks the device when it runs
         if kv_lens is not None:            # (the compiled op has no such argument: a compiled call that ignored the lengths would be a trap)
             raise ValueError("kv_lens is not supported under torch.compile")
         if q_start is not None or causal_align != "top_left":
             raise ValueError("q_start / causal_align are not supported under torch.compile")
+        if window_size is not None:
+            raise ValueError("window_size is not supported under torch.compile")
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32")
     arch = get_gcn_arch(q.device) if q.is_cuda else "cpu"
@@ -530,7 +567,7 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32", split_kv=kwargs.get("split_kv"),
                                             fused_prepass=kwargs.get("fused_prepass"), fp8_scores=kwargs.get("fp8_scores"),
                                             split_kv_exact=kwargs.get("split_kv_exact", False), kv_lens=kv_lens,
-                                            q_start=q_start, causal_align=causal_align)
+                                            q_start=q_start, causal_align=causal_align, window_size=window_size)
     raise ValueError(f"Unsupported architecture: {arch} (sageattention_amd targets gfx950 / MI355X only)")
 
 
@@ -923,7 +960,7 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
                                  qk_quant_gran: str = "per_thread", sm_scale: Optional[float] = None,
                                  pv_accum_dtype: str = "fp32+fp16", smooth_k: bool = True, smooth_v: bool = False,
                                  return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, q_start=None,
-                                 causal_align: str = "top_left", **kwargs: Any):
+                                 causal_align: str = "top_left", window_size=None, **kwargs: Any):
     """INT8 QK^T + FP8 (e4m3) PV (reference core.py:636-826).  "fp32+fp32" and "fp32+fp16" both
     run the two-level kernel with an FP32 tile buffer (gfx950's FP8 MFMA only writes FP32, so V
     keeps the full ``scale_max=448``; the reference's 2.25 is an FP16-accumulator artefact,
@@ -959,15 +996,36 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     tiles -- correct, slower.  The route is ``kv_lens``'s (without ``kv_lens`` the attention entry gets lengths filled with
     ``kv_len`` and the plain pre-pass runs, the one-launch route included), so its restrictions hold and raise ValueError: per-thread
     granularity with the fused Q quantiser, two-level accumulation, the exact score form, no ``smooth_v``, no split-KV (a decode-shaped
-    call of ``qo_len <= 128`` therefore launches ``B * Hq`` workgroups), not under torch.compile."""
+    call of ``qo_len <= 128`` therefore launches ``B * Hq`` workgroups), not under torch.compile.
+
+    ``window_size=(left, right)`` (gfx950 extension; FlashAttention's convention: ints, ``-1`` = unbounded on that side, ``None`` or
+    ``(-1, -1)`` = no window): a bounded look-back without a mask tensor.  With the sample's offset ``s_b`` (``q_start[b]``, or what
+    ``causal_align`` forms, default 0), a window of ``W`` keys and a diagonal shift ``r``, row i attends to key j iff
+    ``s_b + r + i - W < j <= s_b + r + i`` and ``0 <= j < len_b``.  ``is_causal=True``: ``right`` must be 0 or -1, ``W = left + 1``, ``r = 0``.
+    ``is_causal=False`` with ``right >= 0``: the call runs the causal kernels with the diagonal moved right, ``r = right`` (added to the offsets
+    on the device, no host read) and ``W = left + right + 1``, unbounded for ``left = -1``; ``q_start`` is accepted here as the rows' position
+    on the key axis.  The window is a Python int, a property of the model and a constant of a captured graph.  A work item starts at the
+    64-key tile of the first key its rows see and ends at its diagonal: tiles outside are never requested, and key rows, k scales and V
+    images in front of the first one are never read.  The K mean, the K scale groups and the V scales are those of the call without the
+    window on the same ``kv_lens`` (the window masks scores, it does not change operands).  A row whose window holds no key -- in front of
+    key 0, or wholly behind ``len_b`` -- gives ``o = +0``, ``lse = -inf``.  A window that cuts no row (``left >= kv_len + qo_len``) gives
+    the bits of the call without it.  The restrictions are ``q_start``'s and raise ValueError naming ``window_size``."""
     if torch.compiler.is_compiling():
         if kv_lens is not None:
             raise ValueError("kv_lens is not supported under torch.compile (the compiled op takes the default routes)")
         if q_start is not None or causal_align != "top_left":
             raise ValueError("q_start / causal_align are not supported under torch.compile (the compiled op takes the default routes)")
+        if window_size is not None:
+            raise ValueError("window_size is not supported under torch.compile (the compiled op takes the default routes)")
         return _compiled_call("fp8", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse, kwargs)
     _check_shapes(q, k, v, tensor_layout)
     with_lens = _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
+    win = _window_args(window_size, is_causal, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
+    window, shift = win if win is not None else (0, 0)
+    if win is not None:                    # the causal kernels, the diagonal `shift` keys further right; offsets 0 unless the caller places the rows
+        is_causal = True
+        if q_start is None and causal_align == "top_left":
+            q_start = 0
     with_start = _q_start_args(q_start, causal_align, is_causal, q, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     exact = _split_exact_args(kwargs, qk_quant_gran, pv_accum_dtype, _dims(k, tensor_layout)[2])
     dtype = q.dtype
@@ -991,23 +1049,23 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
         # nothing here reads the lengths on the host (int64 is converted on the device)
         lens = kv_lens.to(torch.int32).contiguous()
         B_, _, Lq_ = _dims(q, tensor_layout)[:3]
-        start = _q_start_tensor(q_start, kv_lens, B_, Lq_, _dims(k, tensor_layout)[2], q.device) if with_start else None
+        start = _q_start_tensor(q_start, kv_lens, B_, Lq_, _dims(k, tensor_layout)[2], q.device, shift) if with_start else None
         lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
                                                                               return_lse, False, kv_lens=lens)
         o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, q_start=start)
+                               kv_lens=lens, q_start=start, window=window)
         return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
     if with_start:
         # query offsets without key lengths: the plain pre-pass (the one-launch route included) and the same attention entry with lengths
         # filled with kv_len -- full lengths give the plain call's bits
         B_, _, Lq_ = _dims(q, tensor_layout)[:3]
         Lk_ = _dims(k, tensor_layout)[2]
-        start = _q_start_tensor(q_start, None, B_, Lq_, Lk_, q.device)
+        start = _q_start_tensor(q_start, None, B_, Lq_, Lk_, q.device, shift)
         lens = torch.full((B_,), Lk_, dtype=torch.int32, device=q.device)
         lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
                                                                               return_lse, fused)
         o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, q_start=start)
+                               kv_lens=lens, q_start=start, window=window)
         return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
     if fuse_q:
         # default route: Q is quantised inside the attention kernel (same bits, no INT8 copy of Q in HBM).

@@ -181,8 +181,17 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // (correct, slower).  A row with s_b + i < 0 sees nothing: every score of it is masked in every tile its wave runs, its maximum stays at
 // kNegBig and its l at 0, and the epilogue gives it o = +0, lse = -inf as it does for a chunk of the inexact causal split that lies wholly
 // behind a row's diagonal.
+// WINDOW (a QSTART kernel, units sage_attn_d{128,64}_f8w.hip; stands in front of QSTART in the parameter list, which therefore still ends with the
+// QSTART and KVLEN flags): row i additionally sees only the last W = p.window keys up to its diagonal, s_b + i - W < j <= s_b + i.
+// A work item starts at the 64-key tile that holds the first key its first row sees (kc0: k_off, v_tile0 and ks_ptr shifted as the SEED branch
+// shifts them, Lk and kchunk0 in the shifted coordinates, so that loop bounds, steady tiles and masks follow as they do for QSTART) -- the tiles
+// in front of it are never requested.  Its first `nh` tiles (at most three) are those in which some row of the block is cut on the left: they run
+// as general iterations with one more comparison, in ascending key order, and behind them the ring is drained and primed again so that the
+// pipelined loop is entered as ever, with its first tile in slot 0.  p.cu_qs may be null (offsets 0).  s_b is clamped to [-p.Lq, p.Lk + W]: a
+// clamp to p.Lk would move the LEFT edge of an offset beyond the keys, which must see nothing.  With W >= p.Lk + p.Lq no row is cut, kc0 = 0 and
+// nh = 0: the work item runs what the QSTART kernel runs.
 template <int D, bool PV_FP8, bool CAUSAL, bool KTHREAD, bool TWO_LEVEL, int NH, int MASK = 0, int QF = 0, bool SFOLD = true, bool CPERS = false,
-          bool VROWS = false, bool SEED = false, bool QSTART = false, bool KVLEN = false>
+          bool VROWS = false, bool SEED = false, bool WINDOW = false, bool QSTART = false, bool KVLEN = false>
 __global__ void __launch_bounds__(256, SAGE_MIN_WAVES(D, MASK))
 sage_attn_kernel(const AttnParams p_arg)
 {
@@ -213,6 +222,7 @@ sage_attn_kernel(const AttnParams p_arg)
     static_assert(!KVLEN || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS && !SEED),
                   "per-sample key lengths: FP8 PV, fused per-thread Q, exact score form, dense");
     static_assert(!QSTART || (KVLEN && CAUSAL), "per-sample query offsets: the causal kv_lens kernels");
+    static_assert(!WINDOW || QSTART, "the sliding window: the q_start kernels");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     // (wave index in an SGPR, lane index from v_mbcnt wherever it is needed: nothing derived from threadIdx.x has to stay in a VGPR across
@@ -368,6 +378,7 @@ sage_attn_kernel(const AttnParams p_arg)
     // ---- per-sequence geometry ---------------------------------------------------------------
     int Lq = p.Lq, Lk = p.Lk;
     [[maybe_unused]] int qstart = 0;      // (QSTART) the position of the sample's query row 0 on the key axis
+    [[maybe_unused]] int wwin = 0, kc0w = 0;      // (WINDOW) keys a row sees up to and including its diagonal; the work item's first key (a multiple of 64)
     long q_off, k_off, o_off;
     long v_tile0, v_tstride;              // V image index = v_tile0 + t * v_tstride
     const float *qs_ptr, *ks_ptr;
@@ -413,8 +424,15 @@ sage_attn_kernel(const AttnParams p_arg)
             const int len = ((cint_p)p.cu_k)[__builtin_amdgcn_readfirstlane(b)];
             Lk = len < 0 ? 0 : (len < p.Lk ? len : p.Lk);
             if constexpr (QSTART) {        // the sample's query offset, requested with the length: p.cu_qs is as free in a dense launch as p.cu_k
+                if constexpr (WINDOW) {
+                    const int w = p.window, s = p.cu_qs != nullptr ? ((cint_p)p.cu_qs)[__builtin_amdgcn_readfirstlane(b)] : 0;
+                    wwin = w < 1 ? 1 : (w < (1 << 30) ? w : (1 << 30));
+                    const int sl = s < -p.Lq ? -p.Lq : s;                 // (the lower clamp first: sl - p.Lk cannot overflow)
+                    qstart = sl - p.Lk > wwin ? p.Lk + wwin : sl;       // (above p.Lk + W no row sees a key either way)
+                } else {
                 const int s = ((cint_p)p.cu_qs)[__builtin_amdgcn_readfirstlane(b)];
                 qstart = s < -p.Lq ? -p.Lq : (s < p.Lk ? s : p.Lk);
+                }
             }
         }
         q_off = (long)b * p.q_sb + (long)hq * p.q_sh;
@@ -427,6 +445,15 @@ sage_attn_kernel(const AttnParams p_arg)
         qs_stride = 1;
         ks_ptr = p.k_scale + ((long)b * p.Hkv + hk) * p.nks;
         ks_tstride = KTHREAD ? 4 : 1;
+        if constexpr (WINDOW) {
+            // the first key any row of the block sees, a0 = max(0, s + 128 qblk - W + 1), and the tile it lies in: the item's key 0 from here on
+            const int a0 = (qstart - wwin) + qblk * BLKQ + 1;
+            kc0w = a0 > 0 ? (a0 & ~(BLKK - 1)) : 0;
+            k_off += (long)kc0w * p.k_sl;
+            v_tile0 += kc0w >> 6;
+            ks_ptr += (kc0w >> 6) * 4;
+            Lk = Lk > kc0w ? Lk - kc0w : 0;
+        }
     }
 
     SAGE_TSTAMP(1);
@@ -436,7 +463,7 @@ sage_attn_kernel(const AttnParams p_arg)
     // key <= row  <=>  local key <= row - kchunk0
     // (QSTART: row i sees key <= i + qstart -- the same shift with kchunk0 = -qstart, in [-p.Lk, p.Lq].  Every bound below is formed from
     //  it in signed arithmetic: a division that truncates a negative numerator towards zero yields a value the following clamp to 0 replaces)
-    const int kchunk0 = QSTART ? -qstart
+    const int kchunk0 = QSTART ? kc0w - qstart
                       : SEED ? (CAUSAL ? p.kv_base + (hk % p.kv_split) * Lk : 0)
                              : ((CAUSAL && p.kv_split > 1 && p.cu_q == nullptr) ? (hk % p.kv_split) * Lk : 0);
     const int crow0 = row0 - kchunk0;
@@ -448,6 +475,18 @@ sage_attn_kernel(const AttnParams p_arg)
         lim = lim > 0 ? lim : 0;
         n_iters = lim < n_iters ? lim : n_iters;
     }
+    // (WINDOW) head tiles: the block's last row that exists sees keys from x on (the item's coordinates), so tiles 0 .. ceil(x / 64) - 1 cut some row
+    // on the left
+    [[maybe_unused]] int nh = 0;
+    if constexpr (WINDOW) {
+        int rlast = qblk * BLKQ + BLKQ - 1;
+        rlast = rlast < Lq ? rlast : Lq - 1;
+        const int x = rlast - kchunk0 + 1 - wwin;
+        nh = x > 0 ? (x + BLKK - 1) >> 6 : 0;
+        nh = nh < n_iters ? nh : n_iters;
+    }
+    int n_lim = n_iters;                  // tiles of the run in hand: all of them, or (WINDOW) the head tiles first
+    if constexpr (WINDOW) n_lim = nh > 0 ? nh : n_iters;
 
     // ---- Q fragments (B operand of S^T = K Q^T), resident in VGPRs ---------------------------
     v4i qf[C::KSTEPS];
@@ -606,11 +645,11 @@ sage_attn_kernel(const AttnParams p_arg)
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     };
-    if (n_iters > 0) {
+    if (n_lim > 0) {
         load_kscales(0, ksc);
         issue_loads(0, 0);
     }
-    if (n_iters > 1) issue_loads(1, 1);
+    if (n_lim > 1) issue_loads(1, 1);
     // The Q fragments are fetched AFTER the first tiles' LDS-DMA has been issued: hipcc waits vmcnt(0) at the first use of an
     // ordinary VGPR load, and with the Q loads in front it did so after the first DMA instruction -- the Q round trip and the
     // tiles' round trip ran one after the other in every workgroup's prologue.
@@ -700,15 +739,15 @@ sage_attn_kernel(const AttnParams p_arg)
         }
     }
     SAGE_TSTAMP(2);
-    ring_wait(n_iters > 1);
+    ring_wait(n_lim > 1);
     SAGE_TSTAMP(3);
 
     int cur = 0;
     // One K/V tile in the general form: masked, ragged, or one of a workgroup's last two (the whole, unmasked tiles in front of them run the
     // software-pipelined loops below).
     auto tile_iter = [&](const int it) {
-        const bool more = (it + 1) < n_iters;
-        const bool more2 = (it + 2) < n_iters;
+        const bool more = (it + 1) < n_lim;
+        const bool more2 = (it + 2) < n_lim;
         const int nxt = (cur + 1 == NSTAGE) ? 0 : cur + 1;
         float ksc_next[NH][2];
         if (more) load_kscales(it + 1, ksc_next);
@@ -719,7 +758,7 @@ sage_attn_kernel(const AttnParams p_arg)
 #pragma unroll
         for (int hh = 0; hh < NH; hh++) {
             const int key0 = it * KT + hh * BLKK;
-            if (key0 < Lk && (!CAUSAL || key0 <= crow0 + 31)) nact = hh + 1;
+            if (key0 < Lk && (!CAUSAL || key0 <= crow0 + 31) && (!WINDOW || key0 + BLKK - 1 > crow0 - wwin)) nact = hh + 1;     // (WINDOW: not wholly in front of the wave's first row's window)
         }
         // ---- attn_mask (Triton-named API only; attn_qk_int8_per_block.py:31-51): additive term per
         //      score in the log2 domain.  bool: 0 / -1e6, and a tile whose whole 128x64 mask block is
@@ -751,7 +790,7 @@ sage_attn_kernel(const AttnParams p_arg)
             const unsigned char *ks = smem + cur * C::STAGE_BYTES;
             const unsigned char *vs = ks + C::K_TILE_BYTES;
             const int last_key = it * KT + nact * BLKK - 1;
-            const bool full = (MASK == 0) && (nact == NH) && !(CAUSAL && last_key > crow0) && (last_key < Lk);
+            const bool full = (MASK == 0) && (nact == NH) && !(CAUSAL && last_key > crow0) && (last_key < Lk) && !(WINDOW && it < nh);
 
             // ---- S^T = K Q^T (int8 -> int32), NS sub-tiles of 32 keys ----
             v16i s[NS];
@@ -809,7 +848,7 @@ sage_attn_kernel(const AttnParams p_arg)
                         if (sb < 2 * nact) {
                             const float cc = cs[sb >> 1][(KTHREAD && (i & 2)) ? 1 : 0];
                             const int key = it * KT + sb * 32 + crow(i, g);
-                            const bool ok = (key < Lk) && (!CAUSAL || key <= cmy_row);
+                            const bool ok = (key < Lk) && (!CAUSAL || key <= cmy_row) && (!WINDOW || key > cmy_row - wwin);
                             if constexpr (MASK != 0) mx = fmaxf(mx, (ok ? sfl(s[sb][i]) * cc : 0.0f) + mk[sb][i] - OFF);
                             else mx = fmaxf(mx, ok ? __builtin_fmaf(sfl(s[sb][i]), cc, -OFF) : -INFINITY);
                         }
@@ -858,7 +897,7 @@ sage_attn_kernel(const AttnParams p_arg)
                         else v = __builtin_amdgcn_exp2f(__builtin_fmaf(sfl(s[sb][i]), cc, -m_new));
                         if constexpr (decltype(masked)::value) {
                             const int key = it * KT + sb * 32 + crow(i, g);
-                            const bool ok = (sb < 2 * nact) && (key < Lk) && (!CAUSAL || key <= cmy_row);
+                            const bool ok = (sb < 2 * nact) && (key < Lk) && (!CAUSAL || key <= cmy_row) && (!WINDOW || key > cmy_row - wwin);
                             v = ok ? v : 0.0f;
                         }
                     }
@@ -973,6 +1012,22 @@ sage_attn_kernel(const AttnParams p_arg)
     };
 
     int it = 0;
+    if constexpr (WINDOW) {
+        // the head tiles, then the ring again from slot 0 for what follows (the pipelined loop enters with its first tile there): the last head
+        // tile ended behind vmcnt(0) and a barrier, so every wave is past its reads of all three slots
+        if (nh > 0) {
+#pragma nounroll
+            for (; it < nh; it++) tile_iter(it);
+            n_lim = n_iters;
+            cur = 0;
+            if (it < n_iters) {
+                load_kscales(it, ksc);
+                issue_loads(it, 0);
+                if (it + 1 < n_iters) issue_loads(it + 1, 1);
+                ring_wait(it + 1 < n_iters);
+            }
+        }
+    }
     if constexpr (MASK == 0) {
         static_assert(NH == 1 && NSTAGE == 3, "the pipelined loops are written for 64-key iterations on the 3-slot ring");
         constexpr bool SIX_BODIES = D == 128 || PV_FP8;         // the pipelined loops' ring slot as a compile-time constant (see the FP8 loop; not D = 64 FP16 PV)
@@ -993,7 +1048,9 @@ sage_attn_kernel(const AttnParams p_arg)
         //  nothing at all -- which the last-tile bodies, whose masked scores still set a row maximum, do not provide for: general iterations.
         //  With a multiple of 64 every row of a block that runs these bodies sees key 0: they need n_iters >= 2, i.e. 128 qblk + 128 - kchunk0 > 64,
         //  so crow0 of wave 0 is > -64, hence >= 0; the one negative case, crow0 = -64, has lim = 1 and runs no pipelined body)
-        const bool diag_ok = DIAG_PIPE && (!QSTART || (kchunk0 & (KT - 1)) == 0) && (n_steady > 0 ? n_iters - n_steady == 2 : (PV_FP8 && n_iters == 2 && Lk >= 2 * KT));
+        // (WINDOW: and neither of the two is a head tile -- every row then sees its diagonal key in them, and whole rows of the first)
+        bool diag_ok = DIAG_PIPE && (!QSTART || (kchunk0 & (KT - 1)) == 0) && (n_steady > 0 ? n_iters - n_steady == 2 : (PV_FP8 && n_iters == 2 && Lk >= 2 * KT));
+        if constexpr (WINDOW) diag_ok = diag_ok && nh <= (n_steady > 0 ? n_steady : 0);
         // TAIL_PIPE (non-causal FP8 PV): the two whole tiles the steady loop leaves (it looks two tiles ahead) and a ragged last one behind them take the
         // pipelined body as well -- keys past Lk masked like keys behind the diagonal, the ragged tile requested in the general (clamped) form
         // (FP16 PV, D = 128: the two whole tiles of a call whose Lk is a multiple of 64, behind at least one steady tile -- kinds 1 and 2 as they are)

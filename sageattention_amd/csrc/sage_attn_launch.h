@@ -179,7 +179,7 @@ hipError_t launch_attn_f8_kvlens(const AttnParams &p, const AttnVariant &v, int 
 {
     using C = TileCfg<D, true, 1>;
 #define SAGE_F8K(C_, F_) if (v.causal == C_ && v.qf == F_) \
-    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, !C_);
+    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, !C_);
     SAGE_F8K(false, 1) SAGE_F8K(false, 2) SAGE_F8K(true, 1) SAGE_F8K(true, 2)
 #undef SAGE_F8K
     return hipErrorInvalidValue;
@@ -192,9 +192,22 @@ hipError_t launch_attn_f8_qstart(const AttnParams &p, const AttnVariant &v, int 
 {
     using C = TileCfg<D, true, 1>;
 #define SAGE_F8Q(F_) if (v.causal && v.qf == F_) \
-    return launch_kernel<sage_attn_kernel<D, true, true, true, true, 1, 0, F_, false, false, false, false, true, true>>(C::LDS_BYTES, p, nwork, l, false);
+    return launch_kernel<sage_attn_kernel<D, true, true, true, true, 1, 0, F_, false, false, false, false, false, true, true>>(C::LDS_BYTES, p, nwork, l, false);
     SAGE_F8Q(1) SAGE_F8Q(2)
 #undef SAGE_F8Q
+    return hipErrorInvalidValue;
+}
+
+// A sliding window on top of the query offsets (sage_attn_kernel's WINDOW): the q_start kernels with p.window keys per row, p.cu_qs nullable: the
+// units sage_attn_d{128,64}_f8w.hip.  The hardware's dispatch over the causal work order planned for the padded shapes.
+template <int D>
+hipError_t launch_attn_f8_window(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
+{
+    using C = TileCfg<D, true, 1>;
+#define SAGE_F8W(F_) if (v.causal && v.qf == F_) \
+    return launch_kernel<sage_attn_kernel<D, true, true, true, true, 1, 0, F_, false, false, false, false, true, true, true>>(C::LDS_BYTES, p, nwork, l, false);
+    SAGE_F8W(1) SAGE_F8W(2)
+#undef SAGE_F8W
     return hipErrorInvalidValue;
 }
 

@@ -47,7 +47,7 @@ inline bool multiples_of(int n, const Strides &s) { return multiples_of(n, s.sb,
 struct MaskArg { const void *ptr; int kind; int64_t sb, sh, sq, sk; };
 
 // SageLaunchAttr (nullable) -> the launch workspace and the launcher's options; the attributes are arguments of THIS call, nothing is kept
-struct LaunchAttr { unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; const int32_t *q_start; };
+struct LaunchAttr { unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; const int32_t *q_start; int window; };
 int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAttr &out)
 {
     out.ws = nullptr;
@@ -55,6 +55,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     out.trace = nullptr;
     out.trace_wgs = 0;
     out.q_start = nullptr;
+    out.window = 0;
     if (attr == nullptr) return SAGE_OK;
     SageLaunchAttr a{};
     // struct_bytes is what the CALLER's struct holds: fewer bytes than ours (an older caller) are read as far as they go, more (a newer
@@ -63,6 +64,8 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     const size_t n = attr->struct_bytes > sizeof(SageLaunchAttr) ? sizeof(SageLaunchAttr) : attr->struct_bytes;
     memcpy(&a, attr, n);
     if (n < offsetof(SageLaunchAttr, q_start) + sizeof(a.q_start)) a.q_start = nullptr;      // (a struct that ends inside the field does not have it)
+    if (n < offsetof(SageLaunchAttr, window) + sizeof(a.window)) a.window = 0;
+    SAGE_REQUIRE(a.window >= 0, "SageLaunchAttr.window = %d: the number of keys a row sees up to its diagonal, 0 = unbounded", a.window);
     SAGE_REQUIRE((a.flags & ~(SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES | SAGE_ATTR_FORCE_PERSISTENT)) == 0, "unknown SageLaunchAttr.flags 0x%x", a.flags);
     SAGE_REQUIRE((a.flags & (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES)) != (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES),
                  "SageLaunchAttr.flags asks for both FP8 score forms");
@@ -77,6 +80,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     out.trace = a.trace;
     out.trace_wgs = a.trace != nullptr ? a.trace_wgs : 0;
     out.q_start = a.q_start;
+    out.window = a.window;
     return SAGE_OK;
 }
 
@@ -173,6 +177,9 @@ int attn_run(const AttnCall &c)
     // (per-sample query offsets travel in the attributes; kv_lens marks the one entry point that takes them)
     SAGE_REQUIRE(la.q_start == nullptr || (c.kv_lens != nullptr && c.is_causal && !la.opts.fp8_folded),
                  "SageLaunchAttr.q_start: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
+    // (so does the window, which may come without offsets)
+    SAGE_REQUIRE(la.window == 0 || (c.kv_lens != nullptr && c.is_causal && !la.opts.fp8_folded),
+                 "SageLaunchAttr.window: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
     SAGE_REQUIRE(c.kv_lens == nullptr || (per_thread && fp8 && !split && c.v_rows == nullptr && !la.opts.fp8_folded),
                  "kv_lens: FP8 PV, the exact score form (SAGE_ATTR_FP8_FOLDED_SCORES), no split");
     SAGE_REQUIRE(!(per_block && varlen) || c.cu_q != nullptr, "varlen needs cu_seqlens_q");
@@ -225,6 +232,7 @@ int attn_run(const AttnCall &c)
     if (c.mask != nullptr) { p.mask = c.mask->ptr; p.m_sb = c.mask->sb; p.m_sh = c.mask->sh; p.m_sq = c.mask->sq; p.m_sk = c.mask->sk; v.mask_kind = c.mask->kind; }
     if (c.kv_lens != nullptr) { p.cu_k = c.kv_lens; v.kv_lens = true; }
     if (la.q_start != nullptr) { p.cu_qs = la.q_start; v.q_start = true; }
+    p.window = v.window = la.window;
     v.head_dim = c.D; v.pv_fp8 = fp8; v.causal = c.is_causal != 0;
     // FP16 PV: the kernel's TWO_LEVEL parameter selects the Triton kernel form (true) or the CUDA kernel form (false)
     v.two_level = fp8 ? c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : c.pv_accum == SAGE_PV_ACCUM_TRITON;
@@ -1122,6 +1130,7 @@ SAGE_API int sage_attn_fused_q_pv_f8_split_exact(const void *q, const int8_t *k,
     if (const int rc = read_attr(attr, stream, false, la)) return rc;
     SAGE_REQUIRE(!la.opts.fp8_folded, "the exact split takes the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES given)");
     SAGE_REQUIRE(la.q_start == nullptr, "SageLaunchAttr.q_start: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
+    SAGE_REQUIRE(la.window == 0, "SageLaunchAttr.window: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
     if (const int rc = split_exact_check(q, k, k_scale, B, Hq, Hkv, kv_split, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, q_dtype)) return rc;
     SAGE_REQUIRE(v_image && v_scale && o_part && lse_part && chunk_max, "null tensor pointer");
     SAGE_REQUIRE(tail == 0 || tail == 1, "tail must be 0 (the whole chunks) or 1 (the ragged tail), got %d", tail);

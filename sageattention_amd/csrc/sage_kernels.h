@@ -61,6 +61,8 @@ struct AttnParams {
     const float *seed_max;
     int seed_chunks, seed_first;
     int kv_base;
+    int window;               // AttnVariant::window: keys a row sees up to and including its diagonal (the WINDOW kernels; in the block's tail padding:
+                              // its size and the offsets of the hidden arguments behind it are what they were)
 };
 
 // launch attributes of an attention call that are not kernel parameters (the C ABI's SageLaunchAttr, include/sage_gfx950.h)
@@ -92,6 +94,8 @@ struct AttnVariant {
                         // sage_quant_qk_int8_kvlens / sage_prep_v_fp8_kvlens
     bool q_start;       // per-sample query offsets (kv_lens and causal): AttnParams::cu_qs = int32 offsets [B] in device memory, row i of sample b
                         // attends to key j iff j <= clamp(cu_qs[b], -p.Lq, p.Lk) + i and j < its length
+    int window;         // > 0: a sliding window on the causal kv_lens kernels (AttnParams::window = this): row i sees key j iff additionally
+                        // j > s_b + i - window, s_b = cu_qs[b] (0 without q_start); 0: none
 };
 constexpr int attn_qf(bool per_block, int q_dtype) { return (per_block ? 3 : 1) + (q_dtype == 0 ? 0 : 1); }   // q_dtype: DT_F16 (0) / DT_BF16
 // the one attention launcher: plans the work order, checks that the route exists (hipErrorInvalidValue) and launches the variant's kernel.

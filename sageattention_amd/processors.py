@@ -21,7 +21,7 @@ from .core import sageattn, sageattn_qk_int8_pv_fp16_triton
 def sdpa(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, attn_mask: Optional[torch.Tensor] = None,
          dropout_p: float = 0.0, is_causal: bool = False, scale: Optional[float] = None, enable_gqa: bool = False,
          tensor_layout: str = "HND", kv_lens: Optional[torch.Tensor] = None, q_start=None,
-         causal_align: str = "top_left") -> torch.Tensor:
+         causal_align: str = "top_left", window_size=None) -> torch.Tensor:
     """``torch.nn.functional.scaled_dot_product_attention`` signature on the gfx950 kernels.
 
     Without a mask: ``sageattn`` (INT8 QK^T + FP8 PV, two-level accumulation).  With ``attn_mask`` (bool or additive,
@@ -32,6 +32,7 @@ def sdpa(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, attn_mask:
     ``q_start`` (int, or int32 / int64 ``[B]``) / ``causal_align="bottom_right"`` (with ``is_causal=True``, without a mask): where the causal
     diagonal of each sample lies -- row i attends to key j iff ``j <= q_start[b] + i``; ``"bottom_right"`` is torch's ``causal_lower_right``.
     Forwarded to ``sageattn`` as ``kv_lens`` is.
+    ``window_size=(left, right)`` (FlashAttention's convention, without a mask): a sliding window on the same kernels, forwarded likewise.
     Dropout is not part of the reference's path and is rejected."""
     if dropout_p != 0.0:
         raise NotImplementedError("sageattention has no dropout (the reference's callers pass dropout_p=0.0)")
@@ -40,9 +41,11 @@ def sdpa(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, attn_mask:
     with_start = q_start is not None or causal_align != "top_left"
     if attn_mask is not None and with_start:
         raise ValueError("pass either attn_mask or q_start / causal_align: the masked route takes no query offsets")
-    if kv_lens is not None or with_start:
+    if attn_mask is not None and window_size is not None:
+        raise ValueError("pass either attn_mask or window_size: the masked route takes no window")
+    if kv_lens is not None or with_start or window_size is not None:
         return sageattn(query, key, value, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=scale, kv_lens=kv_lens,
-                        q_start=q_start, causal_align=causal_align)
+                        q_start=q_start, causal_align=causal_align, window_size=window_size)
     if attn_mask is not None:
         if is_causal:
             raise ValueError("pass either attn_mask or is_causal, as with scaled_dot_product_attention")
