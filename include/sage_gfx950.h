@@ -122,7 +122,11 @@ SAGE_API int sage_quant_qk_int8(const void *x, const void *mean, int8_t *out, fl
  *   seq_order   (nullable) the sequences by descending query length: the unit order of an attention launch WITHOUT a work list
  *   work_items  (nullable) the work list of the attention launch: (sequence, 128-row query block) int32 pairs for every query block that
  *               exists, sorted by descending weight = 64-key tiles the block visits under `is_causal` (ties: sequence index, then the
- *               later block first); the caller allocates 2 * (ceil(sum Lq / 128) + nseq) ints, a host-known bound of the count
+ *               later block first); the caller allocates 2 * (ceil(sum Lq / 128) + nseq) ints, a host-known bound of the count.
+ *               is_causal selects the mask the WEIGHTS assume: 0 none, 2 the bottom-right causal mask (block j of a sequence weighs
+ *               clamp(ceil((Lk - Lq + 128 (j + 1)) / 64), 0, ceil(Lk / 64)) tiles, what a SAGE_ATTR_CAUSAL_BOTTOM_RIGHT launch runs; blocks of
+ *               weight 0 stay in the list, last), any other non-zero value the top-left one (min(2 j + 2, ceil(Lk / 64))).  Since results never
+ *               depend on the order (below), the value 2 changes only how its caller's launch is scheduled.
  *   slab_first / slab_seq  (nullable, together) the 512-token slabs of sage_prepass_kv_varlen: prefix sums of the slab counts of the nseq
  *               sequences and of two gap segments -- rows cu_k[nseq] .. total_k and rows 0 .. cu_k[0] of the packed tensors, which belong to no
  *               sequence but which `k.mean(dim=0)` (core.py:432-434) still averages over: statistics only -- (nseq + 3 ints), and slab ->
@@ -339,6 +343,17 @@ SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale
  *                   len_b -- gives o = +0, lse = -inf, never NaN.  A window that cuts no row (window >= Lk + Lq) gives the bits of the call
  *                   without it.  Every other sage_attn_* entry point, and that one with is_causal = 0 or SAGE_ATTR_FP8_FOLDED_SCORES, refuses
  *                   a non-zero window (SAGE_EINVAL).  The reference has no counterpart.
+ *  flags bit 8      SAGE_ATTR_CAUSAL_BOTTOM_RIGHT: the causal mask of a PACKED batch aligned bottom-right, per sequence (Python:
+ *                   sageattn_qk_int8_pv_fp8_varlen(causal_align="bottom_right")).  With Lq_b, Lk_b from cu_seqlens_q / cu_seqlens_k, row i of
+ *                   sequence b attends to key j of that sequence iff j <= i + Lk_b - Lq_b: the last row sees every key (a chunk of prefill
+ *                   against a cached prefix, decode rows with Lq = 1, speculative verification and full prefills packed into one call).  No
+ *                   operand: the kernel forms the offset from the cu_seqlens words it loads anyway.  A row with i + Lk_b - Lq_b < 0 (the first
+ *                   Lq_b - Lk_b rows of a sequence with more rows than keys, every row of one without keys) sees nothing: o = +0, lse = -inf,
+ *                   never NaN.  A sequence whose offset is a multiple of 64 keeps the pipelined diagonal tiles, any other runs the diagonal of
+ *                   a query block as three general tiles.  Build the work list with sage_varlen_plan(is_causal = 2).  Honoured by
+ *                   sage_attn_fused_qblock_pv_f8_varlen with is_causal = 1 and pv_accum = SAGE_PV_ACCUM_TWO_LEVEL alone; that entry with
+ *                   is_causal = 0 or SAGE_PV_ACCUM_SINGLE, and every other sage_attn_* entry point, refuses the bit (SAGE_EINVAL).  Without the
+ *                   bit a packed causal launch keeps the reference's top-left mask (attn_qk_int8_per_block_causal_varlen.py:45-46).
  */
 typedef struct SageLaunchAttr {
     uint32_t struct_bytes;
@@ -366,6 +381,8 @@ typedef struct SageLaunchAttr {
 #define SAGE_ATTR_FP8_FOLDED_SCORES 4u
 /* tests: take the persistent route from two rounds of workgroups up instead of twelve (needs launch_ws) */
 #define SAGE_ATTR_FORCE_PERSISTENT 2u
+/* packed batches: the causal mask aligned bottom-right per sequence (the attribute block above: flags bit 8) */
+#define SAGE_ATTR_CAUSAL_BOTTOM_RIGHT 8u
 SAGE_API int64_t sage_attn_launch_ws_bytes(void);
 
 /*
@@ -568,7 +585,7 @@ SAGE_API int sage_attn_fused_qblock_pv_f16_varlen(const void *q, const int8_t *k
                                                   int is_causal, float q_premul, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr);
 /* Its FP8-PV form (ABI 22): the operands of sage_attn_qk_int8_pv_f8_varlen without q_scale / cu_q_scale, q in fp16 / bf16 quantised per
  * 128-row block in the prologue after the multiplication by q_premul (= sm_scale log2(e)); pv_accum two-level / single, exact score form,
- * lse as there. */
+ * lse as there.  The one entry point that honours SAGE_ATTR_CAUSAL_BOTTOM_RIGHT (is_causal = 1, two-level). */
 SAGE_API int sage_attn_fused_qblock_pv_f8_varlen(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
                                                  const float *k_scale, const float *v_scale,
                                                  const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, const int32_t *cu_k_scale,

@@ -630,12 +630,12 @@ def sageattn_qk_int8_pv_fp16_triton(q, k, v, tensor_layout: str = "HND", quantiz
 class _VarlenState:
     """Operands of the attention launch of one ``sageattn_varlen`` call (what its pre-pass produces)."""
     __slots__ = ("q", "q_int8", "q_scale", "k_int8", "k_scale", "v_image", "cu_q", "cu_k", "cu_qs", "cu_ks", "order", "plan", "fuse_q",
-                 "max_seqlen_q", "is_causal", "q_premul", "dtype", "head_dim_og", "v_scale", "km", "sm_scale")
+                 "max_seqlen_q", "is_causal", "q_premul", "dtype", "head_dim_og", "v_scale", "km", "sm_scale", "bottom_right")
 
 
 @torch.compiler.disable
 def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k, kwargs,
-                    v_fp8: bool = False) -> _VarlenState:
+                    v_fp8: bool = False, bottom_right: bool = False) -> _VarlenState:
     """Everything of ``sageattn_varlen`` in front of the attention launch (core.py:427-444): the index arrays (one launch, no host
     synchronisation), ``km`` over all packed tokens, INT8 K, the fp16 V image -- one launch that reads K and V once where the head barrier
     reaches (``prepass_kv_varlen``), else the kernel sequence with the same bits.  ``v_fp8`` (``sageattn_qk_int8_pv_fp8_varlen``): the same
@@ -659,8 +659,10 @@ def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     nseq = cu_q.shape[0] - 1
     # block-count prefix sums, the attention launch's work list and the pre-pass's slab map from one small launch (None: more sequences than
     # it takes -- then torch prefix sums, an on-device argsort for the order and the kernel sequence)
-    plan = varlen_plan(cu_q, cu_k, want_q_blocks=not fuse_q, total_q=q.shape[0], total_k=k.shape[0], is_causal=is_causal, Hq=Hq, Hkv=Hkv,
-                       head_dim=D, pv_fp8=v_fp8) if kwargs.get("varlen_plan", True) else None
+    # (bottom-right alignment: the work list is sorted by the weights of that mask -- sage_varlen_plan's is_causal = 2)
+    st.bottom_right = bool(bottom_right)
+    plan = varlen_plan(cu_q, cu_k, want_q_blocks=not fuse_q, total_q=q.shape[0], total_k=k.shape[0], is_causal=2 if bottom_right else is_causal,
+                       Hq=Hq, Hkv=Hkv, head_dim=D, pv_fp8=v_fp8) if kwargs.get("varlen_plan", True) else None
     st.plan = plan if (plan is not None and kwargs.get("work_list", True)) else None
     fused = kwargs.get("fused_prepass")
     if fused is None:
@@ -751,7 +753,9 @@ def _varlen_attend_f8(st: _VarlenState, two_level: bool, return_lse: bool):
     plan = st.plan
     items, hdr, bound = (plan.items, plan.hdr, plan.items_bound) if plan is not None else (None, None, 0)
     nseq = st.cu_q.shape[0] - 1
-    attr = ops.attn_attr(q.device, st.is_causal, Hq * (T // 128), packed=st.fuse_q) if plan is not None else None
+    # (the bottom-right flag travels in the attributes, with the work list's ticket block or -- no work list: the hardware's dispatch -- alone)
+    attr = ops.attn_attr(q.device, st.is_causal, Hq * (T // 128), packed=st.fuse_q, causal_bottom_right=st.bottom_right) if plan is not None \
+        else _cabi.launch_attr(causal_bottom_right=st.bottom_right)
     if st.fuse_q:
         rc = _cabi.load().sage_attn_fused_qblock_pv_f8_varlen(
             _p(q), _p(st.k_int8), _p(st.v_image), _p(o), _p(lse), _p(st.k_scale), _p(st.v_scale), _p(st.cu_q), _p(st.cu_k), _p(st.cu_ks),
@@ -778,10 +782,28 @@ def sageattn_qk_int8_pv_fp8_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seql
     ``pv_accum_dtype`` "fp32+fp32" (two-level accumulation) or "fp32" (single level); the exact score form.  ``return_lse``: ``(o, lse)``
     with ``lse`` fp32 ``[Hq, sum Lq]`` in natural-log units, smooth_k corrected as the dense calls' (core.py:328-329).  Route switches as
     ``sageattn_varlen``'s (``fuse_q_quant``, ``work_list``, ``varlen_plan``, ``fused_prepass``): the same bits either way.  No host
-    synchronisation on any route."""
+    synchronisation on any route.
+    ``causal_align`` (a keyword taken from ``kwargs`` by name -- the function's parameter list is pinned by tests/test_varlen_fp8_host.py -- and
+    validated here, before any device call): "top_left", the default (the reference's mask: row i of a sequence sees keys j <= i), or
+    "bottom_right" (row i of sequence b sees keys j <= i + Lk_b - Lq_b, the lengths from ``cu_seqlens``: the last row sees every key, as
+    FlashAttention's varlen call aligns its mask -- chunks of prefill against a cached prefix, decode rows, speculative verification and full prefills in one packed call).  "bottom_right" needs
+    ``is_causal=True``, ``pv_accum_dtype="fp32+fp32"`` and the fused Q quantiser; rows in front of key 0 (the first ``Lq_b - Lk_b`` rows of a
+    sequence with more rows than keys, every row of one without keys) give ``o = +0`` and ``lse = -inf``."""
     if pv_accum_dtype not in ("fp32", "fp32+fp32"):
         raise ValueError(f"Unsupported pv_accum_dtype: {pv_accum_dtype}")
-    st = _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k, kwargs, v_fp8=True)
+    causal_align = kwargs.pop("causal_align", "top_left")
+    if not isinstance(causal_align, str) or causal_align not in ("top_left", "bottom_right"):
+        raise ValueError(f'causal_align must be "top_left" or "bottom_right" (got {causal_align!r})')
+    bottom_right = causal_align == "bottom_right"
+    if bottom_right:
+        if not is_causal:
+            raise ValueError('causal_align="bottom_right" needs is_causal=True')
+        if pv_accum_dtype != "fp32+fp32":
+            raise ValueError(f'causal_align="bottom_right" needs pv_accum_dtype="fp32+fp32" (got {pv_accum_dtype!r})')
+        if not kwargs.get("fuse_q_quant", True):
+            raise ValueError('causal_align="bottom_right" needs the fused Q quantiser (fuse_q_quant=False is not supported)')
+    st = _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k, kwargs, v_fp8=True,
+                         bottom_right=bottom_right)
     o, lse = _varlen_attend_f8(st, pv_accum_dtype == "fp32+fp32", return_lse)
     if not return_lse:
         return o

@@ -181,6 +181,10 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // (correct, slower).  A row with s_b + i < 0 sees nothing: every score of it is masked in every tile its wave runs, its maximum stays at
 // kNegBig and its l at 0, and the epilogue gives it o = +0, lse = -inf as it does for a chunk of the inexact causal split that lies wholly
 // behind a row's diagonal.
+// QSTART without KVLEN (a CAUSAL packed launch, FP8 PV, per-block Q, two-level: units sage_attn_d{128,64}_f8vb.hip) is the packed route's
+// bottom-right alignment: p.cu_q != null, and the offset of sequence b is s_b = Lk_b - Lq_b, formed from the four cu_seqlens words the packed
+// branch has just loaded -- no operand of its own.  Everything above follows from kchunk0 = -s_b as it does for the dense kernels; a query block
+// wholly in front of key 0 (lim = 0) and every block of a sequence without keys run no tile and write o = +0, lse = -inf.
 // WINDOW (a QSTART kernel, units sage_attn_d{128,64}_f8w.hip; stands in front of QSTART in the parameter list, which therefore still ends with the
 // QSTART and KVLEN flags): row i additionally sees only the last W = p.window keys up to its diagonal, s_b + i - W < j <= s_b + i.
 // A work item starts at the 64-key tile that holds the first key its first row sees (kc0: k_off, v_tile0 and ks_ptr shifted as the SEED branch
@@ -221,7 +225,8 @@ sage_attn_kernel(const AttnParams p_arg)
                   "the seeded split: FP8 PV, fused per-thread Q, exact score form, dense");
     static_assert(!KVLEN || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS && !SEED),
                   "per-sample key lengths: FP8 PV, fused per-thread Q, exact score form, dense");
-    static_assert(!QSTART || (KVLEN && CAUSAL), "per-sample query offsets: the causal kv_lens kernels");
+    static_assert(!QSTART || (CAUSAL && (KVLEN || (PV_FP8 && !KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && QF >= 3 && !VROWS && !SEED && !WINDOW))),
+                  "query offsets: the causal kv_lens kernels (dense, p.cu_qs), or a packed launch's bottom-right alignment (FP8 PV, per-block Q, two-level)");
     static_assert(!WINDOW || QSTART, "the sliding window: the q_start kernels");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -393,6 +398,7 @@ sage_attn_kernel(const AttnParams p_arg)
         Lq = q1 - q0;
         Lk = k1 - k0;
         if (qblk * BLKQ >= Lq) break;
+        if constexpr (QSTART && !KVLEN) qstart = Lk - Lq;      // (packed, bottom-right: in [-Lq, Lk] by construction, wave-uniform, from the words just loaded)
         q_off = (long)q0 * p.q_sl + (long)h * p.q_sh;
         k_off = (long)k0 * p.k_sl + (long)hk * p.k_sh;
         o_off = (long)q0 * p.o_sl + (long)h * p.o_sh;
@@ -1107,8 +1113,10 @@ sage_attn_kernel(const AttnParams p_arg)
     v4f sc4[C::DT][4], mn4[C::DT][4];
     // (KVLEN) all ones, or zero for a sample without keys: a bit mask the compiler cannot see through -- as a select on Lk it moved the factor
     // loads below behind a branch, 0.6 us per work item (profiles/kv_lens_trace_wan.txt)
-    [[maybe_unused]] unsigned keep = (!KVLEN || Lk > 0) ? ~0u : 0u;
-    if constexpr (KVLEN) asm volatile("" : "+v"(keep));
+    // (a packed bottom-right launch -- QSTART without KVLEN -- likewise: a sequence without keys has no V scales of its own)
+    constexpr bool KEEP = KVLEN || QSTART;
+    [[maybe_unused]] unsigned keep = (!KEEP || Lk > 0) ? ~0u : 0u;
+    if constexpr (KEEP) asm volatile("" : "+v"(keep));
 #pragma unroll
     for (int dt = 0; dt < C::DT; dt++) {
 #pragma unroll
@@ -1134,7 +1142,7 @@ sage_attn_kernel(const AttnParams p_arg)
             for (int j = 0; j < 4; j++) {
                 x[j] = o[dt][4 * r4 + j] * inv;
                 if (PV_FP8) x[j] *= sc4[dt][r4][j];
-                if constexpr (KVLEN) x[j] = __uint_as_float(__float_as_uint(x[j]) & keep);      // (a sample without keys: +0 whatever its scale slots hold)
+                if constexpr (KEEP) x[j] = __uint_as_float(__float_as_uint(x[j]) & keep);      // (a sample without keys: +0 whatever its scale slots hold)
                 x[j] += mn4[dt][r4][j];
             }
             if constexpr (SEED) {      // FP32 partial rows straight from the registers: four channels per lane

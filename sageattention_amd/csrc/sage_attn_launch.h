@@ -157,6 +157,22 @@ hipError_t launch_attn_f8_varlen(const AttnParams &p, const AttnVariant &v, int 
     return hipErrorInvalidValue;
 }
 
+// The packed route with bottom-right causal alignment (sage_attn_kernel's QSTART without KVLEN: the offset of a sequence is Lk - Lq, formed from its
+// cu_seqlens words): causal, FP8 PV two-level, the exact score form, per-block Q (qf 3 / 4), each as the ticket kernel (CPERS, over the work list)
+// and as the plain one (no work list: the hardware's dispatch): the units sage_attn_d{128,64}_f8vb.hip.
+template <int D>
+hipError_t launch_attn_f8_varlen_br(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
+{
+    using C = TileCfg<D, true, 1>;
+    if (!v.causal || !v.two_level) return hipErrorInvalidValue;
+    const bool list = p.work_items != nullptr;
+#define SAGE_F8VB(F_, P_) if (v.qf == F_ && list == P_) \
+    return launch_kernel<sage_attn_kernel<D, true, true, false, true, 1, 0, F_, false, P_, false, false, false, true, false>>(C::LDS_BYTES, p, nwork, l, P_);
+    SAGE_F8VB(3, true) SAGE_F8VB(3, false) SAGE_F8VB(4, true) SAGE_F8VB(4, false)
+#undef SAGE_F8VB
+    return hipErrorInvalidValue;
+}
+
 // The exact split's pass 2 (sage_attn_kernel's SEED): the fused per-thread Q quantiser (qf 1 / 2), FP8 PV two-level, the exact score form; the
 // running maximum starts from pass 1's prefix maximum and the partial outputs are FP32: the units sage_attn_d{128,64}_f8s.hip.  Split launches
 // take the hardware's dispatch (as the inexact split's do).

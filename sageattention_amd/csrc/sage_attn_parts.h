@@ -48,4 +48,10 @@ hipError_t launch_attn_f8_window(const AttnParams &p, const AttnVariant &v, int 
 extern template hipError_t launch_attn_f8_window<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_f8_window<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 
+// the packed FP8-PV route with bottom-right causal alignment (offset Lk - Lq per sequence, from cu_seqlens): units sage_attn_d{128,64}_f8vb.hip
+template <int D>
+hipError_t launch_attn_f8_varlen_br(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l);
+extern template hipError_t launch_attn_f8_varlen_br<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_f8_varlen_br<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+
 }  // namespace sage

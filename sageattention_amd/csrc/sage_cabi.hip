@@ -47,7 +47,7 @@ inline bool multiples_of(int n, const Strides &s) { return multiples_of(n, s.sb,
 struct MaskArg { const void *ptr; int kind; int64_t sb, sh, sq, sk; };
 
 // SageLaunchAttr (nullable) -> the launch workspace and the launcher's options; the attributes are arguments of THIS call, nothing is kept
-struct LaunchAttr { unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; const int32_t *q_start; int window; };
+struct LaunchAttr { unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; const int32_t *q_start; int window; bool bottom_right; };
 int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAttr &out)
 {
     out.ws = nullptr;
@@ -56,6 +56,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     out.trace_wgs = 0;
     out.q_start = nullptr;
     out.window = 0;
+    out.bottom_right = false;
     if (attr == nullptr) return SAGE_OK;
     SageLaunchAttr a{};
     // struct_bytes is what the CALLER's struct holds: fewer bytes than ours (an older caller) are read as far as they go, more (a newer
@@ -66,7 +67,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     if (n < offsetof(SageLaunchAttr, q_start) + sizeof(a.q_start)) a.q_start = nullptr;      // (a struct that ends inside the field does not have it)
     if (n < offsetof(SageLaunchAttr, window) + sizeof(a.window)) a.window = 0;
     SAGE_REQUIRE(a.window >= 0, "SageLaunchAttr.window = %d: the number of keys a row sees up to its diagonal, 0 = unbounded", a.window);
-    SAGE_REQUIRE((a.flags & ~(SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES | SAGE_ATTR_FORCE_PERSISTENT)) == 0, "unknown SageLaunchAttr.flags 0x%x", a.flags);
+    SAGE_REQUIRE((a.flags & ~(SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES | SAGE_ATTR_FORCE_PERSISTENT | SAGE_ATTR_CAUSAL_BOTTOM_RIGHT)) == 0, "unknown SageLaunchAttr.flags 0x%x", a.flags);
     SAGE_REQUIRE((a.flags & (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES)) != (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES),
                  "SageLaunchAttr.flags asks for both FP8 score forms");
     SAGE_REQUIRE(a.launch_ws == nullptr || (a.launch_ws_bytes >= sage::kAttnSchedBytes && (reinterpret_cast<uintptr_t>(a.launch_ws) & 127u) == 0),
@@ -81,6 +82,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     out.trace_wgs = a.trace != nullptr ? a.trace_wgs : 0;
     out.q_start = a.q_start;
     out.window = a.window;
+    out.bottom_right = (a.flags & SAGE_ATTR_CAUSAL_BOTTOM_RIGHT) != 0;
     return SAGE_OK;
 }
 
@@ -180,6 +182,9 @@ int attn_run(const AttnCall &c)
     // (so does the window, which may come without offsets)
     SAGE_REQUIRE(la.window == 0 || (c.kv_lens != nullptr && c.is_causal && !la.opts.fp8_folded),
                  "SageLaunchAttr.window: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
+    // (bottom-right alignment of a packed batch: the one entry point with FP8 PV, the per-block Q quantiser and cu_seqlens)
+    SAGE_REQUIRE(!la.bottom_right || (per_block && fp8 && varlen && c.is_causal && c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL),
+                 "SAGE_ATTR_CAUSAL_BOTTOM_RIGHT: sage_attn_fused_qblock_pv_f8_varlen with is_causal = 1 and SAGE_PV_ACCUM_TWO_LEVEL only");
     SAGE_REQUIRE(c.kv_lens == nullptr || (per_thread && fp8 && !split && c.v_rows == nullptr && !la.opts.fp8_folded),
                  "kv_lens: FP8 PV, the exact score form (SAGE_ATTR_FP8_FOLDED_SCORES), no split");
     SAGE_REQUIRE(!(per_block && varlen) || c.cu_q != nullptr, "varlen needs cu_seqlens_q");
@@ -233,6 +238,7 @@ int attn_run(const AttnCall &c)
     if (c.kv_lens != nullptr) { p.cu_k = c.kv_lens; v.kv_lens = true; }
     if (la.q_start != nullptr) { p.cu_qs = la.q_start; v.q_start = true; }
     p.window = v.window = la.window;
+    v.bottom_right = la.bottom_right;
     v.head_dim = c.D; v.pv_fp8 = fp8; v.causal = c.is_causal != 0;
     // FP16 PV: the kernel's TWO_LEVEL parameter selects the Triton kernel form (true) or the CUDA kernel form (false)
     v.two_level = fp8 ? c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : c.pv_accum == SAGE_PV_ACCUM_TRITON;
@@ -381,7 +387,7 @@ SAGE_API int sage_varlen_plan(const int32_t *cu_seqlens_q, const int32_t *cu_seq
     sage::VarlenPlanParams p{};
     SAGE_REQUIRE(slab_seq == nullptr || total_k > 0, "the slab map needs total_k, the row count of the packed k / v tensors");
     p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k; p.nseq = nseq; p.blkq = blkq; p.blkk = blkk; p.total_k = total_k;
-    p.causal = is_causal ? 1 : 0; p.Hq = Hq > 0 ? Hq : 1; p.Hkv = Hkv > 0 ? Hkv : 1; p.head_dim = head_dim; p.pv_fp8 = pv_fp8 ? 1 : 0;
+    p.causal = is_causal == 2 ? 2 : (is_causal ? 1 : 0); p.Hq = Hq > 0 ? Hq : 1; p.Hkv = Hkv > 0 ? Hkv : 1; p.head_dim = head_dim; p.pv_fp8 = pv_fp8 ? 1 : 0;
     p.cu_qs = cu_q_scale; p.cu_ks = cu_k_scale; p.order = seq_order; p.items = work_items;
     p.slab_first = slab_first; p.slab_seq = slab_seq; p.hdr = hdr;
     p.items_cap = work_items_cap; p.slab_cap = slab_seq_cap;
@@ -406,7 +412,7 @@ SAGE_API int sage_debug_varlen_items(const int32_t *lq, const int32_t *lk, int n
     if (nitems > items_cap) return fail(SAGE_EINVAL, "sage_debug_varlen_items: %d items do not fit %d", nitems, items_cap);
     for (int s = 0; s < nseq; s++)
         for (int j = 0; j < (lq[s] + 127) / 128; j++) {
-            const int r = sage::varlen_item_rank(lq, lk, nseq, s, j, is_causal != 0);
+            const int r = sage::varlen_item_rank(lq, lk, nseq, s, j, is_causal == 2 ? 2 : (is_causal ? 1 : 0));
             if (r < 0 || r >= nitems) return fail(SAGE_ELAUNCH, "sage_debug_varlen_items: rank %d out of range", r);
             items_out[2 * r] = s; items_out[2 * r + 1] = j;
         }
@@ -1131,6 +1137,7 @@ SAGE_API int sage_attn_fused_q_pv_f8_split_exact(const void *q, const int8_t *k,
     SAGE_REQUIRE(!la.opts.fp8_folded, "the exact split takes the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES given)");
     SAGE_REQUIRE(la.q_start == nullptr, "SageLaunchAttr.q_start: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
     SAGE_REQUIRE(la.window == 0, "SageLaunchAttr.window: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
+    SAGE_REQUIRE(!la.bottom_right, "SAGE_ATTR_CAUSAL_BOTTOM_RIGHT: sage_attn_fused_qblock_pv_f8_varlen with is_causal = 1 and SAGE_PV_ACCUM_TWO_LEVEL only");
     if (const int rc = split_exact_check(q, k, k_scale, B, Hq, Hkv, kv_split, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, q_dtype)) return rc;
     SAGE_REQUIRE(v_image && v_scale && o_part && lse_part && chunk_max, "null tensor pointer");
     SAGE_REQUIRE(tail == 0 || tail == 1, "tail must be 0 (the whole chunks) or 1 (the ragged tail), got %d", tail);

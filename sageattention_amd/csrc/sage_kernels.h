@@ -96,6 +96,8 @@ struct AttnVariant {
                         // attends to key j iff j <= clamp(cu_qs[b], -p.Lq, p.Lk) + i and j < its length
     int window;         // > 0: a sliding window on the causal kv_lens kernels (AttnParams::window = this): row i sees key j iff additionally
                         // j > s_b + i - window, s_b = cu_qs[b] (0 without q_start); 0: none
+    bool bottom_right;  // a packed causal launch (FP8 PV, per-block Q, two-level, the exact score form): row i of sequence b attends to key j iff
+                        // j <= i + Lk_b - Lq_b, the lengths from cu_q / cu_k -- no operand of its own (SAGE_ATTR_CAUSAL_BOTTOM_RIGHT)
 };
 constexpr int attn_qf(bool per_block, int q_dtype) { return (per_block ? 3 : 1) + (q_dtype == 0 ? 0 : 1); }   // q_dtype: DT_F16 (0) / DT_BF16
 // the one attention launcher: plans the work order, checks that the route exists (hipErrorInvalidValue) and launches the variant's kernel.

@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(1024) varlen_plan_kernel(const VarlenPlanParam
         for (int idx = i; idx < nitems_all; idx += 1024) {
             const int s = owner(sq[cur], idx);
             const int j = idx - (s > 0 ? sq[cur][s - 1] : 0);
-            const int rank = varlen_item_rank(lq_s, lk_s, nseq, s, j, p.causal != 0);
+            const int rank = varlen_item_rank(lq_s, lk_s, nseq, s, j, p.causal);
             if (rank >= 0 && rank < nitems) {
                 p.items[2 * rank] = s;
                 p.items[2 * rank + 1] = j;

@@ -89,50 +89,59 @@ SAGE_HD int plan_work_order(WorkOrder &w, int nheads, int nqblk, long kv_len, in
 }
 
 // ---- packed (varlen) batches ---------------------------------------------------------------------------------------------------
-// The query blocks of ALL sequences form one item list per query head, sorted by descending weight (64-key tiles the block visits);
+// The query blocks of ALL sequences form one item list per query head, sorted by descending weight (64-key tiles the block visits under the launch's mask);
 // the launch then IS a dense launch over nheads = Hq heads of `nitems` "query blocks" each: the same work_item() deals the list to the
 // XCDs, so a kv-head's K/V of every sequence streams through one L2 and the heaviest blocks are dispatched first.  The list is built on
 // the device (varlen_plan_kernel, sage_quant.hip) from the functions below; sage_debug_varlen_items runs the same functions on the host.
 // The reference sizes its grid by max_seqlen_q for every sequence and lets the blocks past a sequence's end exit
 // (triton/attn_qk_int8_block_varlen.py:22-30,98-121).
 
-// 64-key tiles query block j (128 rows) of a sequence with lq queries and lk keys visits (top-left causal mask: key <= query)
-SAGE_HD int varlen_item_weight(int lk, int j, bool causal)
+// The weights only order the list: every item is in it exactly once whatever they are, and no result depends on the order.  `causal` is the
+// mask the WEIGHTS assume: 0 none, 1 top-left (key <= query), 2 bottom-right (key <= query + lk - lq: the packed route's
+// SAGE_ATTR_CAUSAL_BOTTOM_RIGHT launches).  A caller who passes 2 changes how its launch is scheduled, nothing else.
+
+// ceil((lk - lq) / 64) for the bottom-right mask, 0 otherwise: the causal tile limit of query block j is 2 j + 2 + this
+SAGE_HD int varlen_causal_shift(int lq, int lk, int causal) { return causal == 2 ? (lk - lq + 63) >> 6 : 0; }      // (arithmetic shift: floor)
+
+// 64-key tiles query block j (128 rows) of a sequence with lq queries and lk keys visits: what the kernel's `lim` gives,
+// clamp(ceil((shift + 128 (j + 1)) / 64), 0, ceil(lk / 64)), shift = 0 (top-left) or lk - lq (bottom-right)
+SAGE_HD int varlen_item_weight(int lq, int lk, int j, int causal)
 {
     const int ntk = (lk + 63) >> 6;
-    if (!causal) return ntk;
-    const int lim = 2 * j + 2;
+    if (causal == 0) return ntk;
+    int lim = 2 * j + 2 + varlen_causal_shift(lq, lk, causal);
+    lim = lim > 0 ? lim : 0;                         // (a block wholly in front of key 0: weight 0 -- it stays in the list and writes its zeros)
     return lim < ntk ? lim : ntk;
 }
 
 // number of query blocks j in [0, nq) of that sequence whose weight is > w
-SAGE_HD int varlen_count_heavier(int nq, int lk, int w, bool causal)
+SAGE_HD int varlen_count_heavier(int nq, int lq, int lk, int w, int causal)
 {
     const int ntk = (lk + 63) >> 6;
     if (ntk <= w || nq <= 0) return 0;
-    if (!causal) return nq;
-    const int first = w < 0 ? 0 : (w >> 1);            // 2 j + 2 > w  <=>  j >= floor(w / 2)
+    if (causal == 0 || w < 0) return nq;             // (every weight is >= 0)
+    // w >= 0: max(2 j + 2 + c, 0) > w  <=>  2 j + 2 + c > w  <=>  j >= floor((w - c) / 2)
+    int first = (w - varlen_causal_shift(lq, lk, causal)) >> 1;
+    first = first > 0 ? first : 0;
     return first < nq ? nq - first : 0;
 }
 
 // rank of item (sequence s, query block j) in the list sorted by (weight descending, sequence index ascending, query block descending):
 // a total order, so every rank in [0, nitems) is taken exactly once.  lq / lk: the nseq sequence lengths.
-SAGE_HD int varlen_item_rank(const int *lq, const int *lk, int nseq, int s, int j, bool causal)
+SAGE_HD int varlen_item_rank(const int *lq, const int *lk, int nseq, int s, int j, int causal)
 {
-    const int w = varlen_item_weight(lk[s], j, causal);
+    const int w = varlen_item_weight(lq[s], lk[s], j, causal);
     int rank = 0;
     for (int t = 0; t < nseq; t++) {
         const int nq = (lq[t] + 127) >> 7;
-        const int gt = varlen_count_heavier(nq, lk[t], w, causal);
+        const int gt = varlen_count_heavier(nq, lq[t], lk[t], w, causal);
         rank += gt;
-        if (t < s) rank += varlen_count_heavier(nq, lk[t], w - 1, causal) - gt;           // equal weight, earlier sequence
+        if (t < s) rank += varlen_count_heavier(nq, lq[t], lk[t], w - 1, causal) - gt;           // equal weight, earlier sequence
     }
-    // equal weight, same sequence, later query block (weights do not decrease with j, so these are j + 1 .. last block of weight w)
+    // equal weight, same sequence, later query block (weights do not decrease with j under any of the masks, so these are j + 1 .. last block of weight w)
     const int nq_s = (lq[s] + 127) >> 7;
-    const int ge_w = varlen_count_heavier(nq_s, lk[s], w - 1, causal);                      // blocks of weight >= w: the last ge_w blocks
-    const int gt_w = varlen_count_heavier(nq_s, lk[s], w, causal);
+    const int gt_w = varlen_count_heavier(nq_s, lq[s], lk[s], w, causal);
     rank += (nq_s - gt_w) - 1 - j;                                                         // blocks j' with j < j' < nq_s - gt_w
-    (void)ge_w;
     return rank;
 }
 

@@ -29,6 +29,8 @@ UNITS = ("sage_attn_d128_f8.hip", "sage_attn_d128_f8f.hip", "sage_attn_d128_f16.
 UNITS_PAIR = ("sage_attn_d128_f8q.hip", "sage_attn_d64_f8q.hip")
 # the window_size route's units, two kernels each as well (a list of their own: UNITS and UNITS_PAIR are what their users compare them with)
 UNITS_WINDOW = ("sage_attn_d128_f8w.hip", "sage_attn_d64_f8w.hip")
+# the packed route's bottom-right units, four kernels each (per-block Q fp16 / bf16, with and without the ticket loop); again a list of their own
+UNITS_PACKED_BR = ("sage_attn_d128_f8vb.hip", "sage_attn_d64_f8vb.hip")
 NEED = {"v_mfma_f32_32x32x64_f8f6f4": 19, "v_mfma_scale_f32_32x32x64_f8f6f4": 19}        # 16 passes; everything else used here: 8 passes
 NEED_DEFAULT = 11
 PASSES = {k: 16 for k in NEED}
@@ -184,7 +186,7 @@ def lint(asm_text):
 
 
 def main(argv):
-    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW
+    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW + UNITS_PACKED_BR
     total = 0
     for u in units:
         f, n = lint(listing(u))
