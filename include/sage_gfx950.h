@@ -342,7 +342,16 @@ SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale
  *                   never read, as those from len_b on are not.  A row whose window holds no key -- in front of key 0, or wholly behind
  *                   len_b -- gives o = +0, lse = -inf, never NaN.  A window that cuts no row (window >= Lk + Lq) gives the bits of the call
  *                   without it.  Every other sage_attn_* entry point, and that one with is_causal = 0 or SAGE_ATTR_FP8_FOLDED_SCORES, refuses
- *                   a non-zero window (SAGE_EINVAL).  The reference has no counterpart.
+ *                   a non-zero window (SAGE_EINVAL) -- with one exception.  The reference has no counterpart.
+ *                   PACKED batches: sage_attn_fused_qblock_pv_f8_varlen honours a non-zero window ONLY TOGETHER WITH
+ *                   SAGE_ATTR_CAUSAL_BOTTOM_RIGHT (hence is_causal = 1, SAGE_PV_ACCUM_TWO_LEVEL, the exact score form): with s_b = Lk_b - Lq_b from
+ *                   cu_seqlens, row i of sequence b attends to key j iff s_b + i - window < j <= s_b + i and 0 <= j < Lk_b (FlashAttention's
+ *                   varlen convention, window = left + 1; Python: sageattn_qk_int8_pv_fp8_varlen(causal_align="bottom_right", window_size=)).
+ *                   Without the flag that entry refuses the window like every other one.  The offset needs no clamp there;
+ *                   max_seqlen_q <= 2^29.  Key rows, k scales and V images in front of a query block's first visible key are never read; rows
+ *                   in front of key 0 and every row of a sequence without keys give o = +0, lse = -inf; a window that cuts no row
+ *                   (window >= Lk_b + Lq_b for every sequence) gives the bits of the flag alone.  The work list is the unwindowed one,
+ *                   sage_varlen_plan(is_causal = 2): results never depend on the order.
  *  flags bit 8      SAGE_ATTR_CAUSAL_BOTTOM_RIGHT: the causal mask of a PACKED batch aligned bottom-right, per sequence (Python:
  *                   sageattn_qk_int8_pv_fp8_varlen(causal_align="bottom_right")).  With Lq_b, Lk_b from cu_seqlens_q / cu_seqlens_k, row i of
  *                   sequence b attends to key j of that sequence iff j <= i + Lk_b - Lq_b: the last row sees every key (a chunk of prefill
@@ -354,6 +363,8 @@ SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale
  *                   sage_attn_fused_qblock_pv_f8_varlen with is_causal = 1 and pv_accum = SAGE_PV_ACCUM_TWO_LEVEL alone; that entry with
  *                   is_causal = 0 or SAGE_PV_ACCUM_SINGLE, and every other sage_attn_* entry point, refuses the bit (SAGE_EINVAL).  Without the
  *                   bit a packed causal launch keeps the reference's top-left mask (attn_qk_int8_per_block_causal_varlen.py:45-46).
+ *                   Together with a non-zero `window` (above) the bit selects the packed sliding window: the one combination in which that
+ *                   entry point takes a window; the bit alone is the unbounded mask.
  */
 typedef struct SageLaunchAttr {
     uint32_t struct_bytes;
@@ -585,7 +596,8 @@ SAGE_API int sage_attn_fused_qblock_pv_f16_varlen(const void *q, const int8_t *k
                                                   int is_causal, float q_premul, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr);
 /* Its FP8-PV form (ABI 22): the operands of sage_attn_qk_int8_pv_f8_varlen without q_scale / cu_q_scale, q in fp16 / bf16 quantised per
  * 128-row block in the prologue after the multiplication by q_premul (= sm_scale log2(e)); pv_accum two-level / single, exact score form,
- * lse as there.  The one entry point that honours SAGE_ATTR_CAUSAL_BOTTOM_RIGHT (is_causal = 1, two-level). */
+ * lse as there.  The one entry point that honours SAGE_ATTR_CAUSAL_BOTTOM_RIGHT (is_causal = 1, two-level), and with it a non-zero
+ * SageLaunchAttr.window (the packed sliding window). */
 SAGE_API int sage_attn_fused_qblock_pv_f8_varlen(const void *q, const int8_t *k, const void *v_image, void *o, float *lse,
                                                  const float *k_scale, const float *v_scale,
                                                  const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, const int32_t *cu_k_scale,

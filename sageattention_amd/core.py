@@ -630,12 +630,12 @@ def sageattn_qk_int8_pv_fp16_triton(q, k, v, tensor_layout: str = "HND", quantiz
 class _VarlenState:
     """Operands of the attention launch of one ``sageattn_varlen`` call (what its pre-pass produces)."""
     __slots__ = ("q", "q_int8", "q_scale", "k_int8", "k_scale", "v_image", "cu_q", "cu_k", "cu_qs", "cu_ks", "order", "plan", "fuse_q",
-                 "max_seqlen_q", "is_causal", "q_premul", "dtype", "head_dim_og", "v_scale", "km", "sm_scale", "bottom_right")
+                 "max_seqlen_q", "is_causal", "q_premul", "dtype", "head_dim_og", "v_scale", "km", "sm_scale", "bottom_right", "window")
 
 
 @torch.compiler.disable
 def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k, kwargs,
-                    v_fp8: bool = False, bottom_right: bool = False) -> _VarlenState:
+                    v_fp8: bool = False, bottom_right: bool = False, window: int = 0) -> _VarlenState:
     """Everything of ``sageattn_varlen`` in front of the attention launch (core.py:427-444): the index arrays (one launch, no host
     synchronisation), ``km`` over all packed tokens, INT8 K, the fp16 V image -- one launch that reads K and V once where the head barrier
     reaches (``prepass_kv_varlen``), else the kernel sequence with the same bits.  ``v_fp8`` (``sageattn_qk_int8_pv_fp8_varlen``): the same
@@ -659,8 +659,10 @@ def _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     nseq = cu_q.shape[0] - 1
     # block-count prefix sums, the attention launch's work list and the pre-pass's slab map from one small launch (None: more sequences than
     # it takes -- then torch prefix sums, an on-device argsort for the order and the kernel sequence)
-    # (bottom-right alignment: the work list is sorted by the weights of that mask -- sage_varlen_plan's is_causal = 2)
+    # (bottom-right alignment: the work list is sorted by the weights of that mask -- sage_varlen_plan's is_causal = 2; a window on top of it
+    #  keeps that order, the unwindowed one: results never depend on it, and everything else in front of the launch is the unwindowed call's)
     st.bottom_right = bool(bottom_right)
+    st.window = int(window)
     plan = varlen_plan(cu_q, cu_k, want_q_blocks=not fuse_q, total_q=q.shape[0], total_k=k.shape[0], is_causal=2 if bottom_right else is_causal,
                        Hq=Hq, Hkv=Hkv, head_dim=D, pv_fp8=v_fp8) if kwargs.get("varlen_plan", True) else None
     st.plan = plan if (plan is not None and kwargs.get("work_list", True)) else None
@@ -754,8 +756,9 @@ def _varlen_attend_f8(st: _VarlenState, two_level: bool, return_lse: bool):
     items, hdr, bound = (plan.items, plan.hdr, plan.items_bound) if plan is not None else (None, None, 0)
     nseq = st.cu_q.shape[0] - 1
     # (the bottom-right flag travels in the attributes, with the work list's ticket block or -- no work list: the hardware's dispatch -- alone)
-    attr = ops.attn_attr(q.device, st.is_causal, Hq * (T // 128), packed=st.fuse_q, causal_bottom_right=st.bottom_right) if plan is not None \
-        else _cabi.launch_attr(causal_bottom_right=st.bottom_right)
+    # (so does the window, a Python int: SageLaunchAttr.window, honoured together with the flag only)
+    attr = ops.attn_attr(q.device, st.is_causal, Hq * (T // 128), packed=st.fuse_q, causal_bottom_right=st.bottom_right, window=st.window) \
+        if plan is not None else _cabi.launch_attr(causal_bottom_right=st.bottom_right, window=st.window)
     if st.fuse_q:
         rc = _cabi.load().sage_attn_fused_qblock_pv_f8_varlen(
             _p(q), _p(st.k_int8), _p(st.v_image), _p(o), _p(lse), _p(st.k_scale), _p(st.v_scale), _p(st.cu_q), _p(st.cu_k), _p(st.cu_ks),
@@ -770,6 +773,37 @@ def _varlen_attend_f8(st: _VarlenState, two_level: bool, return_lse: bool):
             _cabi.attr_arg(attr))
         ops.attn_check(rc, "sage_attn_qk_int8_pv_f8_varlen", attr, q.device)
     return o[..., :st.head_dim_og], lse
+
+
+def _varlen_window_args(window_size, is_causal: bool, causal_align: str, pv_accum_dtype: str, max_seqlen_q, max_seqlen_k, kwargs) -> int:
+    """``window_size=(left, right)`` of ``sageattn_qk_int8_pv_fp8_varlen`` as ``W``, the keys a row sees up to and including its bottom-right
+    diagonal (0: no window).  :func:`_window_args`' checks and wording where the two share a rule; the packed route's own restrictions
+    behind them.  Checked before any work, on any device."""
+    if window_size is None:
+        return 0
+    ok_int = lambda x: isinstance(x, int) and not isinstance(x, bool)
+    if not isinstance(window_size, (tuple, list)) or len(window_size) != 2 or not all(ok_int(x) for x in window_size):
+        raise ValueError(f"window_size must be a pair of ints (left, right), -1 = unbounded on that side (got {window_size!r})")
+    left, right = window_size
+    if left < -1 or right < -1:
+        raise ValueError(f"window_size=({left}, {right}): a side is -1 (unbounded) or a number of keys >= 0")
+    if is_causal and right not in (0, -1):
+        raise ValueError(f"window_size=({left}, {right}) with is_causal=True: right must be 0 or -1 (a causal row sees no key behind its diagonal)")
+    if left == -1 and (is_causal or right == -1):
+        return 0                           # unbounded: the call without the keyword
+    if not is_causal:
+        raise ValueError(f"window_size=({left}, {right}) with is_causal=False is not supported on packed batches (the packed route has no operand "
+                         f"for the diagonal's shift): is_causal=True with right 0 or -1")
+    if causal_align != "bottom_right":
+        raise ValueError(f'window_size=({left}, {right}) needs causal_align="bottom_right": packed windows are bottom-right aligned (FlashAttention\'s '
+                         f'varlen convention); for sequences with Lq = Lk the two alignments coincide (got causal_align={causal_align!r})')
+    if pv_accum_dtype != "fp32+fp32":
+        raise ValueError(f'window_size needs pv_accum_dtype="fp32+fp32" (got {pv_accum_dtype!r})')
+    if not kwargs.get("fuse_q_quant", True):
+        raise ValueError("window_size needs the fused Q quantiser (fuse_q_quant=False given)")
+    if int(max_seqlen_q) + int(max_seqlen_k) > 2 ** 29:
+        raise ValueError(f"window_size: max_seqlen_q + max_seqlen_k must not exceed 2**29 (got {max_seqlen_q} + {max_seqlen_k})")
+    return min(left + 1, 2 ** 30)
 
 
 @torch.compiler.disable
@@ -788,13 +822,22 @@ def sageattn_qk_int8_pv_fp8_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seql
     "bottom_right" (row i of sequence b sees keys j <= i + Lk_b - Lq_b, the lengths from ``cu_seqlens``: the last row sees every key, as
     FlashAttention's varlen call aligns its mask -- chunks of prefill against a cached prefix, decode rows, speculative verification and full prefills in one packed call).  "bottom_right" needs
     ``is_causal=True``, ``pv_accum_dtype="fp32+fp32"`` and the fused Q quantiser; rows in front of key 0 (the first ``Lq_b - Lk_b`` rows of a
-    sequence with more rows than keys, every row of one without keys) give ``o = +0`` and ``lse = -inf``."""
+    sequence with more rows than keys, every row of one without keys) give ``o = +0`` and ``lse = -inf``.
+    ``window_size=(left, right)`` (taken from ``kwargs`` by name as well; FlashAttention's varlen convention, -1 = unbounded on that side): a
+    sliding window aligned bottom-right -- with ``W = left + 1`` row i of sequence b sees key j iff ``i + Lk_b - Lq_b - W < j <= i + Lk_b - Lq_b``
+    and ``0 <= j < Lk_b``; tiles in front of a query block's window are never requested.  ``None``, ``(-1, -1)`` and, with ``is_causal=True``,
+    ``(-1, 0)`` are the call without the keyword.  A bounded ``left`` needs ``is_causal=True``, ``right`` 0 or -1, ``causal_align="bottom_right"``,
+    ``pv_accum_dtype="fp32+fp32"`` and the fused Q quantiser (``is_causal=False`` with a window is refused: the packed route has no operand for
+    the diagonal's shift).  The pre-pass is the unwindowed call's: K mean, k scales and V scales over every key of a sequence.  Rows whose
+    window holds no key give ``o = +0`` and ``lse = -inf``."""
     if pv_accum_dtype not in ("fp32", "fp32+fp32"):
         raise ValueError(f"Unsupported pv_accum_dtype: {pv_accum_dtype}")
     causal_align = kwargs.pop("causal_align", "top_left")
     if not isinstance(causal_align, str) or causal_align not in ("top_left", "bottom_right"):
         raise ValueError(f'causal_align must be "top_left" or "bottom_right" (got {causal_align!r})')
     bottom_right = causal_align == "bottom_right"
+    # (the window first: what it needs is worded for its keyword)
+    window = _varlen_window_args(kwargs.pop("window_size", None), is_causal, causal_align, pv_accum_dtype, max_seqlen_q, max_seqlen_k, kwargs)
     if bottom_right:
         if not is_causal:
             raise ValueError('causal_align="bottom_right" needs is_causal=True')
@@ -803,7 +846,7 @@ def sageattn_qk_int8_pv_fp8_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seql
         if not kwargs.get("fuse_q_quant", True):
             raise ValueError('causal_align="bottom_right" needs the fused Q quantiser (fuse_q_quant=False is not supported)')
     st = _varlen_prepare(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k, kwargs, v_fp8=True,
-                         bottom_right=bottom_right)
+                         bottom_right=bottom_right, window=window)
     o, lse = _varlen_attend_f8(st, pv_accum_dtype == "fp32+fp32", return_lse)
     if not return_lse:
         return o

@@ -64,8 +64,10 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
     if (v.seeded != (p.seed_max != nullptr) || (v.seeded && p.kv_split < 1)) return false;
     if (v.kv_lens && (p.cu_k == nullptr || p.kv_split > 1)) return false;
     if (v.q_start != (!varlen && p.cu_qs != nullptr) || (v.q_start && (!v.kv_lens || !v.causal))) return false;
-    // a window: the causal kv_lens kernels (offsets optional); shapes whose sums stay inside the kernel's int arithmetic
-    if (v.window < 0 || v.window != p.window || (v.window > 0 && (!v.kv_lens || !v.causal || (long)p.Lq + p.Lk > (1L << 29)))) return false;
+    // a window: the causal kv_lens kernels (offsets optional), or -- without kv_lens -- a packed bottom-right launch (the next line's conditions);
+    // shapes whose sums stay inside the kernel's int arithmetic (a packed launch has no Lk of its own: p.Lk = 0, the caller bounds the sum)
+    if (v.window < 0 || v.window != p.window ||
+        (v.window > 0 && (!v.causal || (long)p.Lq + p.Lk > (1L << 29) || (!v.kv_lens && !(varlen && v.bottom_right))))) return false;
     // bottom-right alignment of a packed batch: causal, FP8 PV, per-block Q, two-level, the exact score form
     if (v.bottom_right && (!varlen || !v.causal || !v.pv_fp8 || !per_block || !v.two_level || o.fp8_folded)) return false;
     return true;
@@ -78,12 +80,13 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     if (o.grid_out != nullptr) *o.grid_out = 0;
     if (nwork <= 0) return hipSuccess;
     if (!route_exists(p, v, o)) return hipErrorInvalidValue;
-    // the instantiation unit of (head_dim, PV format, FP8 score form, seeded / kv_lens / q_start / window / packed FP8 with the per-block Q quantiser, top-left or bottom-right)
+    // the instantiation unit of (head_dim, PV format, FP8 score form, seeded / kv_lens / q_start / window / packed FP8 with the per-block Q quantiser, top-left, bottom-right or bottom-right with a window)
     const bool d128 = v.head_dim == 128;
     if (v.seeded) return d128 ? launch_attn_f8_seeded<128>(p, v, nwork, o) : launch_attn_f8_seeded<64>(p, v, nwork, o);
-    if (v.window > 0) return d128 ? launch_attn_f8_window<128>(p, v, nwork, o) : launch_attn_f8_window<64>(p, v, nwork, o);
+    if (v.window > 0 && v.kv_lens) return d128 ? launch_attn_f8_window<128>(p, v, nwork, o) : launch_attn_f8_window<64>(p, v, nwork, o);
     if (v.q_start) return d128 ? launch_attn_f8_qstart<128>(p, v, nwork, o) : launch_attn_f8_qstart<64>(p, v, nwork, o);
     if (v.kv_lens) return d128 ? launch_attn_f8_kvlens<128>(p, v, nwork, o) : launch_attn_f8_kvlens<64>(p, v, nwork, o);
+    if (v.bottom_right && v.window > 0) return d128 ? launch_attn_f8_varlen_br_window<128>(p, v, nwork, o) : launch_attn_f8_varlen_br_window<64>(p, v, nwork, o);
     if (v.bottom_right) return d128 ? launch_attn_f8_varlen_br<128>(p, v, nwork, o) : launch_attn_f8_varlen_br<64>(p, v, nwork, o);
     if (v.pv_fp8 && v.qf >= 3) return d128 ? launch_attn_f8_varlen<128>(p, v, nwork, o) : launch_attn_f8_varlen<64>(p, v, nwork, o);
     if (!v.pv_fp8) return d128 ? launch_attn_part<128, false, true>(p, v, nwork, o) : launch_attn_part<64, false, true>(p, v, nwork, o);

@@ -77,6 +77,9 @@
 // __launch_bounds__ waves / SIMD the register allocator must allow: the software-pipelined loops carry two score tiles, which at D = 128 is
 // 2 waves (248 VGPRs); D = 64 fits 3 (167); the attn_mask variants 2.
 #define SAGE_MIN_WAVES(D, MASK) ((MASK) != 0 ? 2 : ((D) == 64 ? 3 : 2))
+// (the packed window's ticket kernel at D = 64 -- WINDOW, QSTART, no KVLEN, CPERS: the general iteration instantiated twice next to the ticket
+//  loop's state -- needs 4 VGPRs more than three waves leave, 172 against 168: it is built for 2 waves rather than with scratch)
+#define SAGE_MIN_WAVES_K(D, MASK, PACKED_WINDOW_TICKETS) (((PACKED_WINDOW_TICKETS) && (D) == 64) ? 2 : SAGE_MIN_WAVES(D, MASK))
 
 // asm text of the pipelined loops: two scores d0 / d1 from the bit patterns s0 / s1 of the QK^T accumulators, d = score * c - m (operands as
 // asm placeholders).  EXACT: the bias of the bit pattern is subtracted first (exact), then the FMA; FOLD (the FP8 opt-in variant): one FMA per
@@ -194,9 +197,13 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // pipelined loop is entered as ever, with its first tile in slot 0.  p.cu_qs may be null (offsets 0).  s_b is clamped to [-p.Lq, p.Lk + W]: a
 // clamp to p.Lk would move the LEFT edge of an offset beyond the keys, which must see nothing.  With W >= p.Lk + p.Lq no row is cut, kc0 = 0 and
 // nh = 0: the work item runs what the QSTART kernel runs.
+// WINDOW with QSTART and without KVLEN (units sage_attn_d{128,64}_f8vbw.hip) is the packed bottom-right form with a window: s_b = Lk_b - Lq_b as
+// above, W = p.window, the same head tiles, second priming and masks; only the shift of the item's first key is written for the packed layouts
+// (V images and per-block k scales: one per 64-key tile, stride Hkv).  With the ticket loop (CPERS) the next item's ticket is requested behind
+// the LAST tile of the item whichever run that is -- the request stands behind the remainder loop, not inside a run.
 template <int D, bool PV_FP8, bool CAUSAL, bool KTHREAD, bool TWO_LEVEL, int NH, int MASK = 0, int QF = 0, bool SFOLD = true, bool CPERS = false,
           bool VROWS = false, bool SEED = false, bool WINDOW = false, bool QSTART = false, bool KVLEN = false>
-__global__ void __launch_bounds__(256, SAGE_MIN_WAVES(D, MASK))
+__global__ void __launch_bounds__(256, SAGE_MIN_WAVES_K(D, MASK, WINDOW && QSTART && !KVLEN && CPERS))
 sage_attn_kernel(const AttnParams p_arg)
 {
     // The parameter block is read through the kernarg segment pointer, and inside the persistent loop through a copy of that pointer the
@@ -225,8 +232,8 @@ sage_attn_kernel(const AttnParams p_arg)
                   "the seeded split: FP8 PV, fused per-thread Q, exact score form, dense");
     static_assert(!KVLEN || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS && !SEED),
                   "per-sample key lengths: FP8 PV, fused per-thread Q, exact score form, dense");
-    static_assert(!QSTART || (CAUSAL && (KVLEN || (PV_FP8 && !KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && QF >= 3 && !VROWS && !SEED && !WINDOW))),
-                  "query offsets: the causal kv_lens kernels (dense, p.cu_qs), or a packed launch's bottom-right alignment (FP8 PV, per-block Q, two-level)");
+    static_assert(!QSTART || (CAUSAL && (KVLEN || (PV_FP8 && !KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && QF >= 3 && !VROWS && !SEED))),
+                  "query offsets: the causal kv_lens kernels (dense, p.cu_qs), or a packed launch's bottom-right alignment (FP8 PV, per-block Q, two-level; with or without a window)");
     static_assert(!WINDOW || QSTART, "the sliding window: the q_start kernels");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -408,6 +415,19 @@ sage_attn_kernel(const AttnParams p_arg)
         qs_stride = 0;
         ks_ptr = p.k_scale + (long)ks0 * p.Hkv + hk;                  // [sum nblk, Hkv]
         ks_tstride = p.Hkv;
+        if constexpr (WINDOW && QSTART && !KVLEN) {
+            // the packed window: W from p.window, clamped as in the dense branch; the offset needs no clamp (above).  The item's first key as
+            // there -- a0 <= Lk - W < Lk for a block that exists, so a shifted item keeps at least one key -- but in the PACKED layouts: V images
+            // and the per-block k scales are one per 64-key tile with stride Hkv
+            const int w = p.window;
+            wwin = w < 1 ? 1 : (w < (1 << 30) ? w : (1 << 30));
+            const int a0 = (qstart - wwin) + qblk * BLKQ + 1;
+            kc0w = a0 > 0 ? (a0 & ~(BLKK - 1)) : 0;
+            k_off += (long)kc0w * p.k_sl;
+            v_tile0 += (long)(kc0w >> 6) * p.Hkv;
+            ks_ptr += (long)(kc0w >> 6) * p.Hkv;
+            Lk = Lk > kc0w ? Lk - kc0w : 0;
+        }
     } else if constexpr (SEED) {
         // exact split (pass 2): chunk `chunk` of kv head hk0 starts at key kc0; q, k, its scales and the V image are the unsplit call's
         const int hk0 = hk / p.kv_split, kc0 = p.kv_base + (hk - hk0 * p.kv_split) * Lk;

@@ -173,6 +173,21 @@ hipError_t launch_attn_f8_varlen_br(const AttnParams &p, const AttnVariant &v, i
     return hipErrorInvalidValue;
 }
 
+// The same route with a sliding window (sage_attn_kernel's WINDOW with QSTART and without KVLEN: p.window keys up to each row's bottom-right
+// diagonal): the same four kernels per unit, the units sage_attn_d{128,64}_f8vbw.hip.
+template <int D>
+hipError_t launch_attn_f8_varlen_br_window(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
+{
+    using C = TileCfg<D, true, 1>;
+    if (!v.causal || !v.two_level || !v.bottom_right || v.window <= 0) return hipErrorInvalidValue;
+    const bool list = p.work_items != nullptr;
+#define SAGE_F8VBW(F_, P_) if (v.qf == F_ && list == P_) \
+    return launch_kernel<sage_attn_kernel<D, true, true, false, true, 1, 0, F_, false, P_, false, false, true, true, false>>(C::LDS_BYTES, p, nwork, l, P_);
+    SAGE_F8VBW(3, true) SAGE_F8VBW(3, false) SAGE_F8VBW(4, true) SAGE_F8VBW(4, false)
+#undef SAGE_F8VBW
+    return hipErrorInvalidValue;
+}
+
 // The exact split's pass 2 (sage_attn_kernel's SEED): the fused per-thread Q quantiser (qf 1 / 2), FP8 PV two-level, the exact score form; the
 // running maximum starts from pass 1's prefix maximum and the partial outputs are FP32: the units sage_attn_d{128,64}_f8s.hip.  Split launches
 // take the hardware's dispatch (as the inexact split's do).

@@ -54,4 +54,10 @@ hipError_t launch_attn_f8_varlen_br(const AttnParams &p, const AttnVariant &v, i
 extern template hipError_t launch_attn_f8_varlen_br<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_f8_varlen_br<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 
+// ... and with a sliding window (SageLaunchAttr.window together with the flag): units sage_attn_d{128,64}_f8vbw.hip
+template <int D>
+hipError_t launch_attn_f8_varlen_br_window(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l);
+extern template hipError_t launch_attn_f8_varlen_br_window<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_f8_varlen_br_window<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+
 }  // namespace sage

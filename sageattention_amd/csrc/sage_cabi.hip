@@ -180,8 +180,11 @@ int attn_run(const AttnCall &c)
     SAGE_REQUIRE(la.q_start == nullptr || (c.kv_lens != nullptr && c.is_causal && !la.opts.fp8_folded),
                  "SageLaunchAttr.q_start: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
     // (so does the window, which may come without offsets)
-    SAGE_REQUIRE(la.window == 0 || (c.kv_lens != nullptr && c.is_causal && !la.opts.fp8_folded),
-                 "SageLaunchAttr.window: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
+    // (... or, on the packed entry, only together with the bottom-right flag and everything that flag needs)
+    SAGE_REQUIRE(la.window == 0 || (c.is_causal && !la.opts.fp8_folded &&
+                                    (c.kv_lens != nullptr || (la.bottom_right && per_block && fp8 && varlen && c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL))),
+                 "SageLaunchAttr.window: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form, or "
+                 "sage_attn_fused_qblock_pv_f8_varlen with SAGE_ATTR_CAUSAL_BOTTOM_RIGHT, is_causal = 1 and SAGE_PV_ACCUM_TWO_LEVEL, only");
     // (bottom-right alignment of a packed batch: the one entry point with FP8 PV, the per-block Q quantiser and cu_seqlens)
     SAGE_REQUIRE(!la.bottom_right || (per_block && fp8 && varlen && c.is_causal && c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL),
                  "SAGE_ATTR_CAUSAL_BOTTOM_RIGHT: sage_attn_fused_qblock_pv_f8_varlen with is_causal = 1 and SAGE_PV_ACCUM_TWO_LEVEL only");

@@ -31,6 +31,8 @@ UNITS_PAIR = ("sage_attn_d128_f8q.hip", "sage_attn_d64_f8q.hip")
 UNITS_WINDOW = ("sage_attn_d128_f8w.hip", "sage_attn_d64_f8w.hip")
 # the packed route's bottom-right units, four kernels each (per-block Q fp16 / bf16, with and without the ticket loop); again a list of their own
 UNITS_PACKED_BR = ("sage_attn_d128_f8vb.hip", "sage_attn_d64_f8vb.hip")
+# ... and their windowed form (window_size= on the packed route), four kernels each
+UNITS_PACKED_WINDOW = ("sage_attn_d128_f8vbw.hip", "sage_attn_d64_f8vbw.hip")
 NEED = {"v_mfma_f32_32x32x64_f8f6f4": 19, "v_mfma_scale_f32_32x32x64_f8f6f4": 19}        # 16 passes; everything else used here: 8 passes
 NEED_DEFAULT = 11
 PASSES = {k: 16 for k in NEED}
@@ -186,7 +188,7 @@ def lint(asm_text):
 
 
 def main(argv):
-    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW + UNITS_PACKED_BR
+    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW + UNITS_PACKED_BR + UNITS_PACKED_WINDOW
     total = 0
     for u in units:
         f, n = lint(listing(u))
