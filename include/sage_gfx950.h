@@ -365,6 +365,18 @@ SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale
  *                   bit a packed causal launch keeps the reference's top-left mask (attn_qk_int8_per_block_causal_varlen.py:45-46).
  *                   Together with a non-zero `window` (above) the bit selects the packed sliding window: the one combination in which that
  *                   entry point takes a window; the bit alone is the unbounded mask.
+ *  flags bit 0x100  SAGE_ATTR_GQA_PACK: a decode-shaped call packs the query heads of a GQA group into one workgroup (Python:
+ *                   sageattn_qk_int8_pv_fp8_cuda(pack_gqa=True)).  A work item of the kernel is 128 query rows of one (batch, query head), 32 per
+ *                   wave; with Lq <= 32 three of its four waves hold no row and still run every tile, and the Hq / Hkv query heads of a kv head
+ *                   each stream the same K tiles and V images into LDS.  With the bit a work item is (batch, kv head, block of four query heads
+ *                   of the group) and wave w serves head 4 * block + w of the group over ONE shared K / V ring: B * Hkv * ceil((Hq / Hkv) / 4)
+ *                   workgroups instead of B * Hq (grid_out reports them).  No operand, and no arithmetic a row sees changes: o and lse are, bit
+ *                   for bit, those of the call without the bit, on every input -- nothing else is promised.  Waves past the group's last head
+ *                   (Hq / Hkv no multiple of 4) load and store nothing.  Always the ordinary launch (launch_ws is ignored).  Honoured by
+ *                   sage_attn_fused_q_pv_f8_kvlens alone -- is_causal = 0 or 1, with or without q_start / window -- and only with Lq <= 32,
+ *                   Hq / Hkv >= 2 and the exact score form; that entry with Lq > 32, Hq = Hkv or SAGE_ATTR_FP8_FOLDED_SCORES, and every other
+ *                   sage_attn_* entry point, refuses the bit (SAGE_EINVAL).  A call without per-sample lengths takes the same entry with kv_lens
+ *                   filled with Lk.  The reference has no counterpart (one thread block per query head, qk_int_sv_f8_cuda_sm89.cuh:720-738).
  */
 typedef struct SageLaunchAttr {
     uint32_t struct_bytes;
@@ -394,6 +406,8 @@ typedef struct SageLaunchAttr {
 #define SAGE_ATTR_FORCE_PERSISTENT 2u
 /* packed batches: the causal mask aligned bottom-right per sequence (the attribute block above: flags bit 8) */
 #define SAGE_ATTR_CAUSAL_BOTTOM_RIGHT 8u
+/* decode-shaped kv_lens calls: a GQA group's query heads four to a workgroup (the attribute block above: flags bit 0x100; 0x10 - 0x80 stay unknown) */
+#define SAGE_ATTR_GQA_PACK 0x100u
 SAGE_API int64_t sage_attn_launch_ws_bytes(void);
 
 /*

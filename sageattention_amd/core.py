@@ -151,13 +151,14 @@ def _v_rows_wanted(q, k, v, tensor_layout: str, is_causal: bool, override) -> bo
 
 @torch.compiler.disable
 def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, sm_scale_log2, return_lse, v_mean=None, folded_scores=False,
-                  v_rows=False, kv_lens=None, q_start=None, window=0):
+                  v_rows=False, kv_lens=None, q_start=None, window=0, gqa_pack=False):
     """FP8-PV two-level attention with the per-thread Q quantisation done in the kernel prologue
     (``sage_attn_fused_q_pv_f8``): bit-identical to ``per_thread_int8`` + the attention op, one launch and
     3 B/element of HBM traffic less.  ``v_rows`` (FP16 PV): ``v_image`` is the fp16 V tensor itself, read in place.
     ``kv_lens`` (FP8 PV, int32 [B] on the device): a key length per sample (``sage_attn_fused_q_pv_f8_kvlens``); ``q_start`` (with
     ``kv_lens``, causal; int32 [B] on the device): a query offset per sample (``SageLaunchAttr.q_start``); ``window`` (with ``kv_lens``,
-    causal; a Python int): the number of keys a row sees up to and including its diagonal, 0 = unbounded (``SageLaunchAttr.window``)."""
+    causal; a Python int): the number of keys a row sees up to and including its diagonal, 0 = unbounded (``SageLaunchAttr.window``);
+    ``gqa_pack`` (with ``kv_lens``, ``Lq <= 32``, ``Hq / Hkv >= 2``): the query heads of a GQA group four to a workgroup (``SAGE_ATTR_GQA_PACK``)."""
     B, Hq, Lq, D, q_sb, q_sh, q_sl = _dims(q, tensor_layout)
     _, Hkv, Lk, _, k_sb, k_sh, k_sl = _dims(k_int8, tensor_layout)
     assert Hq % Hkv == 0, "num_qo_heads must be divisible by num_kv_heads"
@@ -167,7 +168,9 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
     code = _cabi.DTYPE_F16 if q.dtype == torch.float16 else _cabi.DTYPE_BF16
     # (a large non-causal call: persistent launch; FP8 PV: the score form)
     assert (q_start is None and not window) or (kv_lens is not None and is_causal)
-    attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None, q_start=q_start, window=window)
+    assert not gqa_pack or kv_lens is not None
+    attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None, q_start=q_start, window=window,
+                         gqa_pack=gqa_pack)
     if v_rows:                     # FP16 PV on fp16 inputs: V rows in place, no tile image (sage_attn_fused_q_pv_f16_vrows)
         assert v_scale is None and v_mean is None
         _, _, _, _, v_sb, v_sh, v_sl = _dims(v_image, tensor_layout)
@@ -382,6 +385,24 @@ def _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran: str, pv_accum_dtype:
     return True
 
 
+def _pack_gqa_args(pack_gqa, q, k, tensor_layout, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs) -> bool:
+    """Whether ``pack_gqa`` asks for the packed decode launch; its argument errors (checked before any work, on any device).  The launch is one
+    of the ``kv_lens`` kernel family, so that route's restrictions hold (:func:`_offset_route_restrictions`), worded for this keyword; it exists
+    for decode shapes -- no more query rows than one wave's slab holds -- and needs a GQA group to pack."""
+    if pack_gqa is None or pack_gqa is False:
+        return False
+    if pack_gqa is not True:
+        raise ValueError(f"pack_gqa must be None, False or True (got {pack_gqa!r})")
+    _offset_route_restrictions("pack_gqa", qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
+    Hq, Lq = _dims(q, tensor_layout)[1:3]
+    Hkv = _dims(k, tensor_layout)[1]
+    if Lq > 32:
+        raise ValueError(f"pack_gqa needs qo_len <= 32 (got {Lq}): a query head's rows are one wave's 32-row slab")
+    if Hq == Hkv:
+        raise ValueError(f"pack_gqa needs num_qo_heads / num_kv_heads >= 2 (got {Hq} / {Hkv}): there is no GQA group to pack")
+    return True
+
+
 def _window_args(window_size, is_causal: bool, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs):
     """``window_size=(left, right)`` (FlashAttention's convention, -1 = unbounded on that side) as ``(W, r)``: a row sees ``W`` keys up to and
     including its diagonal (0: unbounded), the diagonal shifted right by ``r`` keys; None when there is no window.  Its argument errors are
@@ -542,7 +563,7 @@ def _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
 # ------------------------------------------------------------------------------------------------
 def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND", is_causal: bool = False,
              sm_scale: Optional[float] = None, return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, q_start=None,
-             causal_align: str = "top_left", window_size=None, **kwargs: Any):
+             causal_align: str = "top_left", window_size=None, pack_gqa=None, **kwargs: Any):
     """Select the implementation for the device, as the reference does per compute capability
     (core.py:143-157).  On gfx950 that is INT8 QK^T + FP8 PV with two-level FP32 accumulation
     (the reference's sm90 choice, ``pv_accum_dtype="fp32+fp32"``).  Extra SDPA-style kwargs
@@ -550,7 +571,8 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
     reference ignores them.  ``kv_lens`` (gfx950 extension, int32 / int64 ``[B]`` on q's device): a key length per sample of a right-padded
     batch; ``q_start`` (int, or int32 / int64 ``[B]``) / ``causal_align="bottom_right"``: where the causal diagonal of each sample lies -- row i
     attends to key j iff ``j <= q_start[b] + i`` and ``j < len_b``; ``window_size=(left, right)``: a sliding window in FlashAttention's
-    convention.  See :func:`sageattn_qk_int8_pv_fp8_cuda`."""
+    convention; ``pack_gqa=True``: a decode-shaped call (``qo_len <= 32``) runs a GQA group's query heads four to a workgroup, same bits.
+    See :func:`sageattn_qk_int8_pv_fp8_cuda`."""
     _check_shapes(q, k, v, tensor_layout)      # (again in the entry point called below: this one is in front of the device query)
     if torch.compiler.is_compiling():      # the device query is not traceable; the opaque op checks the device when it runs
         if kv_lens is not None:            # (the compiled op has no such argument: a compiled call that ignored the lengths would be a trap)
@@ -559,6 +581,8 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
             raise ValueError("q_start / causal_align are not supported under torch.compile")
         if window_size is not None:
             raise ValueError("window_size is not supported under torch.compile")
+        if pack_gqa:
+            raise ValueError("pack_gqa is not supported under torch.compile")
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32")
     arch = get_gcn_arch(q.device) if q.is_cuda else "cpu"
@@ -567,7 +591,7 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32", split_kv=kwargs.get("split_kv"),
                                             fused_prepass=kwargs.get("fused_prepass"), fp8_scores=kwargs.get("fp8_scores"),
                                             split_kv_exact=kwargs.get("split_kv_exact", False), kv_lens=kv_lens,
-                                            q_start=q_start, causal_align=causal_align, window_size=window_size)
+                                            q_start=q_start, causal_align=causal_align, window_size=window_size, pack_gqa=pack_gqa)
     raise ValueError(f"Unsupported architecture: {arch} (sageattention_amd targets gfx950 / MI355X only)")
 
 
@@ -1025,7 +1049,7 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
                                  qk_quant_gran: str = "per_thread", sm_scale: Optional[float] = None,
                                  pv_accum_dtype: str = "fp32+fp16", smooth_k: bool = True, smooth_v: bool = False,
                                  return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, q_start=None,
-                                 causal_align: str = "top_left", window_size=None, **kwargs: Any):
+                                 causal_align: str = "top_left", window_size=None, pack_gqa=None, **kwargs: Any):
     """INT8 QK^T + FP8 (e4m3) PV (reference core.py:636-826).  "fp32+fp32" and "fp32+fp16" both
     run the two-level kernel with an FP32 tile buffer (gfx950's FP8 MFMA only writes FP32, so V
     keeps the full ``scale_max=448``; the reference's 2.25 is an FP16-accumulator artefact,
@@ -1074,7 +1098,17 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     images in front of the first one are never read.  The K mean, the K scale groups and the V scales are those of the call without the
     window on the same ``kv_lens`` (the window masks scores, it does not change operands).  A row whose window holds no key -- in front of
     key 0, or wholly behind ``len_b`` -- gives ``o = +0``, ``lse = -inf``.  A window that cuts no row (``left >= kv_len + qo_len``) gives
-    the bits of the call without it.  The restrictions are ``q_start``'s and raise ValueError naming ``window_size``."""
+    the bits of the call without it.  The restrictions are ``q_start``'s and raise ValueError naming ``window_size``.
+
+    ``pack_gqa`` (gfx950 extension; ``None`` / ``False``: today's launch): ``True`` packs the query heads of a GQA group into one workgroup for
+    a decode-shaped call, ``qo_len <= 32`` and ``num_qo_heads / num_kv_heads >= 2``.  The kernel's work item is 128 query rows of one query
+    head, 32 per wave: with at most 32 rows three of four waves hold none and still run every tile, and each query head of a group streams
+    the same K tiles and V images.  Packed, a workgroup serves four query heads of one kv head, one wave each, over one shared K / V ring:
+    ``B * Hkv * ceil(group / 4)`` workgroups instead of ``B * Hq``.  ``o`` and ``lse`` are, bit for bit, those of the same call with
+    ``pack_gqa=False`` -- on every input, and nothing else is promised.  It combines with ``kv_lens``, ``q_start`` / ``causal_align`` and
+    ``window_size`` in every combination they take; alone, the call takes the ``kv_lens`` attention entry with lengths filled with ``kv_len``
+    behind the plain pre-pass.  The route's restrictions are ``kv_lens``'s and raise ValueError naming ``pack_gqa``, as do ``qo_len > 32``,
+    ``num_qo_heads == num_kv_heads`` and use under torch.compile."""
     if torch.compiler.is_compiling():
         if kv_lens is not None:
             raise ValueError("kv_lens is not supported under torch.compile (the compiled op takes the default routes)")
@@ -1082,8 +1116,11 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
             raise ValueError("q_start / causal_align are not supported under torch.compile (the compiled op takes the default routes)")
         if window_size is not None:
             raise ValueError("window_size is not supported under torch.compile (the compiled op takes the default routes)")
+        if pack_gqa:
+            raise ValueError("pack_gqa is not supported under torch.compile (the compiled op takes the default routes)")
         return _compiled_call("fp8", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse, kwargs)
     _check_shapes(q, k, v, tensor_layout)
+    gqa_pack = _pack_gqa_args(pack_gqa, q, k, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)      # (first: its errors name it)
     with_lens = _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     win = _window_args(window_size, is_causal, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     window, shift = win if win is not None else (0, 0)
@@ -1118,7 +1155,7 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
         lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
                                                                               return_lse, False, kv_lens=lens)
         o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, q_start=start, window=window)
+                               kv_lens=lens, q_start=start, window=window, gqa_pack=gqa_pack)
         return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
     if with_start:
         # query offsets without key lengths: the plain pre-pass (the one-launch route included) and the same attention entry with lengths
@@ -1130,7 +1167,16 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
         lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
                                                                               return_lse, fused)
         o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, q_start=start, window=window)
+                               kv_lens=lens, q_start=start, window=window, gqa_pack=gqa_pack)
+        return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
+    if gqa_pack:
+        # packed GQA groups without lengths or offsets: the plain pre-pass and the kv_lens attention entry with lengths filled with kv_len, as above
+        B_ = _dims(q, tensor_layout)[0]
+        lens = torch.full((B_,), _dims(k, tensor_layout)[2], dtype=torch.int32, device=q.device)
+        lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
+                                                                              return_lse, fused)
+        o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
+                               kv_lens=lens, gqa_pack=True)
         return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
     if fuse_q:
         # default route: Q is quantised inside the attention kernel (same bits, no INT8 copy of Q in HBM).

@@ -33,6 +33,8 @@ static int plan_grid(AttnParams &q, const AttnVariant &v)
     q.order_fold = 0;
     q.order_left = 0;
     const int nheads = q.B * q.Hq;
+    // packed GQA groups (decode-shaped, one query block): (batch, kv head, block of four query heads) in head-major order
+    if (v.gqa_pack) return q.B * q.Hkv * ((q.group + 3) / 4);
     if (q.cu_q != nullptr && q.work_items != nullptr)             // varlen, device-built work list: bound of the dense-style grid over it
         return 8 * ((q.Hq & 7) * ((q.items_bound + 7) / 8) + (q.Hq >> 3) * q.items_bound);
     if (q.cu_q != nullptr) return ((q.B * q.Hkv + 7) / 8) * 8 * q.group * q.nqblk;   // varlen: whole rounds of 8 (sequence, kv-head) units
@@ -70,6 +72,9 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
         (v.window > 0 && (!v.causal || (long)p.Lq + p.Lk > (1L << 29) || (!v.kv_lens && !(varlen && v.bottom_right))))) return false;
     // bottom-right alignment of a packed batch: causal, FP8 PV, per-block Q, two-level, the exact score form
     if (v.bottom_right && (!varlen || !v.causal || !v.pv_fp8 || !per_block || !v.two_level || o.fp8_folded)) return false;
+    // packed GQA groups: the kv_lens family (above: fused per-thread Q, FP8 PV, the exact score form, dense, no split), a group to pack and
+    // no more query rows than one wave's slab holds
+    if (v.gqa_pack && (!v.kv_lens || p.Lq > 32 || p.group < 2 || p.nqblk != 1)) return false;
     return true;
 }
 
@@ -80,9 +85,10 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     if (o.grid_out != nullptr) *o.grid_out = 0;
     if (nwork <= 0) return hipSuccess;
     if (!route_exists(p, v, o)) return hipErrorInvalidValue;
-    // the instantiation unit of (head_dim, PV format, FP8 score form, seeded / kv_lens / q_start / window / packed FP8 with the per-block Q quantiser, top-left, bottom-right or bottom-right with a window)
+    // the instantiation unit of (head_dim, PV format, FP8 score form, seeded / kv_lens / q_start / window / packed GQA groups / packed FP8 with the per-block Q quantiser, top-left, bottom-right or bottom-right with a window)
     const bool d128 = v.head_dim == 128;
     if (v.seeded) return d128 ? launch_attn_f8_seeded<128>(p, v, nwork, o) : launch_attn_f8_seeded<64>(p, v, nwork, o);
+    if (v.gqa_pack) return d128 ? launch_attn_f8_gpack<128>(p, v, nwork, o) : launch_attn_f8_gpack<64>(p, v, nwork, o);
     if (v.window > 0 && v.kv_lens) return d128 ? launch_attn_f8_window<128>(p, v, nwork, o) : launch_attn_f8_window<64>(p, v, nwork, o);
     if (v.q_start) return d128 ? launch_attn_f8_qstart<128>(p, v, nwork, o) : launch_attn_f8_qstart<64>(p, v, nwork, o);
     if (v.kv_lens) return d128 ? launch_attn_f8_kvlens<128>(p, v, nwork, o) : launch_attn_f8_kvlens<64>(p, v, nwork, o);

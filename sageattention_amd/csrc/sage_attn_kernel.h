@@ -201,8 +201,18 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // above, W = p.window, the same head tiles, second priming and masks; only the shift of the item's first key is written for the packed layouts
 // (V images and per-block k scales: one per 64-key tile, stride Hkv).  With the ticket loop (CPERS) the next item's ticket is requested behind
 // the LAST tile of the item whichever run that is -- the request stands behind the remainder loop, not inside a run.
-template <int D, bool PV_FP8, bool CAUSAL, bool KTHREAD, bool TWO_LEVEL, int NH, int MASK = 0, int QF = 0, bool SFOLD = true, bool CPERS = false,
-          bool VROWS = false, bool SEED = false, bool WINDOW = false, bool QSTART = false, bool KVLEN = false>
+// GPACK (a KVLEN kernel, with or without QSTART / WINDOW; units sage_attn_d{128,64}_f8g.hip; stands behind QF in the parameter list, in front of every
+// flag older kernels' names end with): a decode-shaped call (p.Lq <= 32) packs the query heads of a GQA group four to a workgroup.  A work
+// item is (batch b, kv head hk, group block gb); wave w serves query head hk * group + 4 gb + w and takes rows 0 .. Lq - 1 of that head as the
+// rows of its 32-row slab (row0 = 0 in every wave).  The head index and what follows from it alone -- q_off, o_off, the lse index -- are
+// per wave (wave-uniform: SGPRs); everything else is what block 0 of the unpacked call forms from qblk = 0: the loop bounds, the head tiles,
+// diag_ok / tail_ok, the tile requests, the barriers, the length / offset / window loads.  So wave w runs, instruction for instruction and on
+// the same LDS contents, what wave 0 of its head's unpacked work item runs: the same bits.  A wave past the group's last
+// head (4 gb + w >= group) is idle: it takes part in the tile requests and every barrier, loads no Q row (zeros, as rows past Lq are) and
+// stores nothing; its head index is the group's first, so that no address is formed from a head past Hq.  No ticket loop: a decode launch
+// does not reach twelve rounds of workgroups.
+template <int D, bool PV_FP8, bool CAUSAL, bool KTHREAD, bool TWO_LEVEL, int NH, int MASK = 0, int QF = 0, bool GPACK = false, bool SFOLD = true,
+          bool CPERS = false, bool VROWS = false, bool SEED = false, bool WINDOW = false, bool QSTART = false, bool KVLEN = false>
 __global__ void __launch_bounds__(256, SAGE_MIN_WAVES_K(D, MASK, WINDOW && QSTART && !KVLEN && CPERS))
 sage_attn_kernel(const AttnParams p_arg)
 {
@@ -235,6 +245,7 @@ sage_attn_kernel(const AttnParams p_arg)
     static_assert(!QSTART || (CAUSAL && (KVLEN || (PV_FP8 && !KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && QF >= 3 && !VROWS && !SEED))),
                   "query offsets: the causal kv_lens kernels (dense, p.cu_qs), or a packed launch's bottom-right alignment (FP8 PV, per-block Q, two-level; with or without a window)");
     static_assert(!WINDOW || QSTART, "the sliding window: the q_start kernels");
+    static_assert(!GPACK || KVLEN, "packed GQA groups: the kv_lens kernels (dense, p.Lq <= 32)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     // (wave index in an SGPR, lane index from v_mbcnt wherever it is needed: nothing derived from threadIdx.x has to stay in a VGPR across
@@ -256,7 +267,7 @@ sage_attn_kernel(const AttnParams p_arg)
     // (round 5: the packed / varlen route's CAUSAL launches over the device-built work list take the route too -- +2.2 ... 2.9 % at C4 -- through
     //  instantiations of their own (CPERS); dense causal launches lose 0.1 ... 7.5 % with tickets and the loop's mere presence costs the dense
     //  Triton-API causal kernel 1.3 %, so their instantiations stay without it: profiles/r5_pers_causal_probe.txt, r5_run_c_qf_pers_ab.txt)
-    constexpr bool PERS_OK = (!CAUSAL || CPERS) && MASK == 0;
+    constexpr bool PERS_OK = (!CAUSAL || CPERS) && MASK == 0 && !GPACK;
     const bool pers = PERS_OK && p.sched != nullptr;
     __shared__ int s_ticket[2];                 // (two slots, alternating: a wave may still be reading the previous ticket when wave 0 posts the next)
     int tpar = 0;
@@ -341,7 +352,21 @@ sage_attn_kernel(const AttnParams p_arg)
     // ---- work item: XCD-aware, heavy-first --------------------------------------------------
     const int nqblk = p.nqblk;
     int b, h, hk, qblk;
-    if (p.cu_q != nullptr && p.work_items != nullptr) {
+    [[maybe_unused]] bool idle = false;       // (GPACK) wave-uniform: this wave's head lies past the group's last one
+    if constexpr (GPACK) {
+        // the grid is B * Hkv * ceil(group / 4) items in head-major order, one contiguous run per XCD as below: the blocks of a kv head -- and
+        // the kv heads of a sample -- stream K / V through one L2
+        const int ngb = (p.group + 3) >> 2;
+        int u, qrank;
+        const WorkOrder wo = {0, 0, 0};
+        if (!work_item(wo, bid, (int)gridDim.x, p.B * p.Hkv * ngb, 1, u, qrank)) break;
+        const int bk = u / ngb, hw = 4 * (u - bk * ngb) + wave_s;
+        b = bk / p.Hkv;
+        hk = bk - b * p.Hkv;
+        idle = hw >= p.group;
+        h = hk * p.group + (idle ? 0 : hw);
+        qblk = 0;
+    } else if (p.cu_q != nullptr && p.work_items != nullptr) {
         // varlen with the device-built work list (sage_varlen_plan): the query blocks of all sequences are one item list per query head,
         // heaviest first, and the launch is a dense launch over Hq heads of `nitems` items each (sage_work_order.h) -- whole GQA groups
         // stay on one XCD, every workgroup has an item (the grid is sized by a host-known bound of nitems; the few past it exit here)
@@ -483,7 +508,9 @@ sage_attn_kernel(const AttnParams p_arg)
     }
 
     SAGE_TSTAMP(1);
-    const int row0 = qblk * BLKQ + wave * 32;        // first query row of this wave
+    const int row0 = GPACK ? 0 : qblk * BLKQ + wave * 32;        // first query row of this wave (GPACK: every wave holds rows 0 .. of its own head)
+    int Lq_w = Lq;                                   // the rows this wave loads and stores: Lq, but (GPACK) none in an idle wave
+    if constexpr (GPACK) Lq_w = idle ? 0 : Lq;
     int my_row = row0 + n;                           // (re-derived behind the pipelined loops, see there)
     // causal mask in the chunk's key coordinates (split-KV: this workgroup sees keys kchunk0 .. kchunk0 + Lk - 1 as 0 .. Lk - 1):
     // key <= row  <=>  local key <= row - kchunk0
@@ -681,7 +708,7 @@ sage_attn_kernel(const AttnParams p_arg)
     // tiles' round trip ran one after the other in every workgroup's prologue.
     if constexpr (QF == 0) {
         const int8_t *qrow = reinterpret_cast<const int8_t *>(p.q) + q_off + (long)my_row * p.q_sl;
-        const bool ok = my_row < Lq;
+        const bool ok = my_row < Lq_w;
 #pragma unroll
         for (int ks = 0; ks < C::KSTEPS; ks++) {
             v4i z = {0, 0, 0, 0};
@@ -704,7 +731,7 @@ sage_attn_kernel(const AttnParams p_arg)
         constexpr bool QBLOCK = QF >= 3;
         const float premul = QBLOCK ? p.q_premul : 1.0f;
         const uint16_t *qrow = reinterpret_cast<const uint16_t *>(p.q) + q_off + (long)my_row * p.q_sl;
-        const bool ok = my_row < Lq;
+        const bool ok = my_row < Lq_w;
         float x[C::KSTEPS][16];
         float amax = 0.0f;
 #pragma unroll
@@ -1115,7 +1142,7 @@ sage_attn_kernel(const AttnParams p_arg)
     __builtin_amdgcn_s_setreg(kHwregModeFp16Ovfl, 0);
     const float l_tot = pair_sum(l_run);
     const float inv = l_tot > 0.0f ? __builtin_amdgcn_rcpf(l_tot) : 0.0f;
-    if (p.lse != nullptr && g == 0 && my_row < Lq) {
+    if (p.lse != nullptr && g == 0 && my_row < Lq_w) {
         long lidx = (p.cu_q != nullptr) ? ((long)h * p.lse_sh + p.cu_q[b] + my_row)
                                         : ((long)b * p.Hq + h) * (long)p.Lq + my_row;
         p.lse[lidx] = __builtin_amdgcn_logf(l_tot) + m_run;   // v_log_f32 is log2
@@ -1193,7 +1220,7 @@ sage_attn_kernel(const AttnParams p_arg)
             const int r = pass * RPP + lane_g / LPR, Q = lane_g % LPR;
             const v4u val = *reinterpret_cast<const v4u *>(obuf + r * (D * 2) + (Q ^ (r & 7)) * 16);
             const int grow = row0 + r;
-            if (grow < Lq) *reinterpret_cast<v4u *>(obase + 2 * ((long)grow * p.o_sl) + Q * 16) = val;
+            if (grow < Lq_w) *reinterpret_cast<v4u *>(obase + 2 * ((long)grow * p.o_sl) + Q * 16) = val;
         }
     }
 #if SAGE_ATTN_TRACE

@@ -92,14 +92,14 @@ hipError_t launch_attn_part(const AttnParams &p, const AttnVariant &v, int nwork
     if (p.v_rows != 0) {                   // V rows read in place (fp16 V, FP16 PV, dense): fused Q quantisation per thread group / per block, or INT8 q
         if constexpr (!PV_FP8) {
 #define SAGE_VR(C_) \
-            if (v.causal == C_ && v.qf == 1) return launch_kernel<sage_attn_kernel<D, false, C_, true, false, NH, 0, 1, true, false, true>>(C::LDS_BYTES, p, nwork, l, pers); \
-            if (v.causal == C_ && v.qf == 3) return launch_kernel<sage_attn_kernel<D, false, C_, false, true, NH, 0, 3, true, false, true>>(C::LDS_BYTES, p, nwork, l, pers);
+            if (v.causal == C_ && v.qf == 1) return launch_kernel<sage_attn_kernel<D, false, C_, true, false, NH, 0, 1, false, true, false, true>>(C::LDS_BYTES, p, nwork, l, pers); \
+            if (v.causal == C_ && v.qf == 3) return launch_kernel<sage_attn_kernel<D, false, C_, false, true, NH, 0, 3, false, true, false, true>>(C::LDS_BYTES, p, nwork, l, pers);
             SAGE_VR(false) SAGE_VR(true)
 #undef SAGE_VR
             // INT8 q with its scales (ABI 21, sage_attn_qk_int8_pv_f16_vrows): the reference's native FP16-PV ops as they are -- query / key INT8,
             // value fp16 rows (pybind_sm80.cpp:21-27; the Triton forward, attn_qk_int8_per_block.py:130) -- in every k-scale grouping and both kernel forms
 #define SAGE_VR0(C_, K_, T_) if (v.qf == 0 && v.causal == C_ && v.kthread == K_ && v.two_level == T_) \
-            return launch_kernel<sage_attn_kernel<D, false, C_, K_, T_, NH, 0, 0, true, false, true>>(C::LDS_BYTES, p, nwork, l, pers);
+            return launch_kernel<sage_attn_kernel<D, false, C_, K_, T_, NH, 0, 0, false, true, false, true>>(C::LDS_BYTES, p, nwork, l, pers);
             SAGE_VR0(false, false, false) SAGE_VR0(false, false, true) SAGE_VR0(true, false, false) SAGE_VR0(true, false, true)
             SAGE_VR0(false, true, false)  SAGE_VR0(false, true, true)  SAGE_VR0(true, true, false)  SAGE_VR0(true, true, true)
 #undef SAGE_VR0
@@ -107,7 +107,7 @@ hipError_t launch_attn_part(const AttnParams &p, const AttnVariant &v, int nwork
         return hipErrorInvalidValue;
     }
     if (v.qf == 1 || v.qf == 2) {      // per-thread groups quantised in the prologue; FP8 PV: two-level, FP16 PV: straight FP32 accumulation
-#define SAGE_FQ(C_, F_) if (v.causal == C_ && v.qf == F_) return launch_kernel<sage_attn_kernel<D, PV_FP8, C_, true, PV_FP8, NH, 0, F_, SFOLD>>(C::LDS_BYTES, p, nwork, l, pers);
+#define SAGE_FQ(C_, F_) if (v.causal == C_ && v.qf == F_) return launch_kernel<sage_attn_kernel<D, PV_FP8, C_, true, PV_FP8, NH, 0, F_, false, SFOLD>>(C::LDS_BYTES, p, nwork, l, pers);
         SAGE_FQ(false, 1) SAGE_FQ(false, 2) SAGE_FQ(true, 1) SAGE_FQ(true, 2)
 #undef SAGE_FQ
         return hipErrorInvalidValue;
@@ -115,8 +115,8 @@ hipError_t launch_attn_part(const AttnParams &p, const AttnVariant &v, int nwork
     if (v.qf == 3 || v.qf == 4) {      // per-block Q in the prologue: the Triton-named API's kernels (FP16 PV, per-block k scales), dense or varlen
         if constexpr (!PV_FP8) {
             if (v.causal && packed_list) {
-                if (v.qf == 3) return launch_kernel<sage_attn_kernel<D, false, true, false, true, NH, 0, 3, true, true>>(C::LDS_BYTES, p, nwork, l, true);
-                return launch_kernel<sage_attn_kernel<D, false, true, false, true, NH, 0, 4, true, true>>(C::LDS_BYTES, p, nwork, l, true);
+                if (v.qf == 3) return launch_kernel<sage_attn_kernel<D, false, true, false, true, NH, 0, 3, false, true, true>>(C::LDS_BYTES, p, nwork, l, true);
+                return launch_kernel<sage_attn_kernel<D, false, true, false, true, NH, 0, 4, false, true, true>>(C::LDS_BYTES, p, nwork, l, true);
             }
 #define SAGE_FQB(C_, F_) if (v.causal == C_ && v.qf == F_) return launch_kernel<sage_attn_kernel<D, false, C_, false, true, NH, 0, F_>>(C::LDS_BYTES, p, nwork, l, pers);
             SAGE_FQB(false, 3) SAGE_FQB(false, 4) SAGE_FQB(true, 3) SAGE_FQB(true, 4)
@@ -125,7 +125,7 @@ hipError_t launch_attn_part(const AttnParams &p, const AttnVariant &v, int nwork
         return hipErrorInvalidValue;
     }
 #define SAGE_CASE(C_, K_, T_) if (v.causal == C_ && v.kthread == K_ && v.two_level == T_) \
-        return launch_kernel<sage_attn_kernel<D, PV_FP8, C_, K_, T_, NH, 0, 0, SFOLD>>(C::LDS_BYTES, p, nwork, l, pers);
+        return launch_kernel<sage_attn_kernel<D, PV_FP8, C_, K_, T_, NH, 0, 0, false, SFOLD>>(C::LDS_BYTES, p, nwork, l, pers);
     SAGE_CASE(false, false, false) SAGE_CASE(false, false, true)
     SAGE_CASE(true, false, false)  SAGE_CASE(true, false, true)
     SAGE_CASE(false, true, false)  SAGE_CASE(false, true, true)
@@ -144,13 +144,13 @@ hipError_t launch_attn_f8_varlen(const AttnParams &p, const AttnVariant &v, int 
     const bool pers = !v.causal;
     if (v.causal && p.work_items != nullptr) {
 #define SAGE_F8VP(F_, T_) if (v.qf == F_ && v.two_level == T_) \
-        return launch_kernel<sage_attn_kernel<D, true, true, false, T_, 1, 0, F_, false, true>>(C::LDS_BYTES, p, nwork, l, true);
+        return launch_kernel<sage_attn_kernel<D, true, true, false, T_, 1, 0, F_, false, false, true>>(C::LDS_BYTES, p, nwork, l, true);
         SAGE_F8VP(3, false) SAGE_F8VP(3, true) SAGE_F8VP(4, false) SAGE_F8VP(4, true)
 #undef SAGE_F8VP
         return hipErrorInvalidValue;
     }
 #define SAGE_F8V(C_, F_, T_) if (v.causal == C_ && v.qf == F_ && v.two_level == T_) \
-    return launch_kernel<sage_attn_kernel<D, true, C_, false, T_, 1, 0, F_, false>>(C::LDS_BYTES, p, nwork, l, pers);
+    return launch_kernel<sage_attn_kernel<D, true, C_, false, T_, 1, 0, F_, false, false>>(C::LDS_BYTES, p, nwork, l, pers);
     SAGE_F8V(false, 3, false) SAGE_F8V(false, 3, true) SAGE_F8V(false, 4, false) SAGE_F8V(false, 4, true)
     SAGE_F8V(true, 3, false)  SAGE_F8V(true, 3, true)  SAGE_F8V(true, 4, false)  SAGE_F8V(true, 4, true)
 #undef SAGE_F8V
@@ -167,7 +167,7 @@ hipError_t launch_attn_f8_varlen_br(const AttnParams &p, const AttnVariant &v, i
     if (!v.causal || !v.two_level) return hipErrorInvalidValue;
     const bool list = p.work_items != nullptr;
 #define SAGE_F8VB(F_, P_) if (v.qf == F_ && list == P_) \
-    return launch_kernel<sage_attn_kernel<D, true, true, false, true, 1, 0, F_, false, P_, false, false, false, true, false>>(C::LDS_BYTES, p, nwork, l, P_);
+    return launch_kernel<sage_attn_kernel<D, true, true, false, true, 1, 0, F_, false, false, P_, false, false, false, true, false>>(C::LDS_BYTES, p, nwork, l, P_);
     SAGE_F8VB(3, true) SAGE_F8VB(3, false) SAGE_F8VB(4, true) SAGE_F8VB(4, false)
 #undef SAGE_F8VB
     return hipErrorInvalidValue;
@@ -182,7 +182,7 @@ hipError_t launch_attn_f8_varlen_br_window(const AttnParams &p, const AttnVarian
     if (!v.causal || !v.two_level || !v.bottom_right || v.window <= 0) return hipErrorInvalidValue;
     const bool list = p.work_items != nullptr;
 #define SAGE_F8VBW(F_, P_) if (v.qf == F_ && list == P_) \
-    return launch_kernel<sage_attn_kernel<D, true, true, false, true, 1, 0, F_, false, P_, false, false, true, true, false>>(C::LDS_BYTES, p, nwork, l, P_);
+    return launch_kernel<sage_attn_kernel<D, true, true, false, true, 1, 0, F_, false, false, P_, false, false, true, true, false>>(C::LDS_BYTES, p, nwork, l, P_);
     SAGE_F8VBW(3, true) SAGE_F8VBW(3, false) SAGE_F8VBW(4, true) SAGE_F8VBW(4, false)
 #undef SAGE_F8VBW
     return hipErrorInvalidValue;
@@ -196,7 +196,7 @@ hipError_t launch_attn_f8_seeded(const AttnParams &p, const AttnVariant &v, int 
 {
     using C = TileCfg<D, true, 1>;
 #define SAGE_F8S(C_, F_) if (v.causal == C_ && v.qf == F_) \
-    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, false);
+    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, false);
     SAGE_F8S(false, 1) SAGE_F8S(false, 2) SAGE_F8S(true, 1) SAGE_F8S(true, 2)
 #undef SAGE_F8S
     return hipErrorInvalidValue;
@@ -210,7 +210,7 @@ hipError_t launch_attn_f8_kvlens(const AttnParams &p, const AttnVariant &v, int 
 {
     using C = TileCfg<D, true, 1>;
 #define SAGE_F8K(C_, F_) if (v.causal == C_ && v.qf == F_) \
-    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, !C_);
+    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, false, false, false, false, false, false, false, true>>(C::LDS_BYTES, p, nwork, l, !C_);
     SAGE_F8K(false, 1) SAGE_F8K(false, 2) SAGE_F8K(true, 1) SAGE_F8K(true, 2)
 #undef SAGE_F8K
     return hipErrorInvalidValue;
@@ -223,7 +223,7 @@ hipError_t launch_attn_f8_qstart(const AttnParams &p, const AttnVariant &v, int 
 {
     using C = TileCfg<D, true, 1>;
 #define SAGE_F8Q(F_) if (v.causal && v.qf == F_) \
-    return launch_kernel<sage_attn_kernel<D, true, true, true, true, 1, 0, F_, false, false, false, false, false, true, true>>(C::LDS_BYTES, p, nwork, l, false);
+    return launch_kernel<sage_attn_kernel<D, true, true, true, true, 1, 0, F_, false, false, false, false, false, false, true, true>>(C::LDS_BYTES, p, nwork, l, false);
     SAGE_F8Q(1) SAGE_F8Q(2)
 #undef SAGE_F8Q
     return hipErrorInvalidValue;
@@ -236,9 +236,27 @@ hipError_t launch_attn_f8_window(const AttnParams &p, const AttnVariant &v, int 
 {
     using C = TileCfg<D, true, 1>;
 #define SAGE_F8W(F_) if (v.causal && v.qf == F_) \
-    return launch_kernel<sage_attn_kernel<D, true, true, true, true, 1, 0, F_, false, false, false, false, true, true, true>>(C::LDS_BYTES, p, nwork, l, false);
+    return launch_kernel<sage_attn_kernel<D, true, true, true, true, 1, 0, F_, false, false, false, false, false, true, true, true>>(C::LDS_BYTES, p, nwork, l, false);
     SAGE_F8W(1) SAGE_F8W(2)
 #undef SAGE_F8W
+    return hipErrorInvalidValue;
+}
+
+// Packed GQA groups for decode-shaped calls (sage_attn_kernel's GPACK: p.Lq <= 32, the query heads of a group four to a workgroup, one wave
+// each over one shared K / V ring): the kv_lens family's four members -- non-causal and causal lengths, query offsets, a window on top of
+// them -- in units of their own, sage_attn_d{128,64}_f8g.hip.  The ordinary launch alone: the ticket loop is not compiled into these kernels
+// (a decode launch of twelve rounds of workgroups does not occur, and the loop costs registers wherever it stands).
+template <int D>
+hipError_t launch_attn_f8_gpack(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
+{
+    using C = TileCfg<D, true, 1>;
+    if (!v.gqa_pack || !v.kv_lens) return hipErrorInvalidValue;
+    const bool window = v.window > 0, offsets = v.q_start || window;
+#define SAGE_F8G(C_, F_, W_, Q_) if (v.causal == C_ && v.qf == F_ && window == W_ && offsets == Q_) \
+    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, true, false, false, false, false, W_, Q_, true>>(C::LDS_BYTES, p, nwork, l, false);
+    SAGE_F8G(false, 1, false, false) SAGE_F8G(false, 2, false, false) SAGE_F8G(true, 1, false, false) SAGE_F8G(true, 2, false, false)
+    SAGE_F8G(true, 1, false, true)   SAGE_F8G(true, 2, false, true)   SAGE_F8G(true, 1, true, true)   SAGE_F8G(true, 2, true, true)
+#undef SAGE_F8G
     return hipErrorInvalidValue;
 }
 

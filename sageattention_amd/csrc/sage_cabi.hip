@@ -47,7 +47,7 @@ inline bool multiples_of(int n, const Strides &s) { return multiples_of(n, s.sb,
 struct MaskArg { const void *ptr; int kind; int64_t sb, sh, sq, sk; };
 
 // SageLaunchAttr (nullable) -> the launch workspace and the launcher's options; the attributes are arguments of THIS call, nothing is kept
-struct LaunchAttr { unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; const int32_t *q_start; int window; bool bottom_right; };
+struct LaunchAttr { unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; const int32_t *q_start; int window; bool bottom_right, gqa_pack; };
 int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAttr &out)
 {
     out.ws = nullptr;
@@ -57,6 +57,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     out.q_start = nullptr;
     out.window = 0;
     out.bottom_right = false;
+    out.gqa_pack = false;
     if (attr == nullptr) return SAGE_OK;
     SageLaunchAttr a{};
     // struct_bytes is what the CALLER's struct holds: fewer bytes than ours (an older caller) are read as far as they go, more (a newer
@@ -67,7 +68,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     if (n < offsetof(SageLaunchAttr, q_start) + sizeof(a.q_start)) a.q_start = nullptr;      // (a struct that ends inside the field does not have it)
     if (n < offsetof(SageLaunchAttr, window) + sizeof(a.window)) a.window = 0;
     SAGE_REQUIRE(a.window >= 0, "SageLaunchAttr.window = %d: the number of keys a row sees up to its diagonal, 0 = unbounded", a.window);
-    SAGE_REQUIRE((a.flags & ~(SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES | SAGE_ATTR_FORCE_PERSISTENT | SAGE_ATTR_CAUSAL_BOTTOM_RIGHT)) == 0, "unknown SageLaunchAttr.flags 0x%x", a.flags);
+    SAGE_REQUIRE((a.flags & ~(SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES | SAGE_ATTR_FORCE_PERSISTENT | SAGE_ATTR_CAUSAL_BOTTOM_RIGHT | SAGE_ATTR_GQA_PACK)) == 0, "unknown SageLaunchAttr.flags 0x%x", a.flags);
     SAGE_REQUIRE((a.flags & (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES)) != (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES),
                  "SageLaunchAttr.flags asks for both FP8 score forms");
     SAGE_REQUIRE(a.launch_ws == nullptr || (a.launch_ws_bytes >= sage::kAttnSchedBytes && (reinterpret_cast<uintptr_t>(a.launch_ws) & 127u) == 0),
@@ -83,6 +84,7 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     out.q_start = a.q_start;
     out.window = a.window;
     out.bottom_right = (a.flags & SAGE_ATTR_CAUSAL_BOTTOM_RIGHT) != 0;
+    out.gqa_pack = (a.flags & SAGE_ATTR_GQA_PACK) != 0;
     return SAGE_OK;
 }
 
@@ -188,6 +190,9 @@ int attn_run(const AttnCall &c)
     // (bottom-right alignment of a packed batch: the one entry point with FP8 PV, the per-block Q quantiser and cu_seqlens)
     SAGE_REQUIRE(!la.bottom_right || (per_block && fp8 && varlen && c.is_causal && c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL),
                  "SAGE_ATTR_CAUSAL_BOTTOM_RIGHT: sage_attn_fused_qblock_pv_f8_varlen with is_causal = 1 and SAGE_PV_ACCUM_TWO_LEVEL only");
+    // (packed GQA groups: the kv_lens entry, decode-shaped, a group to pack)
+    SAGE_REQUIRE(!la.gqa_pack || (c.kv_lens != nullptr && !la.opts.fp8_folded && c.Lq <= 32 && c.Hkv > 0 && c.Hq % c.Hkv == 0 && c.Hq / c.Hkv >= 2),
+                 "SAGE_ATTR_GQA_PACK: sage_attn_fused_q_pv_f8_kvlens with Lq <= 32, Hq / Hkv >= 2 and the exact score form only");
     SAGE_REQUIRE(c.kv_lens == nullptr || (per_thread && fp8 && !split && c.v_rows == nullptr && !la.opts.fp8_folded),
                  "kv_lens: FP8 PV, the exact score form (SAGE_ATTR_FP8_FOLDED_SCORES), no split");
     SAGE_REQUIRE(!(per_block && varlen) || c.cu_q != nullptr, "varlen needs cu_seqlens_q");
@@ -242,6 +247,7 @@ int attn_run(const AttnCall &c)
     if (la.q_start != nullptr) { p.cu_qs = la.q_start; v.q_start = true; }
     p.window = v.window = la.window;
     v.bottom_right = la.bottom_right;
+    v.gqa_pack = la.gqa_pack;
     v.head_dim = c.D; v.pv_fp8 = fp8; v.causal = c.is_causal != 0;
     // FP16 PV: the kernel's TWO_LEVEL parameter selects the Triton kernel form (true) or the CUDA kernel form (false)
     v.two_level = fp8 ? c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : c.pv_accum == SAGE_PV_ACCUM_TRITON;
@@ -1141,6 +1147,7 @@ SAGE_API int sage_attn_fused_q_pv_f8_split_exact(const void *q, const int8_t *k,
     SAGE_REQUIRE(la.q_start == nullptr, "SageLaunchAttr.q_start: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
     SAGE_REQUIRE(la.window == 0, "SageLaunchAttr.window: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
     SAGE_REQUIRE(!la.bottom_right, "SAGE_ATTR_CAUSAL_BOTTOM_RIGHT: sage_attn_fused_qblock_pv_f8_varlen with is_causal = 1 and SAGE_PV_ACCUM_TWO_LEVEL only");
+    SAGE_REQUIRE(!la.gqa_pack, "SAGE_ATTR_GQA_PACK: sage_attn_fused_q_pv_f8_kvlens with Lq <= 32, Hq / Hkv >= 2 and the exact score form only");
     if (const int rc = split_exact_check(q, k, k_scale, B, Hq, Hkv, kv_split, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, q_dtype)) return rc;
     SAGE_REQUIRE(v_image && v_scale && o_part && lse_part && chunk_max, "null tensor pointer");
     SAGE_REQUIRE(tail == 0 || tail == 1, "tail must be 0 (the whole chunks) or 1 (the ragged tail), got %d", tail);

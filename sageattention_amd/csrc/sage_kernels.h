@@ -72,7 +72,7 @@ struct AttnLaunchOpts {
     bool force_persistent;   // take the ticket queues whatever the number of rounds (tests; AttnParams::sched must be set)
     int *grid_out;           // nullable (host): receives the number of workgroups launched
 };
-// Which member of the kernel family a launch takes: the instantiation unit (head_dim, pv_fp8, AttnLaunchOpts::fp8_folded, seeded, kv_lens, q_start; the
+// Which member of the kernel family a launch takes: the instantiation unit (head_dim, pv_fp8, AttnLaunchOpts::fp8_folded, seeded, kv_lens, q_start, window, gqa_pack; the
 // per-block fused Q quantiser with FP8 PV has units of its own) and everything else the template arguments of sage_attn_kernel encode.
 //   INT8 q (qf 0)            every field below; a mask: FP16 PV, per-block scales, non-causal, the Triton kernel form
 //   fused per-thread Q (1/2) dense; kthread, two_level = pv_fp8 (FP16 PV: straight FP32 accumulation)
@@ -98,6 +98,9 @@ struct AttnVariant {
                         // j > s_b + i - window, s_b = cu_qs[b] (0 without q_start); 0: none
     bool bottom_right;  // a packed causal launch (FP8 PV, per-block Q, two-level, the exact score form): row i of sequence b attends to key j iff
                         // j <= i + Lk_b - Lq_b, the lengths from cu_q / cu_k -- no operand of its own (SAGE_ATTR_CAUSAL_BOTTOM_RIGHT)
+    bool gqa_pack;      // a decode-shaped kv_lens launch (p.Lq <= 32, p.group >= 2; with or without q_start / window) whose work item is (batch, kv head,
+                        // block of four query heads of the group), one wave per head over one shared K / V ring: B * Hkv * ceil(group / 4) workgroups,
+                        // the bits of the launch without it (SAGE_ATTR_GQA_PACK); no operand, AttnParams is what it is without
 };
 constexpr int attn_qf(bool per_block, int q_dtype) { return (per_block ? 3 : 1) + (q_dtype == 0 ? 0 : 1); }   // q_dtype: DT_F16 (0) / DT_BF16
 // the one attention launcher: plans the work order, checks that the route exists (hipErrorInvalidValue) and launches the variant's kernel.
