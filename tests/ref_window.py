@@ -55,7 +55,7 @@ def visible_from_keywords(Lq: int, Lk: int, window_size, is_causal: bool, q_star
     i = torch.arange(Lq, dtype=torch.int64)[:, None]
     j = torch.arange(Lk, dtype=torch.int64)[None, :]
     d = j - (q_start + i)                                    # key position relative to the row's diagonal
-    keep = j < max(0, min(length, Lk))
+    keep = (j < max(0, min(length, Lk))).expand(Lq, Lk)      # ([Lq, Lk] also when both sides are unbounded and no row-dependent term follows)
     if right >= 0:
         keep = keep & (d <= right)
     if left >= 0:
