@@ -377,6 +377,24 @@ SAGE_API int sage_prep_v_fp8_varlen(const void *v, void *v_image, float *v_scale
  *                   Hq / Hkv >= 2 and the exact score form; that entry with Lq > 32, Hq = Hkv or SAGE_ATTR_FP8_FOLDED_SCORES, and every other
  *                   sage_attn_* entry point, refuses the bit (SAGE_EINVAL).  A call without per-sample lengths takes the same entry with kv_lens
  *                   filled with Lk.  The reference has no counterpart (one thread block per query head, qk_int_sv_f8_cuda_sm89.cuh:720-738).
+ *  flags bit 0x800  SAGE_ATTR_KV_SPLIT, with the chunk count S = (flags >> SAGE_ATTR_KV_SPLIT_SHIFT) & 0xff in flags bits 16-23: a call of one
+ *                   query block (Lq <= 128) runs as S key-range chunks (Python: sageattn_qk_int8_pv_fp8_cuda(num_splits=S)), so that few
+ *                   sequences with long key ranges fill the device.  T = ceil(ceil(Lk / 64) / S) tiles per chunk, from the padded Lk; chunk c of
+ *                   sample b holds keys [64 T c, 64 T (c + 1)) below len_b, the causal limit j <= s_b + i taken in global key coordinates: no
+ *                   divisibility rule, no tail launch, and a chunk without a visible key requests no tile and weighs nothing.  The entry issues
+ *                   three launches on the stream: pass 1, each chunk's row maxima with the attention kernel's arithmetic; pass 2, the attention
+ *                   kernel per (work item, chunk) with its running maximum started at the maximum of the chunks in front, FP32 normalised
+ *                   partials and log2-domain LSEs; the merge of sage_merge_split_f32 into o and lse.  Every P is the P of the call without the
+ *                   bit; only the FP32 summation order of O and l differs.  Under the bit launch_ws / launch_ws_bytes are the SPLIT WORKSPACE
+ *                   (device memory, 128-byte aligned, need not be zeroed, no ticket block): three segments, each rounded up to 128 bytes,
+ *                     chunk_max [B, Hkv, S, Hq / Hkv, Lq] fp32, lse_part [B, Hkv, S, Hq / Hkv, Lq] fp32, o_part [B, Hkv, S, Hq / Hkv, Lq, D] fp32:
+ *                     bytes = 2 * r128(4 * B * Hq * S * Lq) + r128(4 * B * Hq * S * Lq * D),  r128(x) = (x + 127) / 128 * 128.
+ *                   grid_out reports pass 2's grid: B * Hq * S, or B * Hkv * ceil((Hq / Hkv) / 4) * S with SAGE_ATTR_GQA_PACK.  Honoured by
+ *                   sage_attn_fused_q_pv_f8_kvlens alone -- is_causal = 0, or 1 with or without q_start (null: offsets 0), with or without
+ *                   SAGE_ATTR_GQA_PACK.  That entry refuses (SAGE_EINVAL, naming the flag) a null, misaligned or too small workspace, S outside
+ *                   [2, 255], a count without the bit, Lq > 128, a non-zero window, a non-null v_mean (the partials carry no V mean),
+ *                   SAGE_ATTR_FP8_FOLDED_SCORES and SAGE_ATTR_FORCE_PERSISTENT;
+ *                   every other sage_attn_* entry point refuses the bit and the count bits.  The reference does not split the key range.
  */
 typedef struct SageLaunchAttr {
     uint32_t struct_bytes;
@@ -408,6 +426,10 @@ typedef struct SageLaunchAttr {
 #define SAGE_ATTR_CAUSAL_BOTTOM_RIGHT 8u
 /* decode-shaped kv_lens calls: a GQA group's query heads four to a workgroup (the attribute block above: flags bit 0x100; 0x10 - 0x80 stay unknown) */
 #define SAGE_ATTR_GQA_PACK 0x100u
+/* kv_lens calls of one query block as key-range chunks, exactly (the attribute block above: flags bit 0x800; 0x200 and 0x400 stay unknown); the
+ * chunk count 2 .. 255 sits in flags bits 16-23 */
+#define SAGE_ATTR_KV_SPLIT 0x800u
+#define SAGE_ATTR_KV_SPLIT_SHIFT 16
 SAGE_API int64_t sage_attn_launch_ws_bytes(void);
 
 /*
@@ -524,7 +546,9 @@ SAGE_API int sage_attn_fused_q_pv_f8(const void *q, const int8_t *k, const void 
  *                                  last valid tile are zero; scales of an empty sample are 0.  ws: sage_stats_ws_floats(B, H, L, D)
  *   sage_attn_fused_q_pv_f8_kvlens sage_attn_fused_q_pv_f8 over those operands: non-causal rows see keys < kv_lens[b], causal rows
  *                                  key <= row and key < kv_lens[b]; an empty sample gets o = 0 and lse = -inf.  The exact score form only
- *                                  (SAGE_ATTR_FP8_FOLDED_SCORES is refused); a NULL kv_lens is refused.
+ *                                  (SAGE_ATTR_FP8_FOLDED_SCORES is refused); a NULL kv_lens is refused.  With SAGE_ATTR_KV_SPLIT (the
+ *                                  attribute block above: flags bit 0x800) a call of one query block runs as key-range chunks, exactly --
+ *                                  three launches issued by this entry, launch_ws the split workspace.
  * Replaces nothing in the reference (its dense kernels take one kv_len per call). */
 SAGE_API int sage_channel_mean_kvlens(const void *x, void *mean_out, float *ws, const int32_t *kv_lens, int B, int H, int L, int D,
                                       int64_t x_sb, int64_t x_sh, int64_t x_sl, int dtype, void *stream);

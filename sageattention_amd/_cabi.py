@@ -24,6 +24,7 @@ PV_ACCUM_SINGLE, PV_ACCUM_TWO_LEVEL, PV_ACCUM_TRITON = 0, 1, 2   # 2: FP16 PV, t
 MASK_BOOL, MASK_F16, MASK_BF16 = 1, 2, 3
 ATTR_FP8_EXACT_SCORES, ATTR_FORCE_PERSISTENT, ATTR_FP8_FOLDED_SCORES, ATTR_CAUSAL_BOTTOM_RIGHT = 1, 2, 4, 8
 ATTR_GQA_PACK = 0x100
+ATTR_KV_SPLIT, ATTR_KV_SPLIT_SHIFT = 0x800, 16      # the kv_lens family's exact split; its chunk count 2 .. 255 sits in flags bits 16-23
 
 
 class SageLaunchAttr(ctypes.Structure):
@@ -34,20 +35,27 @@ class SageLaunchAttr(ctypes.Structure):
 
 
 def launch_attr(launch_ws=None, folded_scores: bool = False, force_persistent: bool = False, grid_out=None, trace=None, trace_wgs: int = 0,
-                q_start=None, window: int = 0, causal_bottom_right: bool = False, gqa_pack: bool = False):
+                q_start=None, window: int = 0, causal_bottom_right: bool = False, gqa_pack: bool = False, kv_split: int = 0):
     """A ``SageLaunchAttr`` (or None when every field is at its default).  ``launch_ws``: a zeroed int32 CUDA tensor of
     ``sage_attn_launch_ws_bytes()`` bytes; the caller keeps it (and the returned struct) alive until the C call has returned.
     ``grid_out``: a ``ctypes.c_int32`` that receives the number of workgroups launched.  ``q_start``: an int32 CUDA tensor ``[B]``, the
     per-sample query offsets of a causal ``sage_attn_fused_q_pv_f8_kvlens`` call; ``window``: the number of keys a row of such a call sees up
     to and including its diagonal (0: unbounded).  ``causal_bottom_right``: SAGE_ATTR_CAUSAL_BOTTOM_RIGHT, the bottom-right causal mask of a
     packed ``sage_attn_fused_qblock_pv_f8_varlen`` call.  ``gqa_pack``: SAGE_ATTR_GQA_PACK, the query heads of a GQA group four to a workgroup in
-    a decode-shaped (``Lq <= 32``) ``sage_attn_fused_q_pv_f8_kvlens`` call."""
-    if launch_ws is None and not folded_scores and grid_out is None and trace is None and q_start is None and not window and not causal_bottom_right and not gqa_pack:
+    a decode-shaped (``Lq <= 32``) ``sage_attn_fused_q_pv_f8_kvlens`` call.  ``kv_split``: SAGE_ATTR_KV_SPLIT with that chunk count (2 .. 255) in
+    flags bits 16-23, the exact split of a ``sage_attn_fused_q_pv_f8_kvlens`` call of one query block; ``launch_ws`` is then the split workspace,
+    a CUDA tensor of at least ``kv_split_ws_bytes(...)`` bytes that need not be zeroed."""
+    if launch_ws is None and not folded_scores and grid_out is None and trace is None and q_start is None and not window and not causal_bottom_right and not gqa_pack \
+            and not kv_split:
         return None
     a = SageLaunchAttr()
     a.struct_bytes = ctypes.sizeof(SageLaunchAttr)
     a.flags = (ATTR_FP8_FOLDED_SCORES if folded_scores else 0) | (ATTR_FORCE_PERSISTENT if force_persistent else 0) | \
         (ATTR_CAUSAL_BOTTOM_RIGHT if causal_bottom_right else 0) | (ATTR_GQA_PACK if gqa_pack else 0)
+    if kv_split:
+        if isinstance(kv_split, bool) or not 2 <= int(kv_split) <= 255:
+            raise ValueError(f"kv_split must be a chunk count in [2, 255] (got {kv_split!r})")
+        a.flags |= ATTR_KV_SPLIT | (int(kv_split) << ATTR_KV_SPLIT_SHIFT)
     if launch_ws is not None:
         a.launch_ws = launch_ws.data_ptr()
         a.launch_ws_bytes = launch_ws.numel() * launch_ws.element_size()
@@ -61,6 +69,14 @@ def launch_attr(launch_ws=None, folded_scores: bool = False, force_persistent: b
     a.window = int(window)
     a._keep = (launch_ws, grid_out, trace, q_start)      # (the struct holds raw addresses)
     return a
+
+
+def kv_split_ws_bytes(B: int, Hq: int, Lq: int, D: int, S: int) -> int:
+    """Bytes of the split workspace of a SAGE_ATTR_KV_SPLIT call (the header's formula): ``chunk_max`` and ``lse_part`` ``[B, Hkv, S, group,
+    Lq]`` and ``o_part`` ``[B, Hkv, S, group, Lq, D]``, fp32, each segment rounded up to 128 bytes."""
+    r128 = lambda x: (x + 127) // 128 * 128
+    rows = B * Hq * S * Lq
+    return 2 * r128(4 * rows) + r128(4 * rows * D)
 
 
 def attr_arg(a):

@@ -151,14 +151,16 @@ def _v_rows_wanted(q, k, v, tensor_layout: str, is_causal: bool, override) -> bo
 
 @torch.compiler.disable
 def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, sm_scale_log2, return_lse, v_mean=None, folded_scores=False,
-                  v_rows=False, kv_lens=None, q_start=None, window=0, gqa_pack=False):
+                  v_rows=False, kv_lens=None, q_start=None, window=0, gqa_pack=False, num_splits=0):
     """FP8-PV two-level attention with the per-thread Q quantisation done in the kernel prologue
     (``sage_attn_fused_q_pv_f8``): bit-identical to ``per_thread_int8`` + the attention op, one launch and
     3 B/element of HBM traffic less.  ``v_rows`` (FP16 PV): ``v_image`` is the fp16 V tensor itself, read in place.
     ``kv_lens`` (FP8 PV, int32 [B] on the device): a key length per sample (``sage_attn_fused_q_pv_f8_kvlens``); ``q_start`` (with
     ``kv_lens``, causal; int32 [B] on the device): a query offset per sample (``SageLaunchAttr.q_start``); ``window`` (with ``kv_lens``,
     causal; a Python int): the number of keys a row sees up to and including its diagonal, 0 = unbounded (``SageLaunchAttr.window``);
-    ``gqa_pack`` (with ``kv_lens``, ``Lq <= 32``, ``Hq / Hkv >= 2``): the query heads of a GQA group four to a workgroup (``SAGE_ATTR_GQA_PACK``)."""
+    ``gqa_pack`` (with ``kv_lens``, ``Lq <= 32``, ``Hq / Hkv >= 2``): the query heads of a GQA group four to a workgroup (``SAGE_ATTR_GQA_PACK``);
+    ``num_splits`` (with ``kv_lens``, ``Lq <= 128``, no window; 0 or 2 .. 255): that many key-range chunks, exactly (``SAGE_ATTR_KV_SPLIT``; the
+    split workspace is allocated here, from the shapes alone)."""
     B, Hq, Lq, D, q_sb, q_sh, q_sl = _dims(q, tensor_layout)
     _, Hkv, Lk, _, k_sb, k_sh, k_sl = _dims(k_int8, tensor_layout)
     assert Hq % Hkv == 0, "num_qo_heads must be divisible by num_kv_heads"
@@ -169,8 +171,10 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
     # (a large non-causal call: persistent launch; FP8 PV: the score form)
     assert (q_start is None and not window) or (kv_lens is not None and is_causal)
     assert not gqa_pack or kv_lens is not None
+    assert not num_splits or (kv_lens is not None and not window and Lq <= 128)
+    split_ws = torch.empty((_cabi.kv_split_ws_bytes(B, Hq, Lq, D, num_splits) // 4,), dtype=torch.float32, device=q.device) if num_splits else None
     attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None, q_start=q_start, window=window,
-                         gqa_pack=gqa_pack)
+                         gqa_pack=gqa_pack, kv_split=num_splits, split_ws=split_ws)
     if v_rows:                     # FP16 PV on fp16 inputs: V rows in place, no tile image (sage_attn_fused_q_pv_f16_vrows)
         assert v_scale is None and v_mean is None
         _, _, _, _, v_sb, v_sh, v_sl = _dims(v_image, tensor_layout)
@@ -403,6 +407,59 @@ def _pack_gqa_args(pack_gqa, q, k, tensor_layout, qk_quant_gran: str, pv_accum_d
     return True
 
 
+# The auto plan's constants, set from tools/num_splits_probe.py (profiles/num_splits_probe.json):
+_NUM_SPLITS_AUTO_MAX_WGS = 64        # the largest unsplit launch a split was faster for (at 128 workgroups and more no chunk count was)
+_NUM_SPLITS_AUTO_TARGET = 512        # workgroups the plan aims at: two per compute unit of an MI355X, what the D = 128 kernels keep resident
+_NUM_SPLITS_AUTO_MIN_TILES = 8       # no chunk shorter than this many 64-key tiles
+_NUM_SPLITS_AUTO_MIN_KEYS, _NUM_SPLITS_AUTO_MAX_KEYS = 8192, 65536      # the shortest and the longest key range measured
+_NUM_SPLITS_AUTO_MAX_ROWS = 32       # decode-shaped calls only (measured: 1 and 16 rows; 32 is what one wave's slab and pack_gqa take)
+_NUM_SPLITS_AUTO_MIN_S, _NUM_SPLITS_AUTO_MAX_S = 8, 32      # chunk counts that were faster wherever the plan chooses them (2 and 4 are not: pass 1
+                                                            # costs about what pass 2 does); 32 is the largest measured
+
+
+def _num_splits_plan(B: int, Hq: int, Hkv: int, Lq: int, Lk: int, packed: bool) -> int:
+    """``num_splits="auto"``: the chunk count from the shapes alone (0 = no split).  No split where the unsplit launch -- ``B * Hkv *
+    ceil(group / 4)`` workgroups packed, ``B * Hq`` unpacked -- has more than 64 workgroups, nor below 8192 or above 65536 keys, nor above
+    32 query rows; else the smallest S with ``workgroups * S >= 512``, capped so that no chunk is shorter than eight tiles and at 32, and no
+    split if that leaves fewer than 8 chunks.  Every choice the plan makes on the probe's shapes is faster there than the unsplit call,
+    launches alone and whole call, by more than the measurement's spread.  The probe's shapes are bf16, D 128, GQA 32 / 8, bottom-right
+    causal, 1 and 16 rows, B 1 ... 32, 8192 / 32768 / 65536 keys, packed and unpacked: inside those bounds of rows, keys and workgroups the
+    plan extrapolates over what it does not see or the probe did not vary -- head size, head ratio, the mask, row and key counts between
+    the measured ones -- on the ground that the gain comes from the workgroup count and the chain length alone; outside them it returns no
+    split (an explicit ``num_splits=S`` is the caller's to choose anywhere)."""
+    wgs = B * Hkv * ((Hq // Hkv + 3) // 4) if packed else B * Hq
+    if wgs > _NUM_SPLITS_AUTO_MAX_WGS or not _NUM_SPLITS_AUTO_MIN_KEYS <= Lk <= _NUM_SPLITS_AUTO_MAX_KEYS or Lq > _NUM_SPLITS_AUTO_MAX_ROWS:
+        return 0
+    tiles = (Lk + 63) // 64
+    S = min(-(-_NUM_SPLITS_AUTO_TARGET // wgs), tiles // _NUM_SPLITS_AUTO_MIN_TILES, _NUM_SPLITS_AUTO_MAX_S)
+    return S if S >= _NUM_SPLITS_AUTO_MIN_S else 0
+
+
+def _num_splits_args(num_splits, q, k, tensor_layout, window_size, pack_gqa, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs) -> int:
+    """The chunk count ``num_splits`` asks for (0: none -- ``None`` and ``1`` are the call without the keyword); its argument errors (checked
+    before any work, on any device, and in front of the other keywords' checks so that they name this one).  The split is one of the
+    ``kv_lens`` kernel family, so that route's restrictions hold (:func:`_offset_route_restrictions`), worded for this keyword; it serves
+    calls of one query block and takes no ``window_size`` that bounds the look-back (``left >= 0``; a malformed one is :func:`_window_args`'s
+    to refuse).  ``"auto"`` / ``0`` plans from the shapes (:func:`_num_splits_plan`)."""
+    if num_splits is None:
+        return 0
+    auto = isinstance(num_splits, str) and num_splits == "auto"
+    if isinstance(num_splits, bool) or not (auto or (isinstance(num_splits, int) and 0 <= num_splits <= 255)):
+        raise ValueError(f"num_splits must be None, an int in [0, 255] or 'auto' (got {num_splits!r})")
+    if num_splits == 1:
+        return 0
+    _offset_route_restrictions("num_splits", qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
+    _, Hq, Lq = _dims(q, tensor_layout)[:3]
+    B, Hkv, Lk = _dims(k, tensor_layout)[:3]
+    if Lq > 128:
+        raise ValueError(f"num_splits needs qo_len <= 128 (got {Lq}): the route serves calls of one query block")
+    if isinstance(window_size, (tuple, list)) and len(window_size) == 2 and isinstance(window_size[0], int) and window_size[0] >= 0:
+        raise ValueError(f"num_splits cannot be combined with window_size={tuple(window_size)!r}: a window that bounds the look-back bounds the keys itself")
+    if auto or num_splits == 0:
+        return _num_splits_plan(B, Hq, Hkv, Lq, Lk, pack_gqa is True)
+    return num_splits
+
+
 def _window_args(window_size, is_causal: bool, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs):
     """``window_size=(left, right)`` (FlashAttention's convention, -1 = unbounded on that side) as ``(W, r)``: a row sees ``W`` keys up to and
     including its diagonal (0: unbounded), the diagonal shifted right by ``r`` keys; None when there is no window.  Its argument errors are
@@ -563,7 +620,7 @@ def _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
 # ------------------------------------------------------------------------------------------------
 def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND", is_causal: bool = False,
              sm_scale: Optional[float] = None, return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, q_start=None,
-             causal_align: str = "top_left", window_size=None, pack_gqa=None, **kwargs: Any):
+             causal_align: str = "top_left", window_size=None, pack_gqa=None, num_splits=None, **kwargs: Any):
     """Select the implementation for the device, as the reference does per compute capability
     (core.py:143-157).  On gfx950 that is INT8 QK^T + FP8 PV with two-level FP32 accumulation
     (the reference's sm90 choice, ``pv_accum_dtype="fp32+fp32"``).  Extra SDPA-style kwargs
@@ -571,7 +628,8 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
     reference ignores them.  ``kv_lens`` (gfx950 extension, int32 / int64 ``[B]`` on q's device): a key length per sample of a right-padded
     batch; ``q_start`` (int, or int32 / int64 ``[B]``) / ``causal_align="bottom_right"``: where the causal diagonal of each sample lies -- row i
     attends to key j iff ``j <= q_start[b] + i`` and ``j < len_b``; ``window_size=(left, right)``: a sliding window in FlashAttention's
-    convention; ``pack_gqa=True``: a decode-shaped call (``qo_len <= 32``) runs a GQA group's query heads four to a workgroup, same bits.
+    convention; ``pack_gqa=True``: a decode-shaped call (``qo_len <= 32``) runs a GQA group's query heads four to a workgroup, same bits;
+    ``num_splits=S`` / ``"auto"``: a call of one query block (``qo_len <= 128``) runs as S key-range chunks, exactly.
     See :func:`sageattn_qk_int8_pv_fp8_cuda`."""
     _check_shapes(q, k, v, tensor_layout)      # (again in the entry point called below: this one is in front of the device query)
     if torch.compiler.is_compiling():      # the device query is not traceable; the opaque op checks the device when it runs
@@ -583,6 +641,8 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
             raise ValueError("window_size is not supported under torch.compile")
         if pack_gqa:
             raise ValueError("pack_gqa is not supported under torch.compile")
+        if num_splits is not None and num_splits != 1:
+            raise ValueError("num_splits is not supported under torch.compile")
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32")
     arch = get_gcn_arch(q.device) if q.is_cuda else "cpu"
@@ -591,7 +651,8 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32", split_kv=kwargs.get("split_kv"),
                                             fused_prepass=kwargs.get("fused_prepass"), fp8_scores=kwargs.get("fp8_scores"),
                                             split_kv_exact=kwargs.get("split_kv_exact", False), kv_lens=kv_lens,
-                                            q_start=q_start, causal_align=causal_align, window_size=window_size, pack_gqa=pack_gqa)
+                                            q_start=q_start, causal_align=causal_align, window_size=window_size, pack_gqa=pack_gqa,
+                                            num_splits=num_splits)
     raise ValueError(f"Unsupported architecture: {arch} (sageattention_amd targets gfx950 / MI355X only)")
 
 
@@ -1049,7 +1110,7 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
                                  qk_quant_gran: str = "per_thread", sm_scale: Optional[float] = None,
                                  pv_accum_dtype: str = "fp32+fp16", smooth_k: bool = True, smooth_v: bool = False,
                                  return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, q_start=None,
-                                 causal_align: str = "top_left", window_size=None, pack_gqa=None, **kwargs: Any):
+                                 causal_align: str = "top_left", window_size=None, pack_gqa=None, num_splits=None, **kwargs: Any):
     """INT8 QK^T + FP8 (e4m3) PV (reference core.py:636-826).  "fp32+fp32" and "fp32+fp16" both
     run the two-level kernel with an FP32 tile buffer (gfx950's FP8 MFMA only writes FP32, so V
     keeps the full ``scale_max=448``; the reference's 2.25 is an FP16-accumulator artefact,
@@ -1108,7 +1169,24 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     ``pack_gqa=False`` -- on every input, and nothing else is promised.  It combines with ``kv_lens``, ``q_start`` / ``causal_align`` and
     ``window_size`` in every combination they take; alone, the call takes the ``kv_lens`` attention entry with lengths filled with ``kv_len``
     behind the plain pre-pass.  The route's restrictions are ``kv_lens``'s and raise ValueError naming ``pack_gqa``, as do ``qo_len > 32``,
-    ``num_qo_heads == num_kv_heads`` and use under torch.compile."""
+    ``num_qo_heads == num_kv_heads`` and use under torch.compile.
+
+    ``num_splits`` (gfx950 extension; ``None`` / ``1``: today's call, every bit, launch and grid unchanged): an int ``2 .. 255`` runs a call
+    of one query block (``qo_len <= 128``) as that many key-range chunks, so that few sequences with long key ranges fill the device:
+    ``B * Hq * S`` workgroups, ``B * Hkv * ceil(group / 4) * S`` with ``pack_gqa=True``.  It is exact: a first launch computes each chunk's
+    row maxima with the attention kernel's arithmetic, each chunk then starts its running maximum where the unsplit call's stands at the
+    chunk's first tile, and an FP32 merge adds the chunks up -- every P is the P of the call without ``num_splits``, only the FP32 summation
+    order of O and l differs.  ``T = ceil(ceil(kv_len / 64) / S)`` tiles per chunk from the padded ``kv_len``; chunk c of sample b holds keys
+    ``[64 T c, 64 T (c + 1))`` below ``len_b``, the causal limit in global key coordinates: no divisibility rule, and a chunk that holds no
+    visible key -- past ``len_b``, behind the diagonal, of an empty sample -- requests no tile and weighs nothing.  ``"auto"`` / ``0`` plans
+    S from the shapes alone and splits only inside the region a probe measured the route faster in: at most 64 unsplit workgroups, 8192 to
+    65536 keys, at most 32 query rows.  The keyword rides on
+    the ``kv_lens`` family as ``pack_gqa`` does and combines with ``kv_lens``, ``q_start``, ``causal_align="bottom_right"`` and
+    ``pack_gqa=True`` (whose own rules hold); without ``kv_lens`` the lengths are filled with ``kv_len`` on the device, and ``is_causal=True``
+    without offsets is the top-left mask.  The workspace is allocated from the shapes, nothing reads lengths or offsets on the host: the call
+    captures into a HIP graph and a replay follows the length tensor's contents.  The route's restrictions are ``kv_lens``'s and raise
+    ValueError naming ``num_splits``, as do ``qo_len > 128``, a ``window_size`` that bounds the look-back, a value that is no int in
+    ``[0, 255]`` nor ``"auto"`` and use under torch.compile."""
     if torch.compiler.is_compiling():
         if kv_lens is not None:
             raise ValueError("kv_lens is not supported under torch.compile (the compiled op takes the default routes)")
@@ -1118,9 +1196,12 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
             raise ValueError("window_size is not supported under torch.compile (the compiled op takes the default routes)")
         if pack_gqa:
             raise ValueError("pack_gqa is not supported under torch.compile (the compiled op takes the default routes)")
+        if num_splits is not None and num_splits != 1:
+            raise ValueError("num_splits is not supported under torch.compile (the compiled op takes the default routes)")
         return _compiled_call("fp8", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse, kwargs)
     _check_shapes(q, k, v, tensor_layout)
-    gqa_pack = _pack_gqa_args(pack_gqa, q, k, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)      # (first: its errors name it)
+    splits = _num_splits_args(num_splits, q, k, tensor_layout, window_size, pack_gqa, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
+    gqa_pack = _pack_gqa_args(pack_gqa, q, k, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)      # (in front of kv_lens's checks: its errors name it)
     with_lens = _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     win = _window_args(window_size, is_causal, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     window, shift = win if win is not None else (0, 0)
@@ -1155,7 +1236,7 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
         lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
                                                                               return_lse, False, kv_lens=lens)
         o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, q_start=start, window=window, gqa_pack=gqa_pack)
+                               kv_lens=lens, q_start=start, window=window, gqa_pack=gqa_pack, num_splits=splits)
         return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
     if with_start:
         # query offsets without key lengths: the plain pre-pass (the one-launch route included) and the same attention entry with lengths
@@ -1167,16 +1248,18 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
         lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
                                                                               return_lse, fused)
         o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, q_start=start, window=window, gqa_pack=gqa_pack)
+                               kv_lens=lens, q_start=start, window=window, gqa_pack=gqa_pack, num_splits=splits)
         return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
-    if gqa_pack:
-        # packed GQA groups without lengths or offsets: the plain pre-pass and the kv_lens attention entry with lengths filled with kv_len, as above
+    if gqa_pack or splits:
+        # packed GQA groups / key-range chunks without lengths or offsets: the plain pre-pass and the kv_lens attention entry with lengths filled
+        # with kv_len, as above (is_causal: the top-left mask -- the split's causal kernels take offsets, and none means 0)
         B_ = _dims(q, tensor_layout)[0]
         lens = torch.full((B_,), _dims(k, tensor_layout)[2], dtype=torch.int32, device=q.device)
         lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
                                                                               return_lse, fused)
+        packed = dict(gqa_pack=True) if gqa_pack else {}
         o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, gqa_pack=True)
+                               kv_lens=lens, num_splits=splits, **packed)
         return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
     if fuse_q:
         # default route: Q is quantised inside the attention kernel (same bits, no INT8 copy of Q in HBM).

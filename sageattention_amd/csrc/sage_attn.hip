@@ -62,9 +62,12 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
     // per-block Q: per-block k scales; FP16 PV in the Triton kernel form; FP8 PV over packed batches only, the exact score form
     if (per_block && (v.kthread || (v.pv_fp8 ? (!varlen || o.fp8_folded) : !v.two_level))) return false;
     if (p.v_rows != 0 && (v.pv_fp8 || v.mask_kind != 0 || varlen || p.kv_split > 1 || v.qf == 2 || v.qf == 4)) return false;     // (fp16 q only)
-    if ((v.seeded || v.kv_lens) && (!per_thread || !v.pv_fp8 || o.fp8_folded || (v.seeded && v.kv_lens))) return false;
+    if ((v.seeded || v.kv_lens) && (!per_thread || !v.pv_fp8 || o.fp8_folded)) return false;
     if (v.seeded != (p.seed_max != nullptr) || (v.seeded && p.kv_split < 1)) return false;
-    if (v.kv_lens && (p.cu_k == nullptr || p.kv_split > 1)) return false;
+    if (v.kv_lens && (p.cu_k == nullptr || (p.kv_split > 1 && !v.seeded))) return false;
+    // the kv_lens family's split (seeded with kv_lens): one query block, chunks of whole tiles folded into the kv heads, no window
+    if (v.seeded && v.kv_lens && (p.nqblk != 1 || p.kv_split < 2 || p.kv_base <= 0 || (p.kv_base & 63) != 0 || p.Hkv % p.kv_split != 0 ||
+                                  p.seed_chunks != p.kv_split || p.seed_first != 0 || v.window != 0 || p.sched != nullptr)) return false;
     if (v.q_start != (!varlen && p.cu_qs != nullptr) || (v.q_start && (!v.kv_lens || !v.causal))) return false;
     // a window: the causal kv_lens kernels (offsets optional), or -- without kv_lens -- a packed bottom-right launch (the next line's conditions);
     // shapes whose sums stay inside the kernel's int arithmetic (a packed launch has no Lk of its own: p.Lk = 0, the caller bounds the sum)
@@ -87,6 +90,7 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     if (!route_exists(p, v, o)) return hipErrorInvalidValue;
     // the instantiation unit of (head_dim, PV format, FP8 score form, seeded / kv_lens / q_start / window / packed GQA groups / packed FP8 with the per-block Q quantiser, top-left, bottom-right or bottom-right with a window)
     const bool d128 = v.head_dim == 128;
+    if (v.seeded && v.kv_lens) return d128 ? launch_attn_f8_kvsplit<128>(p, v, nwork, o) : launch_attn_f8_kvsplit<64>(p, v, nwork, o);
     if (v.seeded) return d128 ? launch_attn_f8_seeded<128>(p, v, nwork, o) : launch_attn_f8_seeded<64>(p, v, nwork, o);
     if (v.gqa_pack) return d128 ? launch_attn_f8_gpack<128>(p, v, nwork, o) : launch_attn_f8_gpack<64>(p, v, nwork, o);
     if (v.window > 0 && v.kv_lens) return d128 ? launch_attn_f8_window<128>(p, v, nwork, o) : launch_attn_f8_window<64>(p, v, nwork, o);

@@ -211,6 +211,14 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // head (4 gb + w >= group) is idle: it takes part in the tile requests and every barrier, loads no Q row (zeros, as rows past Lq are) and
 // stores nothing; its head index is the group's first, so that no address is formed from a head past Hq.  No ticket loop: a decode launch
 // does not reach twelve rounds of workgroups.
+// SEED with KVLEN (non-causal, or causal with QSTART; with or without GPACK: units sage_attn_d{128,64}_f8ks.hip) is pass 2 of the kv_lens family's
+// exact split (num_splits=): a call of one query block (p.Lq <= 128) as p.kv_split chunks of p.kv_base = 64 T keys, the chunk folded
+// into the kv-head dimension as above.  A work item forms len_b and s_b as the KVLEN / QSTART kernels do and shifts both into its chunk: its
+// first key is kc0 = chunk * 64 T, Lk becomes clamp(len_b - kc0, 0, 64 T) and kchunk0 = kc0 - s_b, so the loop bounds, the last-tile bodies and
+// every mask are those of a call on the chunk's keys; the ragged last tile of a sample is simply the last tile of its last non-empty chunk.
+// The running maximum starts from the prefix maximum of pass 1's chunk maxima and the FP32 normalised partial and its log2-domain LSE are
+// stored per chunk; a chunk that holds no visible key -- past len_b, behind the block's diagonal, of an empty sample -- requests no tile and
+// gives o = +0, lse = -inf, the weight 0 of the merge.
 template <int D, bool PV_FP8, bool CAUSAL, bool KTHREAD, bool TWO_LEVEL, int NH, int MASK = 0, int QF = 0, bool GPACK = false, bool SFOLD = true,
           bool CPERS = false, bool VROWS = false, bool SEED = false, bool WINDOW = false, bool QSTART = false, bool KVLEN = false>
 __global__ void __launch_bounds__(256, SAGE_MIN_WAVES_K(D, MASK, WINDOW && QSTART && !KVLEN && CPERS))
@@ -240,8 +248,9 @@ sage_attn_kernel(const AttnParams p_arg)
     constexpr int NS = 2 * NH;                       // 32-key S^T sub-tiles per iteration
     static_assert(!SEED || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS),
                   "the seeded split: FP8 PV, fused per-thread Q, exact score form, dense");
-    static_assert(!KVLEN || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS && !SEED),
+    static_assert(!KVLEN || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS),
                   "per-sample key lengths: FP8 PV, fused per-thread Q, exact score form, dense");
+    static_assert(!(SEED && KVLEN) || (!WINDOW && QSTART == CAUSAL), "the kv_lens split: no window, and its causal kernels are the offset kernels");
     static_assert(!QSTART || (CAUSAL && (KVLEN || (PV_FP8 && !KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && QF >= 3 && !VROWS && !SEED))),
                   "query offsets: the causal kv_lens kernels (dense, p.cu_qs), or a packed launch's bottom-right alignment (FP8 PV, per-block Q, two-level; with or without a window)");
     static_assert(!WINDOW || QSTART, "the sliding window: the q_start kernels");
@@ -267,7 +276,7 @@ sage_attn_kernel(const AttnParams p_arg)
     // (round 5: the packed / varlen route's CAUSAL launches over the device-built work list take the route too -- +2.2 ... 2.9 % at C4 -- through
     //  instantiations of their own (CPERS); dense causal launches lose 0.1 ... 7.5 % with tickets and the loop's mere presence costs the dense
     //  Triton-API causal kernel 1.3 %, so their instantiations stay without it: profiles/r5_pers_causal_probe.txt, r5_run_c_qf_pers_ab.txt)
-    constexpr bool PERS_OK = (!CAUSAL || CPERS) && MASK == 0 && !GPACK;
+    constexpr bool PERS_OK = (!CAUSAL || CPERS) && MASK == 0 && !GPACK && !(SEED && KVLEN);      // (the kv_lens split: the ordinary launch alone, as GPACK)
     const bool pers = PERS_OK && p.sched != nullptr;
     __shared__ int s_ticket[2];                 // (two slots, alternating: a wave may still be reading the previous ticket when wave 0 posts the next)
     int tpar = 0;
@@ -453,6 +462,33 @@ sage_attn_kernel(const AttnParams p_arg)
             ks_ptr += (long)(kc0w >> 6) * p.Hkv;
             Lk = Lk > kc0w ? Lk - kc0w : 0;
         }
+    } else if constexpr (SEED && KVLEN) {
+        // the kv_lens split (pass 2): chunk hk - hk0 * S of kv head hk0 holds keys [kc0, kc0 + p.kv_base) of the sample's first len_b, in whole
+        // 64-key tiles of the UNSPLIT call's operands.  The length and the offset are formed as the KVLEN / QSTART kernels form them and shifted
+        // into the chunk's coordinates; k_off, v_tile0 and ks_ptr move as the WINDOW branch moves them.  A chunk from len_b on keeps Lk = 0:
+        // no tile is requested and nothing is formed from its pointers.
+        typedef const __attribute__((address_space(4))) int *cint_p;
+        const int hk0 = hk / p.kv_split, kc0 = (hk - hk0 * p.kv_split) * p.kv_base;
+        const long bh0 = (long)b * (p.Hkv / p.kv_split) + hk0;
+        const int bu = __builtin_amdgcn_readfirstlane(b);
+        const int len = ((cint_p)p.cu_k)[bu];
+        const int lenb = len < 0 ? 0 : (len < p.Lk ? len : p.Lk);
+        if constexpr (QSTART) {            // (p.cu_qs may be null: offsets 0, the top-left mask)
+            const int s = p.cu_qs != nullptr ? ((cint_p)p.cu_qs)[bu] : 0;
+            qstart = s < -p.Lq ? -p.Lq : (s < p.Lk ? s : p.Lk);
+        }
+        kc0w = kc0;
+        const int left = lenb - kc0;
+        Lk = left < 0 ? 0 : (left < p.kv_base ? left : p.kv_base);
+        q_off = (long)b * p.q_sb + (long)(hk0 * p.group + (h - hk * p.group)) * p.q_sh;
+        k_off = (long)b * p.k_sb + (long)hk0 * p.k_sh + (long)kc0 * p.k_sl;
+        o_off = (long)b * p.o_sb + (long)h * p.o_sh;
+        v_tile0 = bh0 * (p.nks >> 2) + (kc0 >> 6);      // (per-thread k scales: four per 64-key tile, so nks / 4 tiles per head of the tensor)
+        v_tstride = 1;
+        qs_ptr = nullptr;
+        qs_stride = 0;
+        ks_ptr = p.k_scale + bh0 * p.nks + (kc0 >> 6) * 4;
+        ks_tstride = 4;
     } else if constexpr (SEED) {
         // exact split (pass 2): chunk `chunk` of kv head hk0 starts at key kc0; q, k, its scales and the V image are the unsplit call's
         const int hk0 = hk / p.kv_split, kc0 = p.kv_base + (hk - hk0 * p.kv_split) * Lk;
@@ -724,7 +760,8 @@ sage_attn_kernel(const AttnParams p_arg)
         else slot = (rin >> 5) * 8 + (rin & 7);      // per-thread: quant_per_thread.py:27-37
         qsc = qs_ptr[slot * qs_stride];
     } else {
-        // Fused Q quantisation.  The lane holds channels [32 ks + 16 g, +16) of its row for every ks -- the layout of
+        // Fused Q quantisation.  (The per-thread form has two restatements that must stay bit-equal, in sage_split_exact.hip: chunk_max_kernel's
+        // prologue and cm_quant_q.)  The lane holds channels [32 ks + 16 g, +16) of its row for every ks -- the layout of
         // the MFMA B operand -- so it quantises exactly the bytes it needs.  A per-thread group is the rows
         // r, r+8, r+16, r+24 of the wave's 32-row tile, all 128 channels: lanes n = r (mod 8), both halves g.
         constexpr int QDT = (QF == 1 || QF == 3) ? DT_F16 : DT_BF16;
@@ -780,7 +817,22 @@ sage_attn_kernel(const AttnParams p_arg)
         }
     }
 
-    if constexpr (SEED) {
+    if constexpr (SEED && KVLEN) {
+        // as below, for this wave's head (GPACK: an idle wave reads its group's first head and stores nothing); up to 254 chunks stand in
+        // front, so the values are requested four at a time instead of one memory round trip each
+        if (my_row < Lq) {
+            const int hk0 = hk / p.kv_split;
+            const long gl = (long)p.group * Lq;
+            const float *sm = p.seed_max + ((long)b * (p.Hkv / p.kv_split) + hk0) * p.seed_chunks * gl + (long)(h - hk * p.group) * Lq + my_row;
+            const int c_end = hk - hk0 * p.kv_split;
+            int c = 0;
+            for (; c + 4 <= c_end; c += 4) {
+                const float a0 = sm[c * gl], a1 = sm[(c + 1) * gl], a2 = sm[(c + 2) * gl], a3 = sm[(c + 3) * gl];
+                m_run = fmaxf(fmaxf(m_run, fmaxf(a0, a1)), fmaxf(a2, a3));
+            }
+            for (; c < c_end; c++) m_run = fmaxf(m_run, sm[c * gl]);
+        }
+    } else if constexpr (SEED) {
         // the running maximum the unsplit call holds in front of this chunk: the maximum of pass 1's values for the chunks before it
         // ([B, Hkv, seed_chunks, group, Lq]; seed_first: the number of pass-1 chunks in front of this launch's chunk 0)
         if (my_row < Lq) {
@@ -1193,7 +1245,7 @@ sage_attn_kernel(const AttnParams p_arg)
                 x[j] += mn4[dt][r4][j];
             }
             if constexpr (SEED) {      // FP32 partial rows straight from the registers: four channels per lane
-                if (my_row < Lq) *reinterpret_cast<v4f *>(reinterpret_cast<float *>(p.o) + o_off + (long)my_row * p.o_sl + d0) = v4f{x[0], x[1], x[2], x[3]};
+                if (my_row < Lq_w) *reinterpret_cast<v4f *>(reinterpret_cast<float *>(p.o) + o_off + (long)my_row * p.o_sl + d0) = v4f{x[0], x[1], x[2], x[3]};
                 continue;
             }
             v2u pk;

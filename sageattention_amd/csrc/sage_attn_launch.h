@@ -260,4 +260,20 @@ hipError_t launch_attn_f8_gpack(const AttnParams &p, const AttnVariant &v, int n
     return hipErrorInvalidValue;
 }
 
+// Pass 2 of the kv_lens family's exact split (sage_attn_kernel's SEED with KVLEN): the chunks of a call of one query block folded into the
+// kv-head dimension, non-causal with lengths or causal with offsets (QSTART, p.cu_qs nullable), each unpacked and with packed GQA groups: the
+// units sage_attn_d{128,64}_f8ks.hip.  The ordinary launch alone.
+template <int D>
+hipError_t launch_attn_f8_kvsplit(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l)
+{
+    using C = TileCfg<D, true, 1>;
+    if (!v.seeded || !v.kv_lens || v.window != 0) return hipErrorInvalidValue;
+#define SAGE_F8KS(C_, F_, G_) if (v.causal == C_ && v.qf == F_ && v.gqa_pack == G_) \
+    return launch_kernel<sage_attn_kernel<D, true, C_, true, true, 1, 0, F_, G_, false, false, false, true, false, C_, true>>(C::LDS_BYTES, p, nwork, l, false);
+    SAGE_F8KS(false, 1, false) SAGE_F8KS(false, 2, false) SAGE_F8KS(true, 1, false) SAGE_F8KS(true, 2, false)
+    SAGE_F8KS(false, 1, true)  SAGE_F8KS(false, 2, true)  SAGE_F8KS(true, 1, true)  SAGE_F8KS(true, 2, true)
+#undef SAGE_F8KS
+    return hipErrorInvalidValue;
+}
+
 }  // namespace sage

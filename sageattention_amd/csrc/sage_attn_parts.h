@@ -1,7 +1,7 @@
 // sage_attn_parts.h -- interface between the host-side dispatch of the attention launches (sage_attn.hip) and the instantiation units
 // sage_attn_d{128,64}_{f8,f8f,f16}.hip, each of which compiles the kernel family of sage_attn_kernel.h for one head size, one PV format and
 // (FP8) one score form, sage_attn_d{128,64}_f8v.hip (the packed FP8 route's fused-Q kernels) and sage_attn_d{128,64}_f8s.hip (the exact
-// split's seeded kernels) and sage_attn_d{128,64}_f8k.hip (the kv_lens route's kernels) and sage_attn_d{128,64}_f8q.hip (the same with a query offset per sample) and sage_attn_d{128,64}_f8w.hip (the same with a sliding window) and sage_attn_d{128,64}_f8g.hip (that family for decode-shaped calls, a GQA group's query heads four to a workgroup).  The split exists for build time only: the units are independent and compile in parallel.
+// split's seeded kernels) and sage_attn_d{128,64}_f8k.hip (the kv_lens route's kernels) and sage_attn_d{128,64}_f8q.hip (the same with a query offset per sample) and sage_attn_d{128,64}_f8w.hip (the same with a sliding window) and sage_attn_d{128,64}_f8g.hip (that family for decode-shaped calls, a GQA group's query heads four to a workgroup) and sage_attn_d{128,64}_f8ks.hip (that family's exact split: its kernels over one key-range chunk each, seeded).  The split exists for build time only: the units are independent and compile in parallel.
 #pragma once
 #include "sage_kernels.h"
 
@@ -65,5 +65,11 @@ template <int D>
 hipError_t launch_attn_f8_gpack(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l);
 extern template hipError_t launch_attn_f8_gpack<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_f8_gpack<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+
+// pass 2 of the kv_lens family's exact split (AttnVariant::seeded with kv_lens; unpacked or gqa_pack): units sage_attn_d{128,64}_f8ks.hip
+template <int D>
+hipError_t launch_attn_f8_kvsplit(const AttnParams &p, const AttnVariant &v, int nwork, const AttnLaunchOpts &l);
+extern template hipError_t launch_attn_f8_kvsplit<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_f8_kvsplit<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
 
 }  // namespace sage

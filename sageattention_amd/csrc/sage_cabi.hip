@@ -47,7 +47,14 @@ inline bool multiples_of(int n, const Strides &s) { return multiples_of(n, s.sb,
 struct MaskArg { const void *ptr; int kind; int64_t sb, sh, sq, sk; };
 
 // SageLaunchAttr (nullable) -> the launch workspace and the launcher's options; the attributes are arguments of THIS call, nothing is kept
-struct LaunchAttr { unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; const int32_t *q_start; int window; bool bottom_right, gqa_pack; };
+struct LaunchAttr {
+    unsigned *ws; sage::AttnLaunchOpts opts; unsigned *trace; int trace_wgs; const int32_t *q_start; int window; bool bottom_right, gqa_pack;
+    // SAGE_ATTR_KV_SPLIT: the bit, the chunk count of flags bits 16-23, and launch_ws / launch_ws_bytes as the split workspace (ws stays null then)
+    bool kv_split_flag; int kv_split; void *split_ws; int64_t split_ws_bytes;
+};
+// the refusal every entry point but sage_attn_fused_q_pv_f8_kvlens gives the split's bit and its count bits
+#define SAGE_REFUSE_KV_SPLIT(la) SAGE_REQUIRE(!(la).kv_split_flag && (la).kv_split == 0, \
+    "SAGE_ATTR_KV_SPLIT (and the chunk count in flags bits 16-23): sage_attn_fused_q_pv_f8_kvlens with Lq <= 128 and the exact score form only")
 int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAttr &out)
 {
     out.ws = nullptr;
@@ -58,6 +65,10 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     out.window = 0;
     out.bottom_right = false;
     out.gqa_pack = false;
+    out.kv_split_flag = false;
+    out.kv_split = 0;
+    out.split_ws = nullptr;
+    out.split_ws_bytes = 0;
     if (attr == nullptr) return SAGE_OK;
     SageLaunchAttr a{};
     // struct_bytes is what the CALLER's struct holds: fewer bytes than ours (an older caller) are read as far as they go, more (a newer
@@ -68,14 +79,20 @@ int read_attr(const SageLaunchAttr *attr, void *stream, bool takes_ws, LaunchAtt
     if (n < offsetof(SageLaunchAttr, q_start) + sizeof(a.q_start)) a.q_start = nullptr;      // (a struct that ends inside the field does not have it)
     if (n < offsetof(SageLaunchAttr, window) + sizeof(a.window)) a.window = 0;
     SAGE_REQUIRE(a.window >= 0, "SageLaunchAttr.window = %d: the number of keys a row sees up to its diagonal, 0 = unbounded", a.window);
-    SAGE_REQUIRE((a.flags & ~(SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES | SAGE_ATTR_FORCE_PERSISTENT | SAGE_ATTR_CAUSAL_BOTTOM_RIGHT | SAGE_ATTR_GQA_PACK)) == 0, "unknown SageLaunchAttr.flags 0x%x", a.flags);
+    SAGE_REQUIRE((a.flags & ~(SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES | SAGE_ATTR_FORCE_PERSISTENT | SAGE_ATTR_CAUSAL_BOTTOM_RIGHT | SAGE_ATTR_GQA_PACK |
+                              SAGE_ATTR_KV_SPLIT | (0xffu << SAGE_ATTR_KV_SPLIT_SHIFT))) == 0, "unknown SageLaunchAttr.flags 0x%x", a.flags);
+    const bool kv_split = (a.flags & SAGE_ATTR_KV_SPLIT) != 0;      // (launch_ws is then the split workspace, checked against the shapes by the entry that honours the bit)
     SAGE_REQUIRE((a.flags & (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES)) != (SAGE_ATTR_FP8_EXACT_SCORES | SAGE_ATTR_FP8_FOLDED_SCORES),
                  "SageLaunchAttr.flags asks for both FP8 score forms");
-    SAGE_REQUIRE(a.launch_ws == nullptr || (a.launch_ws_bytes >= sage::kAttnSchedBytes && (reinterpret_cast<uintptr_t>(a.launch_ws) & 127u) == 0),
+    SAGE_REQUIRE(kv_split || a.launch_ws == nullptr || (a.launch_ws_bytes >= sage::kAttnSchedBytes && (reinterpret_cast<uintptr_t>(a.launch_ws) & 127u) == 0),
                  "the launch workspace is %d bytes, 128-byte aligned, zeroed (got %lld bytes at %p)", sage::kAttnSchedBytes,
                  (long long)a.launch_ws_bytes, a.launch_ws);
-    SAGE_REQUIRE(!(a.flags & SAGE_ATTR_FORCE_PERSISTENT) || a.launch_ws != nullptr, "SAGE_ATTR_FORCE_PERSISTENT needs a launch workspace");
-    out.ws = takes_ws ? static_cast<unsigned *>(a.launch_ws) : nullptr;
+    SAGE_REQUIRE(!(a.flags & SAGE_ATTR_FORCE_PERSISTENT) || (a.launch_ws != nullptr && !kv_split),
+                 "SAGE_ATTR_FORCE_PERSISTENT needs a launch workspace (with SAGE_ATTR_KV_SPLIT there is none: launch_ws is the split workspace)");
+    out.ws = takes_ws && !kv_split ? static_cast<unsigned *>(a.launch_ws) : nullptr;
+    out.kv_split_flag = kv_split;
+    out.kv_split = (int)((a.flags >> SAGE_ATTR_KV_SPLIT_SHIFT) & 0xffu);
+    if (kv_split) { out.split_ws = a.launch_ws; out.split_ws_bytes = a.launch_ws_bytes; }
     out.opts.fp8_folded = (a.flags & SAGE_ATTR_FP8_FOLDED_SCORES) != 0;
     out.opts.force_persistent = takes_ws && (a.flags & SAGE_ATTR_FORCE_PERSISTENT) != 0;
     out.opts.grid_out = a.grid_out;
@@ -169,6 +186,53 @@ void fill_geometry(const AttnCall &c, bool kthread, sage::AttnParams &p)
     if (c.v_rows != nullptr) { p.v_rows = 1; p.v_sb = c.v_rows->sb; p.v_sh = c.v_rows->sh; p.v_sl = c.v_rows->sl; }
 }
 
+// SAGE_ATTR_KV_SPLIT: bytes of the split workspace -- chunk_max, lse_part [B, Hkv, S, group, Lq] and o_part [.., D], fp32, each segment rounded up to 128 bytes
+inline int64_t r128(int64_t x) { return (x + 127) / 128 * 128; }
+inline int64_t kv_split_ws_bytes(int64_t B, int64_t Hq, int64_t Lq, int64_t D, int64_t S) { return 2 * r128(4 * B * Hq * S * Lq) + r128(4 * B * Hq * S * Lq * D); }
+
+// The kv_lens family's exact split (sage_attn_fused_q_pv_f8_kvlens with SAGE_ATTR_KV_SPLIT; the call is validated -- v_mean null --, p / v describe
+// the unsplit launch): pass 1 (the chunk maxima), pass 2 (the chunks folded into the kv heads, seeded, FP32 partials) and the merge, on the call's stream.
+int kv_split_run(const AttnCall &c, const LaunchAttr &la, const sage::AttnParams &p0, const sage::AttnVariant &v0)
+{
+    const int S = la.kv_split, tiles = ((c.Lk + 63) / 64 + S - 1) / S;      // T = ceil(ceil(Lk / 64) / S), from the padded Lk
+    const int64_t need = kv_split_ws_bytes(c.B, c.Hq, c.Lq, c.D, S);
+    SAGE_REQUIRE(la.split_ws != nullptr && (reinterpret_cast<uintptr_t>(la.split_ws) & 127u) == 0 && la.split_ws_bytes >= need,
+                 "SAGE_ATTR_KV_SPLIT: launch_ws is the split workspace, %lld bytes of device memory, 128-byte aligned (got %lld bytes at %p)",
+                 (long long)need, (long long)la.split_ws_bytes, la.split_ws);
+    SAGE_REQUIRE((int64_t)c.B * c.Hq * S < ((int64_t)1 << 31), "SAGE_ATTR_KV_SPLIT: grid too large");
+    const int64_t rows = (int64_t)c.B * c.Hq * S * c.Lq;
+    float *chunk_max = static_cast<float *>(la.split_ws);
+    float *lse_part = reinterpret_cast<float *>(static_cast<char *>(la.split_ws) + r128(4 * rows));
+    float *o_part = reinterpret_cast<float *>(static_cast<char *>(la.split_ws) + 2 * r128(4 * rows));
+    const hipStream_t stream = static_cast<hipStream_t>(c.stream);
+
+    sage::ChunkMaxLensParams m{};
+    m.q = c.q; m.k = c.k; m.k_scale = c.k_scale; m.out = chunk_max; m.kv_lens = c.kv_lens; m.q_start = la.q_start;
+    m.B = c.B; m.Hq = c.Hq; m.Hkv = c.Hkv; m.group = c.Hq / c.Hkv; m.Lq = c.Lq; m.Lk = c.Lk; m.D = c.D;
+    m.S = S; m.tiles = tiles; m.nks = p0.nks;
+    m.q_sb = c.qs.sb; m.q_sh = c.qs.sh; m.q_sl = c.qs.sl; m.k_sb = c.ks.sb; m.k_sh = c.ks.sh; m.k_sl = c.ks.sl;
+    m.sm_scale_log2 = c.sm_scale_log2; m.q_dtype = c.q_dtype; m.causal = c.is_causal != 0;
+    if (const int rc = check_launch(sage::launch_chunk_max_lens(m, stream), "sage_attn_fused_q_pv_f8_kvlens (SAGE_ATTR_KV_SPLIT) pass 1 launch")) return rc;
+
+    // pass 2: the unsplit call's operands read in place, the chunks folded into the kv-head dimension (kv head hk0 * S + chunk); FP32 partials
+    // [B, Hq * S, Lq, D] = [B, Hkv, S, group, Lq, D], LSEs [B, Hq * S, Lq]
+    sage::AttnParams p = p0;
+    sage::AttnVariant v = v0;
+    p.Hq = c.Hq * S; p.Hkv = c.Hkv * S; p.kv_split = S; p.kv_base = 64 * tiles;
+    p.o = o_part; p.lse = lse_part;
+    p.o_sb = (int64_t)p.Hq * c.Lq * c.D; p.o_sh = (int64_t)c.Lq * c.D; p.o_sl = c.D;
+    p.seed_max = chunk_max; p.seed_chunks = S; p.seed_first = 0;
+    p.sched = nullptr;
+    v.seeded = true;
+    if (const int rc = check_launch(sage::launch_attention(p, v, la.opts), "sage_attn_fused_q_pv_f8_kvlens (SAGE_ATTR_KV_SPLIT) pass 2 launch")) return rc;
+
+    sage::SplitMergeParams g{};
+    g.o_part = o_part; g.lse_part = lse_part; g.o_tail = nullptr; g.lse_tail = nullptr; g.o_out = c.o; g.lse_out = c.lse;
+    g.B = c.B; g.S = S; g.H = c.Hq; g.L = c.Lq; g.D = c.D; g.group = c.Hq / c.Hkv;
+    g.o_sb = c.os.sb; g.o_sh = c.os.sh; g.o_sl = c.os.sl; g.dtype = c.out_dtype;
+    return check_launch(sage::launch_merge_split_f32(g, stream), "sage_attn_fused_q_pv_f8_kvlens (SAGE_ATTR_KV_SPLIT) merge launch");
+}
+
 // validates the call, fills the kernel parameter block, launches
 int attn_run(const AttnCall &c)
 {
@@ -177,6 +241,13 @@ int attn_run(const AttnCall &c)
     LaunchAttr la;
     if (const int rc = read_attr(c.attr, c.stream, c.mask == nullptr && !split, la)) return rc;     // (masked and split launches take no launch workspace)
     // ---- the routes a Q form admits
+    if (c.kv_lens == nullptr) SAGE_REFUSE_KV_SPLIT(la);
+    SAGE_REQUIRE(la.kv_split_flag || la.kv_split == 0, "SAGE_ATTR_KV_SPLIT: a chunk count (%d in flags bits 16-23) without the bit", la.kv_split);
+    SAGE_REQUIRE(!la.kv_split_flag || (la.kv_split >= 2 && c.Lq <= 128 && la.window == 0 && !la.opts.fp8_folded),
+                 "SAGE_ATTR_KV_SPLIT: a chunk count of 2 .. 255 in flags bits 16-23 (got %d), Lq <= 128 (got %d), no window (got %d) and the exact score form only",
+                 la.kv_split, c.Lq, la.window);
+    // (pass 2 would add the mean to every chunk's partial, and a row without a visible key would merge to 0 where the unsplit kernel gives the mean)
+    SAGE_REQUIRE(!la.kv_split_flag || c.v_mean == nullptr, "SAGE_ATTR_KV_SPLIT: v_mean must be null (the split's partials carry no V mean)");
     SAGE_REQUIRE(!(fp8 && varlen && la.opts.fp8_folded), "packed (varlen) FP8 attention has the exact score form only (SAGE_ATTR_FP8_FOLDED_SCORES)");
     // (per-sample query offsets travel in the attributes; kv_lens marks the one entry point that takes them)
     SAGE_REQUIRE(la.q_start == nullptr || (c.kv_lens != nullptr && c.is_causal && !la.opts.fp8_folded),
@@ -252,6 +323,7 @@ int attn_run(const AttnCall &c)
     // FP16 PV: the kernel's TWO_LEVEL parameter selects the Triton kernel form (true) or the CUDA kernel form (false)
     v.two_level = fp8 ? c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : c.pv_accum == SAGE_PV_ACCUM_TRITON;
     v.qf = int8q ? 0 : sage::attn_qf(per_block, c.q_dtype);
+    if (la.kv_split_flag) return kv_split_run(c, la, p, v);
     return check_launch(sage::launch_attention(p, v, la.opts), int8q ? "sage_attn launch" : per_block ? "sage_attn_fused_qblock launch" :
                         c.kv_lens != nullptr ? "sage_attn_fused_q_pv_f8_kvlens launch" : "sage_attn_fused_q launch");
 }
@@ -1148,6 +1220,7 @@ SAGE_API int sage_attn_fused_q_pv_f8_split_exact(const void *q, const int8_t *k,
     SAGE_REQUIRE(la.window == 0, "SageLaunchAttr.window: sage_attn_fused_q_pv_f8_kvlens with is_causal = 1 and the exact score form only");
     SAGE_REQUIRE(!la.bottom_right, "SAGE_ATTR_CAUSAL_BOTTOM_RIGHT: sage_attn_fused_qblock_pv_f8_varlen with is_causal = 1 and SAGE_PV_ACCUM_TWO_LEVEL only");
     SAGE_REQUIRE(!la.gqa_pack, "SAGE_ATTR_GQA_PACK: sage_attn_fused_q_pv_f8_kvlens with Lq <= 32, Hq / Hkv >= 2 and the exact score form only");
+    SAGE_REFUSE_KV_SPLIT(la);
     if (const int rc = split_exact_check(q, k, k_scale, B, Hq, Hkv, kv_split, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, q_dtype)) return rc;
     SAGE_REQUIRE(v_image && v_scale && o_part && lse_part && chunk_max, "null tensor pointer");
     SAGE_REQUIRE(tail == 0 || tail == 1, "tail must be 0 (the whole chunks) or 1 (the ragged tail), got %d", tail);

@@ -58,6 +58,8 @@ struct AttnParams {
     // the exact split's pass 2 (AttnVariant::seeded; zero / null for every other launch): kv_split chunks of Lk keys from key kv_base on,
     // folded into the kv-head dimension as above but reading the unsplit operands in place (nks: k scale slots per head of the unsplit call);
     // seed_max: pass 1's chunk maxima [B, Hkv, seed_chunks, group, Lq], seed_first: the pass-1 chunks in front of this launch's chunk 0
+    // (AttnVariant::seeded with kv_lens, the kv_lens family's split: kv_split chunks of kv_base = 64 T keys each from key 0 on, clipped per sample
+    // to its length; Lk stays the padded length of the tensors, seed_chunks = kv_split, seed_first = 0)
     const float *seed_max;
     int seed_chunks, seed_first;
     int kv_base;
@@ -293,5 +295,24 @@ struct ChunkMaxParams {
     int q_dtype, causal;
 };
 hipError_t launch_chunk_max(const ChunkMaxParams &p, hipStream_t stream);
+
+// ---- the same for the kv_lens family's split (num_splits=): a call of one query block (Lq <= 128) whose sample b attends to keys j < len_b and,
+// causal, j <= s_b + i; chunk c holds the tiles c * tiles .. + tiles - 1 of the padded tensor, clipped to ceil(len_b / 64) per sample
+struct ChunkMaxLensParams {
+    const void *q;            // as ChunkMaxParams
+    const int8_t *k;
+    const float *k_scale;
+    float *out;               // [B, Hkv, S, group, Lq]; every element is written (-inf: the chunk holds no visible key of the row)
+    const int32_t *kv_lens;   // [B], clamped to [0, Lk] as the KVLEN kernels clamp it
+    const int32_t *q_start;   // causal: nullable [B] (null: offsets 0), clamped to [-Lq, Lk] as the QSTART kernels clamp it
+    int B, Hq, Hkv, group, Lq, Lk, D;
+    int S, tiles;
+    int nks;
+    long q_sb, q_sh, q_sl;
+    long k_sb, k_sh, k_sl;
+    float sm_scale_log2;
+    int q_dtype, causal;
+};
+hipError_t launch_chunk_max_lens(const ChunkMaxLensParams &p, hipStream_t stream);
 
 }  // namespace sage

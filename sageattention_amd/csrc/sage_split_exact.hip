@@ -11,6 +11,8 @@
 //   * masking is the kernel's: key < Lk, and causal in global key coordinates (key <= row); a chunk with no visible key gives -inf.
 // No softmax, no PV, no LDS: each wave reads its K fragments straight from global memory (the four waves of a workgroup share them through the
 // cache), one tile ahead of the MFMAs.  Grid: one workgroup per (batch, kv head, chunk, query head of the group, 128-row query block).
+// chunk_max_lens_kernel (below) is the same pass for the kv_lens family's split (num_splits=): a key length and a query offset per
+// sample, one query block, chunks clipped to the sample's length.
 // Replaces nothing in the reference (whose kernels do not split the key range).
 #include "sage_common.h"
 #include "sage_kernels.h"
@@ -42,6 +44,7 @@ chunk_max_kernel(const ChunkMaxParams p)
     if (row0 >= p.Lq) return;                   // (waves are independent: no LDS, no barrier)
 
     // ---- Q: the fused-Q prologue of sage_attn_kernel (QF 1 / 2), per-thread groups = rows r, r+8, r+16, r+24 of the wave, both halves ----
+    // (one of THREE copies of this quantiser that must stay bit-equal: sage_attn_kernel.h's fused-Q prologue, this one, and cm_quant_q below)
     v4i qf[KSTEPS];
     float qsc;
     {
@@ -155,6 +158,165 @@ hipError_t launch_chunk_max(const ChunkMaxParams &p_in, hipStream_t stream)
     SAGE_CM(128, DT_F16, false) SAGE_CM(128, DT_F16, true) SAGE_CM(128, DT_BF16, false) SAGE_CM(128, DT_BF16, true)
     SAGE_CM(64, DT_F16, false)  SAGE_CM(64, DT_F16, true)  SAGE_CM(64, DT_BF16, false)  SAGE_CM(64, DT_BF16, true)
 #undef SAGE_CM
+    return hipErrorInvalidValue;
+}
+
+// chunk_max_kernel's Q prologue as a function (that kernel keeps its own copy: its instruction stream stays what it was; with
+// sage_attn_kernel.h's fused-Q prologue that makes THREE copies that must stay bit-equal -- change one, change all) -- the fused-Q
+// prologue of sage_attn_kernel (QF 1 / 2) for the lane's row `qrow` (ok: the row exists, else zeros): per-thread groups = rows
+// r, r+8, r+16, r+24 of the wave, both lane halves; the lane's INT8 fragments (channels 32 ks + 16 g .. + 15) and its group's scale
+template <int D, int QDT>
+__device__ __forceinline__ void cm_quant_q(const uint16_t *qrow, bool ok, int g, v4i (&qf)[D / 32], float &qsc)
+{
+    constexpr int KSTEPS = D / 32;
+    float x[KSTEPS][16];
+    float amax = 0.0f;
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ks++) {
+        v4u raw[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+        if (ok) {
+            raw[0] = *reinterpret_cast<const v4u *>(qrow + 32 * ks + 16 * g);
+            raw[1] = *reinterpret_cast<const v4u *>(qrow + 32 * ks + 16 * g + 8);
+        }
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const unsigned w = raw[j >> 3][(j & 7) >> 1];
+            const float f = ld16<QDT>((uint16_t)((j & 1) ? (w >> 16) : (w & 0xffffu)));
+            x[ks][j] = f;
+            amax = fmaxf(amax, fabsf(f));
+        }
+    }
+    amax = fmaxf(amax, __shfl_xor(amax, 8));
+    amax = fmaxf(amax, __shfl_xor(amax, 16));
+    amax = fmaxf(amax, __shfl_xor(amax, 32));
+    const float sc = quant_scale(amax, QS_TRITON_THREAD);
+    const float y = quant_recip(sc);
+    qsc = sc;
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ks++) {
+        int q8[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) q8[j] = quant_round_triton_nz(x[ks][j], sc, y);
+#pragma unroll
+        for (int w = 0; w < 4; w++) qf[ks][w] = (int)pack_int8x4(q8[4 * w], q8[4 * w + 1], q8[4 * w + 2], q8[4 * w + 3]);
+    }
+}
+
+// The same for the kv_lens family's split (ChunkMaxLensParams): sample b's keys end at len_b = clamp(kv_lens[b], 0, Lk) and, causal, row i sees
+// key j iff j <= s_b + i with s_b = clamp(q_start[b], -Lq, Lk) -- the KVLEN / QSTART kernels' masks in global key coordinates.  Chunk c holds the
+// tiles c * tiles .. + tiles - 1 that lie in front of ceil(len_b / 64) (and, causal, that hold a key the wave's last row sees); key rows, k scales
+// and tiles from len_b on are never requested, and a chunk without a visible key writes -inf for every row.  A call has one query block.  With
+// Lq <= 32 a wave serves one query head and a workgroup four heads of a GQA group, as the packed attention kernels (GPACK) map them -- one
+// workgroup per query head would leave three waves without rows; else a workgroup is one query head, 32 rows per wave.
+// Grid: B * Hkv * S * (Lq <= 32 ? ceil(group / 4) : group).
+template <int D, int QDT, bool CAUSAL>
+__global__ void __launch_bounds__(256, 2)
+chunk_max_lens_kernel(const ChunkMaxLensParams p)
+{
+    constexpr int KSTEPS = D / 32;
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int n = lane & 31, g = lane >> 5;
+    const bool packed = p.Lq <= 32;
+    const int per_kv = packed ? (p.group + 3) >> 2 : p.group;
+    int idx = blockIdx.x;
+    const int gi = idx % per_kv;
+    idx /= per_kv;
+    const int c = idx % p.S;
+    idx /= p.S;
+    const int hk = idx % p.Hkv, b = idx / p.Hkv;
+    const int gq = packed ? 4 * gi + wave : gi;
+    const int row0 = packed ? 0 : wave * 32, my_row = row0 + n;
+    if (gq >= p.group || row0 >= p.Lq) return;  // (waves are independent: no LDS, no barrier)
+    const int h = hk * p.group + gq;
+
+    v4i qf[KSTEPS];
+    float qsc;
+    cm_quant_q<D, QDT>(reinterpret_cast<const uint16_t *>(p.q) + (long)b * p.q_sb + (long)h * p.q_sh + (long)my_row * p.q_sl, my_row < p.Lq, g, qf, qsc);
+
+    // ---- the sample's length and offset, the chunk's tiles ----
+    int len = p.kv_lens[b];
+    len = len < 0 ? 0 : (len < p.Lk ? len : p.Lk);
+    int s = 0;
+    if (CAUSAL) {
+        s = p.q_start != nullptr ? p.q_start[b] : 0;
+        s = s < -p.Lq ? -p.Lq : (s < p.Lk ? s : p.Lk);
+    }
+    const int t0 = c * p.tiles;
+    int t1 = t0 + p.tiles;
+    const int nt = (len + BLKK - 1) / BLKK;
+    t1 = t1 < nt ? t1 : nt;
+    if (CAUSAL) {
+        const int rlast = row0 + 31 < p.Lq ? row0 + 31 : p.Lq - 1;      // the wave's last row that exists
+        const int vis = s + rlast;                                        // ... and the last key it sees
+        const int lim = vis >= 0 ? vis / BLKK + 1 : 0;
+        t1 = t1 < lim ? t1 : lim;
+    }
+    const int8_t *kb = p.k + (long)b * p.k_sb + (long)hk * p.k_sh;
+    const float *ksb = p.k_scale + ((long)b * p.Hkv + hk) * p.nks;
+    // (a tile that runs lies in front of ceil(len / 64), so len >= 1 here and rows from len on read row len - 1; masked below)
+    auto load = [&](int t, v4i (&kf)[2][KSTEPS]) {
+#pragma unroll
+        for (int sb = 0; sb < 2; sb++) {
+            int key = t * BLKK + sb * 32 + n;
+            key = key < len ? key : len - 1;
+            const int8_t *kr = kb + (long)key * p.k_sl + 16 * g;
+#pragma unroll
+            for (int kk = 0; kk < KSTEPS; kk++) kf[sb][kk] = *reinterpret_cast<const v4i *>(kr + 32 * kk);
+        }
+    };
+    int kmax = len - 1;                         // the lane's last visible key (negative: none)
+    if (CAUSAL) kmax = kmax < s + my_row ? kmax : s + my_row;
+    float mx = -INFINITY;
+    v4i kc[2][KSTEPS], kn[2][KSTEPS];
+    if (t0 < t1) load(t0, kc);
+    for (int t = t0; t < t1; t++) {
+        if (t + 1 < t1) load(t + 1, kn);
+        v16i sc[2];
+#pragma unroll
+        for (int sb = 0; sb < 2; sb++) {
+#pragma unroll
+            for (int i = 0; i < 16; i++) sc[sb][i] = 0;
+#pragma unroll
+            for (int kk = 0; kk < KSTEPS; kk++) sc[sb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(kc[sb][kk], qf[kk], sc[sb], 0, 0, 0);
+        }
+        const float s0 = ksb[4 * t + 2 * g], s1 = ksb[4 * t + 2 * g + 1];
+        const float cs0 = __builtin_ldexpf(p.sm_scale_log2 * (qsc * s0), 26);
+        const float cs1 = __builtin_ldexpf(p.sm_scale_log2 * (qsc * s1), 26);
+        // (one select per score against the lane's last visible key, no branch: see chunk_max_kernel)
+        int m0 = INT_MIN, m1 = INT_MIN;
+#pragma unroll
+        for (int sb = 0; sb < 2; sb++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int key = t * BLKK + sb * 32 + cm_crow(i, g);
+                const int v = key <= kmax ? sc[sb][i] : INT_MIN;
+                if (i & 2) m1 = max(m1, v);
+                else m0 = max(m0, v);
+            }
+        if (m0 != INT_MIN) mx = fmaxf(mx, __builtin_fmaf(__builtin_ldexpf((float)m0, -26), cs0, -kFp8Offset));
+        if (m1 != INT_MIN) mx = fmaxf(mx, __builtin_fmaf(__builtin_ldexpf((float)m1, -26), cs1, -kFp8Offset));
+#pragma unroll
+        for (int sb = 0; sb < 2; sb++)
+#pragma unroll
+            for (int kk = 0; kk < KSTEPS; kk++) kc[sb][kk] = kn[sb][kk];
+    }
+    mx = pair_max(mx);
+    if (g == 0 && my_row < p.Lq)
+        p.out[(((long)b * p.Hkv + hk) * p.S + c) * ((long)p.group * p.Lq) + (long)gq * p.Lq + my_row] = mx;
+}
+
+hipError_t launch_chunk_max_lens(const ChunkMaxLensParams &p, hipStream_t stream)
+{
+    if (p.Lq > BLKQ || p.Lq <= 0 || p.S <= 0 || p.tiles <= 0 || p.kv_lens == nullptr) return hipErrorInvalidValue;
+    const long per_kv = p.Lq <= 32 ? (p.group + 3) / 4 : p.group;
+    const long nwg = (long)p.B * p.Hkv * p.S * per_kv;
+    if (nwg <= 0) return hipSuccess;
+    if (nwg > INT_MAX) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nwg), block(256);
+#define SAGE_CML(D_, T_, C_) if (p.D == D_ && p.q_dtype == T_ && (p.causal != 0) == C_) { hipLaunchKernelGGL((chunk_max_lens_kernel<D_, T_, C_>), grid, block, 0, stream, p); return hipGetLastError(); }
+    SAGE_CML(128, DT_F16, false) SAGE_CML(128, DT_F16, true) SAGE_CML(128, DT_BF16, false) SAGE_CML(128, DT_BF16, true)
+    SAGE_CML(64, DT_F16, false)  SAGE_CML(64, DT_F16, true)  SAGE_CML(64, DT_BF16, false)  SAGE_CML(64, DT_BF16, true)
+#undef SAGE_CML
     return hipErrorInvalidValue;
 }
 

@@ -99,11 +99,14 @@ class launch_hooks:
 
 
 def attn_attr(device: torch.device, is_causal, n_items: int, folded_scores: bool = False, packed: bool = False, q_start=None, window: int = 0,
-              causal_bottom_right: bool = False, gqa_pack: bool = False):
+              causal_bottom_right: bool = False, gqa_pack: bool = False, kv_split: int = 0, split_ws=None):
     """The ``attr`` argument of an attention entry point for a call of ``n_items`` work items: NULL, or a ``SageLaunchAttr`` with the launch
     workspace (``attn_launch_ws``) and / or the folded FP8 score form, the dense route's offsets / window, the packed route's bottom-right flag, the decode route's GQA packing flag.  The returned object references the workspace tensor: keep it until
     the C call has returned."""
     h = _hooks
+    if kv_split:       # the kv_lens family's exact split: launch_ws is the split workspace (``split_ws``), and there is no ticket route to force
+        return _cabi.launch_attr(split_ws, grid_out=h.grid_probe, trace=h.trace_buf, trace_wgs=0 if h.trace_buf is None else h.trace_buf.numel() // 16,
+                                 q_start=q_start, gqa_pack=gqa_pack, kv_split=kv_split)
     ws = attn_launch_ws(device, is_causal, n_items if not h.force_persistent else max(n_items, _PERSISTENT_MIN_ITEMS), packed)
     return _cabi.launch_attr(ws, folded_scores=folded_scores, force_persistent=h.force_persistent and ws is not None, grid_out=h.grid_probe,
                              trace=h.trace_buf, trace_wgs=0 if h.trace_buf is None else h.trace_buf.numel() // 16, q_start=q_start, window=window,

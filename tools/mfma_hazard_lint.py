@@ -36,6 +36,8 @@ UNITS_PACKED_WINDOW = ("sage_attn_d128_f8vbw.hip", "sage_attn_d64_f8vbw.hip")
 # the pack_gqa route's units (decode-shaped calls, a GQA group's query heads four to a workgroup), eight kernels each: what UNITS' users expect
 # of a unit holds, but the list is their own so that those users' compile time stays what it is
 UNITS_GQA_PACK = ("sage_attn_d128_f8g.hip", "sage_attn_d64_f8g.hip")
+# the num_splits route's pass 2 (the kv_lens family's exact split: seeded KVLEN kernels, unpacked and packed), eight kernels each; a list of their own likewise
+UNITS_KV_SPLIT = ("sage_attn_d128_f8ks.hip", "sage_attn_d64_f8ks.hip")
 NEED = {"v_mfma_f32_32x32x64_f8f6f4": 19, "v_mfma_scale_f32_32x32x64_f8f6f4": 19}        # 16 passes; everything else used here: 8 passes
 NEED_DEFAULT = 11
 PASSES = {k: 16 for k in NEED}
@@ -191,7 +193,7 @@ def lint(asm_text):
 
 
 def main(argv):
-    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW + UNITS_PACKED_BR + UNITS_PACKED_WINDOW + UNITS_GQA_PACK
+    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW + UNITS_PACKED_BR + UNITS_PACKED_WINDOW + UNITS_GQA_PACK + UNITS_KV_SPLIT
     total = 0
     for u in units:
         f, n = lint(listing(u))
