@@ -24,6 +24,19 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
+}  // namespace
+
+int sage::set_last_error(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+namespace {
+
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int check_launch(hipError_t e, const char *what)

@@ -315,4 +315,8 @@ struct ChunkMaxLensParams {
 };
 hipError_t launch_chunk_max_lens(const ChunkMaxLensParams &p, hipStream_t stream);
 
+// ---- the C ABI's error channel for entry points defined outside sage_cabi.hip (sage_kv_cache.hip): stores the thread-local message that
+// sage_last_error() returns and hands `code` back
+int set_last_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
 }  // namespace sage

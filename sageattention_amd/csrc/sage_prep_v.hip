@@ -22,6 +22,7 @@
 // again and writes 1 B/elt (fp8) -- 5 B/elt against the reference's 9 B/elt (fp16 intermediate written + read twice).
 #include "sage_common.h"
 #include "sage_kernels.h"
+#include "sage_kv_block.h"
 
 namespace sage {
 
@@ -91,7 +92,7 @@ prep_v_kernel(const PrepVParams p)
         if (t == 0 && tid < D) {
             float mean, am;
             chan(tid, mean, am);
-            p.v_scale[((long)b * p.H + h) * D + tid] = am / p.scale_max;
+            p.v_scale[((long)b * p.H + h) * D + tid] = fp8_v_scale(am, p.scale_max);
             if (smooth) p.v_mean[((long)b * p.H + h) * D + tid] = mean;
         }
         unsigned char *out = reinterpret_cast<unsigned char *>(p.out) + tile_idx * (long)(D * 64);
@@ -99,26 +100,9 @@ prep_v_kernel(const PrepVParams p)
         for (int i = 0; i < D * 4 / 256; i++) {
             const int piece = tid + 256 * i;
             const int d = piece >> 2, pc = piece & 3;
-            const int ch = swz_chunk<64>(d, pc);                   // involution: physical <-> logical
             float mean, am;
             chan(d, mean, am);
-            const float recp = am > 0.0f ? p.scale_max / am : 0.0f;   // fused.cu:395
-            float f[16];
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                const int tok = pv_token_of_position(16 * ch + j);
-                float x = ld16<DT>(tile[tok * LDT + d]);
-                if (smooth) x = (t * BLKK + tok < L) ? x - mean : 0.0f;   // padding stays zero
-                x *= recp;
-                f[j] = fminf(fmaxf(x, -448.0f), 448.0f);             // satfinite
-            }
-            v4u pk;
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                int word = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * w], f[4 * w + 1], 0, false);
-                word = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * w + 2], f[4 * w + 3], word, true);
-                pk[w] = (unsigned)word;
-            }
+            const v4u pk = fp8_v_image_piece<DT, LDT>(tile, d, pc, mean, fp8_v_recp(am, p.scale_max), smooth, L - t * BLKK);
             __builtin_nontemporal_store(pk, reinterpret_cast<v4u *>(out + d * 64 + pc * 16));
         }
     } else {

@@ -13,6 +13,7 @@
 #include "sage_common.h"
 #include "sage_kernels.h"
 #include "sage_quant_math.h"
+#include "sage_kv_block.h"
 
 namespace sage {
 
@@ -79,21 +80,7 @@ quant_int8_kernel(const QuantParams p)
                 mraw[0] = ms[0];
                 mraw[1] = ms[1];
             }
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                const unsigned w = raw[j >> 3][(j & 7) >> 1];
-                float f = ld16<DT>((uint16_t)((j & 1) ? (w >> 16) : (w & 0xffffu)));
-                if (mean != nullptr) {
-                    const unsigned mw = mraw[j >> 3][(j & 7) >> 1];
-                    f = f - ld16<DT>((uint16_t)((j & 1) ? (mw >> 16) : (mw & 0xffffu)));
-                    // torch's `k - km` rounds to the input dtype (quant_per_block.py:53-54);
-                    // the CUDA quantiser keeps the fp32 difference (fused.cu:131-137)
-                    if (p.style != QS_CUDA) f = ld16<DT>(st16<DT>(f));
-                }
-                f *= p.pre_scale;
-                v[i][j] = f;
-                amax = fmaxf(amax, fabsf(f));
-            }
+            amax = quant_load16<DT>(raw, mraw, mean != nullptr, p.style, p.pre_scale, v[i]);
             atomicMax(&gmax[group_of_row(r, p.gran, p.warp)], __float_as_uint(amax));
         } else {
 #pragma unroll
@@ -111,27 +98,7 @@ quant_int8_kernel(const QuantParams p)
         const int row = rows[i];
         if (row >= L) continue;
         const float am = __uint_as_float(gmax[group_of_row(r, p.gran, p.warp)]);
-        int q[16];
-        if (p.style == QS_CUDA) {
-            const float inv = 127.0f / am;                           // fused.cu:164
-#pragma unroll
-            for (int j = 0; j < 16; j++) q[j] = quant_round_cuda(v[i][j], inv);
-        } else {
-            // x / scale must be the correctly rounded IEEE quotient (the reference divides, quant_per_block.py:41;
-            // the +-0.5 / truncate that follows makes a 1-ulp error visible in the int8): sage_quant_math.h
-            const float sc = quant_scale(am, p.style);
-            const float y = quant_recip(sc);
-            if (p.style == QS_TRITON_THREAD) {
-#pragma unroll
-                for (int j = 0; j < 16; j++) q[j] = quant_round_triton_nz(v[i][j], sc, y);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 16; j++) q[j] = quant_round_triton(v[i][j], sc, y);
-            }
-        }
-        v4u pk;
-#pragma unroll
-        for (int w = 0; w < 4; w++) pk[w] = pack_int8x4(q[4 * w], q[4 * w + 1], q[4 * w + 2], q[4 * w + 3]);
+        const v4u pk = quant_pack16(v[i], am, p.style);
         __builtin_nontemporal_store(pk, reinterpret_cast<v4u *>(p.out + ooff + (long)row * p.o_sl + col));   // written once, read by a later kernel
     }
 }
