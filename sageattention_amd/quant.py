@@ -63,7 +63,11 @@ def _dims(t: torch.Tensor, tensor_layout: str):
 def _aligned(t: torch.Tensor, elems: int) -> torch.Tensor:
     """The kernels use 16-byte vector accesses; re-pack the rare tensor that is not aligned."""
     ok = t.data_ptr() % 16 == 0 and t.stride(-1) == 1 and all(s % elems == 0 for s in t.stride()[:-1])
-    return t if ok else t.contiguous()
+    if ok:
+        return t
+    c = t.contiguous()
+    # (a contiguous view at an address that is no multiple of 16 -- rows cut out of a flat buffer -- comes back from .contiguous() as it is)
+    return c.clone() if c.data_ptr() % 16 != 0 else c
 
 
 def _squeeze_km(km: Optional[torch.Tensor], tensor_layout: str) -> Optional[torch.Tensor]:

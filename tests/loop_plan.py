@@ -4,7 +4,7 @@
 tiles (WINDOW: general iterations that cut some row on the left), the six-body pipelined loop (``csrc/sage_attn_loop_f8.h``: ``trips`` times six
 bodies, then ``remainder`` single bodies renamed behind them), the last-tile bodies (``diag_ok`` causal, ``tail_ok`` non-causal) and general
 iterations.  This module restates that arithmetic in plain Python -- C's truncating division included -- so that the GPU sweeps
-(tests/test_gpu_route_tile_counts.py) can CHOOSE lengths, offsets and windows by the loop forms they reach and ASSERT what the selection
+(tests/test_gpu_route_tile_counts.py, tests/test_gpu_split_tile_counts.py) can CHOOSE lengths, offsets and windows by the loop forms they reach and ASSERT what the selection
 covers.  It is not a reference for values, and it imports nothing from ``sageattention_amd``.  tests/test_loop_plan_host.py pins it on the
 CPU against tile ranges recomputed from the definition of visibility (``ref_window.visible``).
 
@@ -29,11 +29,12 @@ def _tdiv(a: int, b: int) -> int:
     return q if (a < 0) == (b < 0) else -q
 
 
-def _item(causal: bool, Lq: int, Lk: int, qstart, W: int, qblk: int) -> Plan:
+def _item(causal: bool, Lq: int, Lk: int, qstart, W: int, qblk: int, kc0: int = 0) -> Plan:
     """The kernel's bounds behind its per-route clamps.  ``Lk``: the item's key count (before the window's shift); ``qstart``: None without
-    QSTART; ``W``: 0 without WINDOW (else >= 1, already clamped)."""
+    QSTART; ``W``: 0 without WINDOW (else >= 1, already clamped); ``kc0``: the item's first key where the route and not the window sets it (a
+    chunk of the kv_lens split), a multiple of 64."""
     exists = qblk * BLKQ < Lq
-    kc0 = 0
+    assert kc0 % BLKK == 0 and not (W and kc0)
     if W:
         a0 = (qstart - W) + qblk * BLKQ + 1
         kc0 = (a0 & ~(BLKK - 1)) if a0 > 0 else 0
@@ -86,6 +87,26 @@ def packed(Lq_b: int, Lk_b: int, W: int, qblk: int, D: int = 128) -> Plan:
     if W:
         W = 1 if W < 1 else min(W, W_MAX)
     return _item(True, Lq_b, Lk_b, Lk_b - Lq_b, W, qblk)
+
+
+def split_tiles(Lk_padded: int, S: int) -> int:
+    """T, the 64-key tiles of a chunk of the kv_lens split: ceil(ceil(Lk_padded / 64) / S)."""
+    nt = (Lk_padded + BLKK - 1) // BLKK
+    return (nt + S - 1) // S
+
+
+def split_chunk(causal: bool, Lq: int, Lk_padded: int, len_b: int, s_b, S: int, chunk: int) -> Plan:
+    """Chunk ``chunk`` of pass 2 of the kv_lens split (``num_splits=S``, the ``f8ks`` units; SEED with KVLEN in ``csrc/sage_attn_kernel.h``): a
+    call of one query block on keys [kc0, kc0 + 64 T) of the sample's first ``len_b``.  The length and the offset are formed as the KVLEN /
+    QSTART kernels form them and shifted into the chunk: Lk = clamp(len_b - kc0, 0, 64 T), kchunk0 = kc0 - qstart.  ``s_b``: the offset of a
+    causal call (0: top-left), ignored without ``causal``.  No window, one query block."""
+    assert 1 <= Lq <= BLKQ and 2 <= S <= 255 and 0 <= chunk < S and (s_b is not None or not causal)
+    T = split_tiles(Lk_padded, S)
+    kc0 = chunk * BLKK * T
+    lenb = max(0, min(len_b, Lk_padded))
+    lk = max(0, min(lenb - kc0, BLKK * T))
+    qstart = max(-Lq, min(s_b, Lk_padded)) if causal else None
+    return _item(causal, Lq, lk, qstart, 0, 0, kc0)
 
 
 def nblk(Lq: int) -> int:
@@ -263,6 +284,93 @@ def packed_plans(W: int, pairs):
     return {(lq, lk, j): packed(lq, lk, W, j) for lq, lk in pairs for j in range(nblk(lq))}
 
 
+# ---- (f) num_splits: the chunks of the kv_lens split (tests/test_gpu_split_tile_counts.py).  Keys padded to 2560 (40 tiles); with S = 2 a chunk
+# holds T = 20 tiles, so a chunk's pipelined run reaches 18: two trips and every remainder.  One query block; the unpacked form at Lq in {1, 33,
+# 128}, the packed one at Lq in {1, 16, 32}.
+LKP_SPLIT, S_SPLIT = 2560, 2
+SPLIT_UNPACKED_LQS = (1, 33, 128)
+SPLIT_LQS = tuple(sorted(set(PACK_LQS + SPLIT_UNPACKED_LQS)))
+# non-causal: chunk 0 (no chunk in front of it) and chunk 1 (seeded behind a full chunk 0) as a partial chunk of every whole-tile count 0 .. 20,
+# with a whole last tile and with tails of 1 and 63 keys; chunk 1 empty; no keys; everything
+SPLIT_LENS = tuple(sorted({0, LKP_SPLIT} | {c + 64 * t + e for c in (0, 1280) for t in range(21) for e in (0, 1, 63) if c + 64 * t + e <= LKP_SPLIT}))
+
+
+def split_plans(causal: bool, lq: int, cases, Lkp: int = LKP_SPLIT, S: int = S_SPLIT):
+    """{(len, s, chunk): Plan} of ``cases``: lengths (non-causal; s None) or (len, s) pairs (causal)."""
+    cases = [(n, None) for n in cases] if not causal else list(cases)
+    return {(n, s, c): split_chunk(causal, lq, Lkp, n, s, S, c) for n, s in cases for c in range(S)}
+
+
+def _split_keys(causal, case, Lkp=LKP_SPLIT, S=S_SPLIT, lqs=SPLIT_LQS):
+    """What a case reaches, per Lq and chunk: the pipelined loop's partition and the last-tile bodies of every non-empty chunk; the chunks
+    without work by their cause."""
+    n, s = case if causal else (case, None)
+    keys = set()
+    for lq in lqs:
+        for c in range(S):
+            p = split_chunk(causal, lq, Lkp, n, s, S, c)
+            if p.lk == 0:
+                if min(max(n, 0), Lkp) > 0:
+                    keys.add((lq, "past_len"))             # a chunk from len_b on, of a sample that has keys
+                continue
+            if p.n_iters == 0:
+                keys.add((lq, "behind_diagonal"))
+                continue
+            keys.add((lq, "loop", c, p.trips, p.remainder))
+            if causal:                                     # the run in front of the pipelined diagonal bodies and in front of general tiles
+                keys.add((lq, "diagonal", c, p.trips, p.remainder, p.diag_ok))
+            keys.add((lq, "last", p.diag_ok if causal else p.tail_ok, p.run > 0))
+            if p.lk < BLKK:
+                keys.add((lq, "one_ragged_tile"))
+    return keys
+
+
+def _split_wanted(causal):
+    per_lq = {("loop", c, t, r) for c in range(S_SPLIT) for t, r in TRIPS_REM} | {("last", True, True), ("last", True, False)} | \
+        {("past_len",), ("one_ragged_tile",)}
+    if causal:
+        per_lq |= {("behind_diagonal",), ("last", False, True)} | {("diagonal", c, t, r, d) for c in range(S_SPLIT) for t, r in TRIPS_REM for d in (False, True)}
+    return {(lq,) + k for lq in SPLIT_LQS for k in per_lq}
+
+
+# causal: (len, s).  Offset 64 k + e puts k steady tiles of the chunk it falls into in front of the diagonal; e = 0 keeps the pipelined diagonal
+# bodies, any other e puts the diagonal across general tiles.
+_SPLIT_GRID_LENS = (LKP_SPLIT, 2497, 1281, 1280, 1279, 1217, 700, 65)
+_SPLIT_EDGE = LKP_SPLIT // S_SPLIT            # the first key of chunk 1
+
+
+def _split_causal_candidates():
+    for k in range(-2, 41):
+        for e in (0,) + tuple((1, 37, 63)[(k + i) % 3] for i in range(3)):      # (the first of equals is taken: rotate the unaligned ones)
+            for n in _SPLIT_GRID_LENS:
+                yield (n, 64 * k + e)
+    for n in SPLIT_LENS:                      # bottom-right: the last row's diagonal on the last key
+        for lq in SPLIT_LQS:
+            yield (n, n - lq)
+
+
+# the diagonal of row 0 / of the last row exactly on the chunk boundary and one key to either side; bottom-right at every Lq; rows in front of key 0; offsets at and behind
+# the length; a sample without keys
+SPLIT_CAUSAL_SPECIAL = tuple((n, _SPLIT_EDGE - r + d) for n in (LKP_SPLIT, 1300) for r in (0, 127, 32) for d in (-1, 0, 1)) + \
+    tuple((n, n - lq) for n in (LKP_SPLIT, 1343, 1281) for lq in SPLIT_LQS) + ((LKP_SPLIT, -1), (1500, -64), (LKP_SPLIT, -130), (700, 700), (700, 900), (1300, 1300), (1300, LKP_SPLIT), (0, 5), (0, 0))
+
+
+@functools.lru_cache(maxsize=None)
+def split_causal_pairs():
+    picked = _greedy(_split_causal_candidates(), functools.partial(_split_keys, True), _split_wanted(True))
+    return picked + tuple(p for p in SPLIT_CAUSAL_SPECIAL if p not in picked)
+
+
+# chunk counts: (padded length, S, lengths of the non-causal call, (len, s) pairs of the causal one) -- one tile per chunk; two; four with
+# trailing chunks past the tensor; the full width of the 8-bit count (215 chunks past the tensor, the longest seed prefix); a padded length that is
+# no multiple of 64 (41 tiles, the last of one key).  Full and ragged lengths, bottom-right at Lq 33 and unaligned offsets.
+def _count_entry(Lkp, S):
+    return (Lkp, S, (Lkp, Lkp - 27, 1345, 0), ((Lkp, Lkp - 33), (Lkp - 27, Lkp - 27 - 33), (Lkp, 1061), (1345, 1280), (Lkp - 27, -5)))
+
+
+SPLIT_COUNT_CASES = tuple(_count_entry(Lkp, S) for Lkp, S in ((2560, 40), (2560, 20), (2560, 13), (2560, 255), (2561, 3)))
+
+
 # ================================================================================================ the seeded random sweep of the keyword family
 RANDOM_LKS = (1, 63, 64, 65, 127, 128, 129, 191, 192, 193, 200, 256, 320, 449, 512, 576, 640, 705, 832, 1000, 1024, 1216, 1536)
 
@@ -313,3 +421,37 @@ def random_call_geometry(c: dict):
             ws = (-1, 0) if c["is_causal"] else (-1, -1)
         out.append((n, s, ws, c["is_causal"]))
     return out
+
+
+# ================================================================================================ the seeded random sweep of num_splits
+SPLIT_RANDOM_LKS = RANDOM_LKS + (2049, 2560)
+SPLIT_RANDOM_S = ("2", "3", "4", "7", "tiles", "tiles+3", "255")
+SPLIT_RANDOM_OFFSETS = ("none", "top_left", "bottom_right", "int", "tensor")
+
+
+def random_split_call(seed: int) -> dict:
+    """One ``num_splits=`` call of the dense FP8-PV entry point drawn from ``seed`` (tests/test_gpu_split_random.py), with a stream of its own:
+    ``random_call`` draws what it drew before this generator existed.  One query block (Lq <= 128), no window that bounds the look-back (the
+    keyword refuses both); the keys of the dictionary are ``random_call``'s, plus ``S`` (the chunk count: at least 2, 1 being the call without
+    the keyword) and the names of what was drawn (``S_kind``, ``offset``)."""
+    import random
+    rng = random.Random(47000 + seed)
+    c = dict(seed=seed, D=rng.choice((64, 128, 96)), dtype=rng.choice(("f16", "bf16")), layout=rng.choice(("HND", "NHD")), smooth_k=rng.random() < 0.5,
+             B=rng.randint(1, 3), Hkv=rng.randint(1, 2), group=rng.choice((1, 2, 4, 5)))
+    c["Lq"] = Lq = rng.randint(1, 32) if rng.random() < 0.5 else rng.randint(33, 128)
+    c["Lk"] = Lk = rng.choice([n for n in SPLIT_RANDOM_LKS if n >= Lq] if rng.random() < 0.93 else SPLIT_RANDOM_LKS)
+    c["lens"] = [rng.choice((Lk, rng.randint(0, Lk), rng.randint(max(0, Lk - 70), Lk), rng.randint(Lk // 2, Lk))) for _ in range(c["B"])]
+    c["offset"] = offset = rng.choice(SPLIT_RANDOM_OFFSETS)
+    c["window_size"], c["is_causal"], c["causal_align"], c["q_start"] = None, offset != "none", "top_left", None
+    near = lambda n: rng.choice((n - Lq, n - Lq, 0, rng.randint(-Lq - 5, Lk + 5), rng.randint(max(-Lq - 5, n - Lq - 64), min(Lk + 5, n - Lq + 64))))
+    if offset == "bottom_right":
+        c["causal_align"] = "bottom_right"
+    elif offset == "int":
+        c["q_start"] = near(min(c["lens"]))
+    elif offset == "tensor":
+        c["q_start"] = [near(n) for n in c["lens"]]
+    tiles = (Lk + BLKK - 1) // BLKK
+    c["S_kind"] = kind = rng.choice(SPLIT_RANDOM_S)
+    c["S"] = max(2, {"tiles": tiles, "tiles+3": tiles + 3}.get(kind) or int(kind))
+    c["pack_gqa"] = bool(Lq <= 32 and c["group"] >= 2 and rng.random() < 0.7)
+    return c

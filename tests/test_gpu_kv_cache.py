@@ -6,6 +6,9 @@ Two defining properties, both bit equalities:
   B  ``sageattn_kvcache`` on such a cache returns bit for bit the ``o`` and ``lse`` of ``sageattn_qk_int8_pv_fp8_cuda(q, k, v, kv_lens=...)``.
 Then the cache as it is used -- statistics frozen at prefill time, with head-room -- against FP64 attention, relative to the one-shot call's
 own error; saturation beyond the frozen range; the capacity clamp under guarded memory; capture into a graph.
+Then the cache as a decode loop drives it: property A and B after EVERY append of seeded random schedules (an open block that is wrong until a
+later append re-forms it shows at once); rows appended as a caller holds them -- slices of larger tensors, no copy made here; a used cache
+seeded again.
 
 Shapes -- the smallest that can still go wrong: B 4, Hq 8, Hkv 2, capacity 320 (five 64-key blocks) and the final lengths
   257  four whole blocks and one row         64  exactly one block (the open block is the next, empty one)
@@ -343,3 +346,195 @@ def test_append_and_attention_capture_into_a_graph():
             sl = {"k_int8": (slice(None), slice(0, n)), "k_scale": (slice(None), slice(0, nb * 4)), "v_image": (slice(None), slice(0, nb)),
                   "v_scale": (slice(None),), "k_tail": (slice(None), slice(0, n % 64)), "v_tail": (slice(None), slice(0, n % 64))}[name]
             assert torch.equal(_u8(a[b][sl]), _u8(b_[b][sl])), (name, b)
+
+
+# ---- after every append ---------------------------------------------------------------------------------------------------------------
+# A decode loop attends after every append, so an open block that is wrong until a later append re-forms it is wrong where it matters.  Eight
+# seeded random schedules per case; after EVERY step the cache is compared with the pre-pass of the current prefix under the same frozen
+# statistics (those of the schedule's final content), and every second step attends.
+# (the schedules are ``util.random_append_schedule``; what the eight reach is asserted on the CPU, tests/test_kv_cache_host.py)
+STEP_SEEDS = util.APPEND_SCHEDULE_SEEDS
+
+
+def _check_prefix(c, k, v, km, ref_dec, ref_vs, lens_now, layout, what):
+    """The cache against the pre-pass of the current prefix under the frozen statistics.  Returns the reference operands of an attention call
+    on that prefix: INT8 K (in ``layout``), its scales, the V image."""
+    D = k.shape[-1]
+    lens_t = _ints(lens_now)
+    ref_k, ref_ks = sq.per_thread_int8_k_kvlens(k, km, lens_t, layout)
+    ref_kh = _hnd(ref_k, layout)
+    kh, vh = _hnd(k, layout), _hnd(v, layout)
+    assert c.lens.tolist() == list(lens_now), what
+    now = ref_dec.copy()                                    # the final reference image's e4m3 bytes, key rows >= len zeroed
+    for b, n in enumerate(lens_now):
+        now[b, :, n:] = 0
+    got = util.decode_v_image(c.v_image.cpu().numpy(), CAP, True)
+    for b, n in enumerate(lens_now):
+        nb, r = (n + 63) // 64, n % 64
+        assert torch.equal(c.k_int8[b, :, :n], ref_kh[b, :, :n]), f"{what} sample {b}: INT8 rows differ in {int((c.k_int8[b, :, :n] != ref_kh[b, :, :n]).sum())} bytes"
+        assert torch.equal(c.k_scale[b, :, :nb * 4].view(torch.int32), ref_ks[b, :, :nb * 4].view(torch.int32)), f"{what} sample {b}: k scales"
+        assert np.array_equal(got[b, :, :nb * 64], now[b, :, :nb * 64]), \
+            f"{what} sample {b}: V differs in {int((got[b, :, :nb * 64] != now[b, :, :nb * 64]).sum())} bytes (rows {sorted(set(np.nonzero(got[b, :, :nb * 64] != now[b, :, :nb * 64])[1].tolist()))[:8]})"
+        assert torch.equal(c.k_tail[b, :, :r], kh[b, :, n - r:n]) and torch.equal(c.v_tail[b, :, :r], vh[b, :, n - r:n]), f"{what} sample {b}: tails"
+        assert bool((_u8(c.k_int8[b, :, n:]) == POISON).all()), f"{what} sample {b}: INT8 rows behind {n} written"
+        assert bool((_u8(c.k_scale[b, :, nb * 4:]) == POISON).all()), f"{what} sample {b}: scale slots behind block {nb} written"
+        assert bool((c.v_image[b, :, nb:] == POISON).all()), f"{what} sample {b}: V tiles behind {nb} written"
+        if n:
+            assert torch.equal(c.v_scale[b].view(torch.int32), ref_vs[b].view(torch.int32)), f"{what} sample {b}: v_scale"
+    return ref_k, ref_ks, torch.from_numpy(np.ascontiguousarray(util.encode_v_image(now, True))).to(DEV)
+
+
+@pytest.mark.parametrize("seed", STEP_SEEDS)
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_every_step_holds_the_prepass_of_its_prefix(case, seed):
+    from sageattention_amd import core as sc
+    D, dt, layout = case
+    k, v = _content(*case)[:2]
+    final, steps = util.random_append_schedule(seed, B, CAP)
+    lens_f = _ints(final)
+    km = sq.channel_mean_kvlens(k, lens_f, layout)
+    ref_vi, ref_vs = sq.per_channel_fp8_kvlens(v, lens_f, layout)
+    valid = (torch.arange(CAP, device=DEV)[None, :] < lens_f[:, None]).view(B, 1, CAP, 1)
+    v_amax = torch.where(valid, _hnd(v, layout).abs().float(), 0.0).amax(dim=2)
+    ref_dec = util.decode_v_image(ref_vi.cpu().numpy(), CAP, True)                  # [B, HKV, CAP, D] e4m3 bytes
+    c = _poisoned_cache(D, dt)
+    c.seed(km, v_amax)
+    q = _q(D, dt, layout, 1, seed=40 + seed)
+    sm = D ** -0.5
+    corr = sc._lse_correction(q, km.unsqueeze(1 if layout == "NHD" else 2), layout)
+    have, attended = [0] * B, 0
+    print(f"schedule {seed}: final {final}, {len(steps)} steps {[(T, n, kd) for T, n, kd in steps]}")
+    for i, (T, counts, kind) in enumerate(steps):
+        new_lens = None if kind == "none" else torch.tensor(counts, dtype=torch.int64 if kind == "i64" else torch.int32, device=DEV)
+        c.append(_rows(k, layout, have, counts, T), _rows(v, layout, have, counts, T), new_lens, layout)
+        have = [h + max(0, min(int(n), T)) for h, n in zip(have, counts)]
+        what = f"schedule {seed} step {i} (T {T}, counts {counts}, {kind}) -> {have}"
+        ref_k, ref_ks, vi_now = _check_prefix(c, k, v, km, ref_dec, ref_vs, have, layout, what)
+        if i & 1 or i == len(steps) - 1:
+            lens_t = _ints(have)
+            o, lse = sageattn_kvcache(q, c, tensor_layout=layout, is_causal=True, causal_align="bottom_right", pack_gqa=True, return_lse=True)
+            o_ref, l_ref = sc._attn_fused_q(q, ref_k, vi_now, ref_vs, ref_ks, layout, True, sc._sm_log2(sm), True, kv_lens=lens_t,
+                                            q_start=sc._q_start_tensor(None, lens_t, B, 1, CAP, DEV), gqa_pack=True)
+            o_ref, l_ref = sc._finish(o_ref, l_ref, D, True, True, corr, sm)
+            assert torch.equal(o, o_ref), f"{what}: o differs in {int((o != o_ref).sum())} of {o.numel()} elements"
+            assert torch.equal(lse, l_ref), f"{what}: lse differs in {int((lse != l_ref).sum())} of {lse.numel()} rows"
+            for b, n in enumerate(have):
+                assert n > 0 or (bool((o[b] == 0).all()) and bool(torch.isneginf(lse[b]).all())), what
+            attended += 1
+    assert tuple(have) == final and attended >= 1
+    for b, n in enumerate(final):                           # (the last step's reference image is the pre-pass's own, zero tail included)
+        assert torch.equal(vi_now[b, :, :(n + 63) // 64], ref_vi[b, :, :(n + 63) // 64]), b
+
+
+# ---- rows as a caller holds them -------------------------------------------------------------------------------------------------------
+# Slices of a larger tensor, no copy made here: the stride arithmetic of both append kernels (k_sl, k_sh, k_sb of real views).  Every element
+# around the views holds a NaN bit pattern.  Each append is compared with the same append of a contiguous copy: every byte of the cache.
+VIEW_T, VIEW_AT = 70, 30                 # 70 rows behind 30: the rows cross a block end and leave an open block
+VIEW_COUNTS = (70, 34, 5, 0)             # ... end exactly on one, stay inside the open block, take nothing
+VIEWS = ("narrow_hnd", "narrow_nhd", "packed_qkv", "row_stride_2d", "offset_16_bytes", "offset_8_bytes")
+
+
+def _nan_like(shape, dt):
+    return torch.full(shape, -1, dtype=torch.int16, device=DEV).view(dt)          # 0xFFFF: NaN as fp16 and as bf16
+
+
+def _views(name, kh, vh, dt):
+    """(k view, v view, layout) of rows ``kh`` / ``vh`` [B, HKV, T, D] inside larger NaN-filled tensors."""
+    T, D = kh.shape[2], kh.shape[3]
+    if name == "narrow_hnd":
+        bk, bv = _nan_like((B, HKV, T + 20, D), dt), _nan_like((B, HKV, T + 20, D), dt)
+        kv, vv = bk.narrow(2, 7, T), bv.narrow(2, 7, T)
+        layout = "HND"
+    elif name == "narrow_nhd":
+        bk, bv = _nan_like((B, T + 20, HKV, D), dt), _nan_like((B, T + 20, HKV, D), dt)
+        kv, vv = bk.narrow(1, 7, T), bv.narrow(1, 7, T)
+        layout = "NHD"
+    elif name == "packed_qkv":
+        qkv = _nan_like((B, T + 9, 3, HKV, D), dt)
+        kv, vv = qkv[:, 5:5 + T, 1], qkv[:, 5:5 + T, 2]
+        layout = "NHD"
+    elif name == "row_stride_2d":
+        bk, bv = _nan_like((B, HKV, T + 3, 2 * D), dt), _nan_like((B, HKV, T + 3, 2 * D), dt)
+        kv, vv = bk[:, :, 2:2 + T, :D], bv[:, :, 1:1 + T, D:]
+        layout = "HND"
+    else:
+        off = 8 if name == "offset_16_bytes" else 4
+        n = B * HKV * T * D
+        bk, bv = _nan_like((n + 64,), dt), _nan_like((n + 64,), dt)
+        kv, vv = bk[off:off + n].view(B, HKV, T, D), bv[off:off + n].view(B, HKV, T, D)
+        layout = "HND"
+    kv.copy_(kh if layout == "HND" else kh.transpose(1, 2))
+    vv.copy_(vh if layout == "HND" else vh.transpose(1, 2))
+    return kv, vv, layout
+
+
+@pytest.mark.parametrize("name", VIEWS)
+@pytest.mark.parametrize("case", [CASES[0], CASES[3]], ids=[CASE_IDS[0], CASE_IDS[3]])
+def test_appended_views_give_the_bytes_of_a_contiguous_copy(case, name):
+    D, dt, _ = case
+    k, v, km, v_amax = _content(D, dt, "HND")[:4]
+    kh, vh = k[:, :, VIEW_AT:VIEW_AT + VIEW_T], v[:, :, VIEW_AT:VIEW_AT + VIEW_T]
+    kv, vv, layout = _views(name, kh, vh, dt)
+    assert not kv.is_contiguous() or name.startswith("offset")
+    copied = sq._aligned(kv, 8) is not kv                  # which path ran: the wrapper re-packs what is not 16-byte aligned, else the kernels read the view
+    print(f"{name}: strides {kv.stride()}, offset {kv.storage_offset()} elements, data_ptr % 16 = {kv.data_ptr() % 16}: "
+          f"{'re-packed by the wrapper (a copy)' if copied else 'read in place by the kernels'}")
+    assert copied == (name == "offset_8_bytes"), name
+    caches = []
+    for rows in ((kv, vv, layout), (kh.contiguous(), vh.contiguous(), "HND")):
+        c = _poisoned_cache(D, dt)
+        c.seed(km, v_amax)
+        c.append(k[:, :, :VIEW_AT].contiguous(), v[:, :, :VIEW_AT].contiguous(), _ints([VIEW_AT, VIEW_AT, VIEW_AT, 0]))
+        c.append(rows[0], rows[1], _ints(VIEW_COUNTS), rows[2])
+        caches.append(c)
+    torch.cuda.synchronize()
+    a, b_ = caches
+    assert a.lens.tolist() == [VIEW_AT + VIEW_COUNTS[0], VIEW_AT + VIEW_COUNTS[1], VIEW_AT + VIEW_COUNTS[2], 0]
+    for t in ("k_int8", "k_scale", "v_image", "v_scale", "k_tail", "v_tail", "lens"):
+        x, y = _u8(getattr(a, t)), _u8(getattr(b_, t))
+        assert torch.equal(x, y), f"{name}: {t} differs in {int((x != y).sum())} bytes from the append of a contiguous copy"
+    assert bool((_u8(a.k_int8[0, :, :100]) != POISON).any()) and not bool(torch.isnan(a.k_tail[0, :, :36].float()).any())
+
+
+# ---- re-seeding ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_a_reseeded_cache_is_a_fresh_one(case):
+    """A cache filled to (257, 64, 130, 0), seeded again with other statistics and filled by the "mixed" schedule with other content equals a
+    fresh poisoned cache given that seed and schedule wherever the second content defines bytes: the stale tails, scales and tiles of the
+    first life reach nothing, the first block included."""
+    D, dt, layout = case
+    k, v, km, v_amax = _content(*case)[:4]
+    seq = 2 if layout == "HND" else 1
+    k2 = (0.5 * k.float().flip(seq) + 1.0).to(dt)          # other content: other means, other ranges
+    v2 = (1.75 * v.float().roll(11, seq)).to(dt)
+    lens = _ints(FINAL)
+    km2 = sq.channel_mean_kvlens(k2, lens, layout)
+    valid = (torch.arange(CAP, device=DEV)[None, :] < lens[:, None]).view(B, 1, CAP, 1)
+    v_amax2 = torch.where(valid, _hnd(v2, layout).abs().float(), 0.0).amax(dim=2)
+    assert not torch.equal(km2, km) and not torch.equal(v_amax2, v_amax)
+    used = _poisoned_cache(D, dt)
+    used.seed(km, v_amax)
+    assert tuple(_fill(used, k, v, layout, SCHEDULES["one"])) == FINAL
+    used.seed(km2, v_amax2)
+    assert used.lens.tolist() == [0] * B
+    fresh = _poisoned_cache(D, dt)
+    fresh.seed(km2, v_amax2)
+    for c in (used, fresh):
+        assert tuple(_fill(c, k2, v2, layout, SCHEDULES["mixed"])) == FINAL
+    torch.cuda.synchronize()
+    assert used.lens.tolist() == fresh.lens.tolist() == list(FINAL)
+    assert torch.equal(used.k_mean, fresh.k_mean) and torch.equal(used.v_amax, fresh.v_amax)
+    for b, n in enumerate(FINAL):
+        nb, r = (n + 63) // 64, n % 64
+        for name, sl in (("k_int8", slice(0, n)), ("k_scale", slice(0, nb * 4)), ("v_image", slice(0, nb)), ("k_tail", slice(0, r)), ("v_tail", slice(0, r))):
+            x, y = _u8(getattr(used, name)[b, :, sl]), _u8(getattr(fresh, name)[b, :, sl])
+            assert torch.equal(x, y), f"sample {b}: {name} differs in {int((x != y).sum())} bytes from the fresh cache"
+        if n:
+            assert torch.equal(used.v_scale[b].view(torch.int32), fresh.v_scale[b].view(torch.int32)), f"sample {b}: v_scale"
+    # ... and both are the pre-pass of the second content
+    ref_k, ref_ks = sq.per_thread_int8_k_kvlens(k2, km2, lens, layout)
+    ref_vi, _ = sq.per_channel_fp8_kvlens(v2, lens, layout)
+    for b, n in enumerate(FINAL):
+        nb = (n + 63) // 64
+        assert torch.equal(used.k_int8[b, :, :n], _hnd(ref_k, layout)[b, :, :n]) and torch.equal(used.v_image[b, :, :nb], ref_vi[b, :, :nb]), f"sample {b}"
+        assert torch.equal(used.k_scale[b, :, :nb * 4].view(torch.int32), ref_ks[b, :, :nb * 4].view(torch.int32)), f"sample {b}"

@@ -375,7 +375,7 @@ def _poisoned(t, lens, layout, byte):
     raw = _hnd(out, layout).view(torch.int16)
     fill = int(np.array([byte, byte], dtype=np.uint8).view(np.int16)[0])
     for b, n in enumerate(lens):
-        raw[b, :, max(0, min(n, LK)):] = fill
+        raw[b, :, max(0, min(n, raw.shape[2])):] = fill      # (raw.shape[2]: LK here, other padded lengths in the sweeps that import this)
     return out
 
 

@@ -186,3 +186,22 @@ def test_prepass_route_choice(monkeypatch):
     # without a GPU the C ABI reports a maximum head length of 0: never the fused route, never a crash
     monkeypatch.undo()
     assert not core.prepass_fused_ok(torch.empty(1, 1, 64, 64, dtype=torch.float16)) or torch.cuda.is_available()
+
+
+def test_aligned_repacks_a_contiguous_view_at_an_unaligned_address():
+    """``quant._aligned`` hands the kernels 16-byte aligned rows: a strided view is re-packed by ``.contiguous()``, and a CONTIGUOUS view whose
+    first element lies 8 bytes past an aligned address -- which ``.contiguous()`` returns as it is -- is copied too; aligned tensors pass through
+    as they are (no copy on the hot path)."""
+    from sageattention_amd.quant import _aligned
+    buf = torch.arange(4 * 2 * 3 * 64 + 64, dtype=torch.float32).to(torch.float16)
+    assert buf.data_ptr() % 16 == 0
+    for off, passes in ((0, True), (8, True), (4, False), (1, False)):
+        view = buf[off:off + 4 * 2 * 3 * 64].view(4, 2, 3, 64)
+        assert view.is_contiguous() and (view.data_ptr() % 16 == 0) == passes
+        out = _aligned(view, 8)
+        assert (out is view) == passes and out.data_ptr() % 16 == 0 and out.is_contiguous() and torch.equal(out, view)
+    strided = buf[:4 * 2 * 3 * 64].view(4, 2, 3, 64)[..., :60]          # rows 64 elements apart, 60 long: aligned rows, passes through
+    assert _aligned(strided, 8) is strided
+    odd = buf[:4 * 2 * 3 * 62].view(4, 2, 3, 62)                          # rows 124 bytes apart: re-packed
+    out = _aligned(odd.transpose(1, 2), 8)
+    assert out.is_contiguous() and out.data_ptr() % 16 == 0 and torch.equal(out, odd.transpose(1, 2))

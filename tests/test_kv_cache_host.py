@@ -234,3 +234,30 @@ def test_from_prefill_value_errors():
                      ((long, long, 64), {})):        # 72 rows do not fit into 64
         with pytest.raises(ValueError):
             QuantizedKVCache.from_prefill(*args, **kw)
+
+
+def test_the_random_append_schedules_reach_what_they_are_for():
+    """The eight schedules tests/test_gpu_kv_cache.py checks after every step (B 4, capacity 320): every T, counts below 0 and above T, all
+    three kinds of new_lens, a step that crosses a block end, one that ends on one, a sample without rows."""
+    B, cap = 4, 320
+    seen_t, kinds, flags = set(), set(), set()
+    for seed in util.APPEND_SCHEDULE_SEEDS:
+        final, steps = util.random_append_schedule(seed, B, cap)
+        assert (final, steps) == util.random_append_schedule(seed, B, cap)
+        have = [0] * B
+        flags |= {"empty"} if 0 in final else set()
+        for T, counts, kind in steps:
+            seen_t.add(T)
+            kinds.add(kind)
+            assert kind != "none" or counts == (T,) * B
+            for b, n in enumerate(counts):
+                take = max(0, min(n, T))
+                flags |= {"below"} if n < 0 else {"above"} if n > T else set()
+                if take and (have[b] + take) % 64 == 0:
+                    flags.add("ends_on_a_block_end")
+                if take and have[b] // 64 != (have[b] + take - 1) // 64 and have[b] % 64:
+                    flags.add("crosses_a_block_end")
+                have[b] += take
+        assert tuple(have) == final and all(0 <= n <= cap for n in final)
+    assert seen_t == set(util.APPEND_SCHEDULE_TS) and kinds == {"i32", "i64", "none"}, (seen_t, kinds)
+    assert flags >= {"below", "above", "ends_on_a_block_end", "crosses_a_block_end", "empty"}, flags

@@ -1,5 +1,6 @@
 """CPU: tests/loop_plan.py -- the host model of a work item's loop partition -- against the definition of visibility, and what the GPU sweeps
-chosen with it reach (tests/test_gpu_route_tile_counts.py, tests/test_gpu_route_random.py).
+chosen with it reach (tests/test_gpu_route_tile_counts.py, tests/test_gpu_route_random.py, tests/test_gpu_split_tile_counts.py,
+tests/test_gpu_split_random.py).
 
 The model restates the kernel's integer arithmetic, so it cannot vouch for itself.  For every work item of every sweep case the tile ranges are
 recomputed here from ``ref_window.visible`` alone -- a boolean [rows, keys] matrix, no arithmetic of the kernel's:
@@ -8,6 +9,7 @@ recomputed here from ``ref_window.visible`` alone -- a boolean [rows, keys] matr
     tile ``kc0 / 64 + n_iters - 1``, and every tile a row that exists sees lies in the item's range;
   * the tiles of the range in which some existing row has a key in front of its window's left edge (visible without the window, not with
     it) are the model's ``nh`` head tiles.
+A chunk of the kv_lens split (``split_chunk``) is checked the same way against the definition restricted to the chunk's keys.
 The coverage sets are the sweeps' contract: they say which loop forms of which units the selection runs.
 """
 import itertools
@@ -189,3 +191,153 @@ def test_random_calls_mostly_see_keys():
         kinds.add(("pack", c["pack_gqa"]))
     assert good >= 95, good
     assert len(kinds) == 4 + 3 + 2, kinds
+
+
+# ---------------------------------------------------------------------------------------------- num_splits: a chunk of the kv_lens split
+def _chunk_agrees_with_visibility(p, causal, Lq, Lkp, length, s, S, chunk):
+    """``split_chunk`` against the definition restricted to the chunk's keys [kc0, kc0 + 64 T): the chunk's tile range over the block's 128 row
+    slots and over the rows that exist, in the chunk's own tile numbers."""
+    T = lp.split_tiles(Lkp, S)
+    what = (causal, Lq, Lkp, length, s, S, chunk, p)
+    assert p.kc0 == chunk * 64 * T and p.nh == 0 and p.exists, what
+    s_def = max(-Lq, min(s, Lkp)) if causal else Lkp          # (the kernel's clamp: outside it no row's keys change; non-causal: every diagonal behind the last key)
+    keep = rw.visible(lp.BLKQ, Lkp, s_def, 0, 0, length)[:, p.kc0:p.kc0 + 64 * T]
+    t_slots, t_rows = _tiles(keep), _tiles(keep[:Lq])
+    n_keys = int(keep.any(dim=0).sum()) if not causal else None
+    if not causal:
+        assert p.lk == n_keys, what                          # the chunk's keys in front of len_b
+    assert p.lk == max(0, min(max(0, min(length, Lkp)) - p.kc0, 64 * T)), what
+    assert all(0 <= t < p.n_iters for t in t_rows), what
+    if t_rows:
+        assert t_rows[0] == 0, what                          # visibility is a prefix of the keys: a chunk a row reaches, it reaches from its first key
+    assert p.n_iters == (t_slots[-1] + 1 if t_slots else 0), what
+    if Lq == lp.BLKQ:
+        assert t_rows == t_slots, what
+    assert p.run == 6 * p.trips + p.remainder and 0 <= p.remainder < 6, what
+    assert p.run + (2 if p.run or p.diag_ok or p.tail_ok else 0) <= p.n_iters, what
+    # the steady tiles are whole tiles in front of len_b that every row slot sees whole (no mask of either kind)
+    if p.run:
+        whole = rw.visible(lp.BLKQ, Lkp, s_def, 0, 0, length)[:, p.kc0:p.kc0 + 64 * p.run]
+        assert bool(whole.all()), what
+
+
+def test_split_chunks_agree_with_visibility_on_the_tables():
+    for lq in lp.SPLIT_LQS:
+        for (n, s, c), p in lp.split_plans(False, lq, lp.SPLIT_LENS).items():
+            _chunk_agrees_with_visibility(p, False, lq, lp.LKP_SPLIT, n, 0, lp.S_SPLIT, c)
+        for (n, s, c), p in lp.split_plans(True, lq, lp.split_causal_pairs()).items():
+            _chunk_agrees_with_visibility(p, True, lq, lp.LKP_SPLIT, n, s, lp.S_SPLIT, c)
+    for Lkp, S, lens, pairs in lp.SPLIT_COUNT_CASES:
+        for lq in (1, 33, 128):
+            for (n, s, c), p in lp.split_plans(False, lq, lens, Lkp, S).items():
+                _chunk_agrees_with_visibility(p, False, lq, Lkp, n, 0, S, c)
+            for (n, s, c), p in lp.split_plans(True, lq, pairs, Lkp, S).items():
+                _chunk_agrees_with_visibility(p, True, lq, Lkp, n, s, S, c)
+
+
+def test_split_chunks_on_a_grid_of_lengths_offsets_and_counts():
+    """Beyond the tables: lengths and offsets around the tile and chunk edges at a small padded length (449 keys: 8 tiles, the last of one key),
+    every chunk of S = 2, 3, 5, 8 and 11 -- chunks past len_b, behind the diagonal and past the tensor (S = 5: T = 2, chunk 4 starts at the
+    tensor's end; S = 11: T = 1, three chunks past it) among them -- non-causal and causal."""
+    Lkp = 449
+    seen = set()
+    for S, lq in itertools.product((2, 3, 5, 8, 11), (1, 33, 128)):
+        T = lp.split_tiles(Lkp, S)
+        for n in (449, 448, 400, 385, 384, 257, 256, 130, 64, 63, 1, 0, -4, 500):
+            for c in range(S):
+                _chunk_agrees_with_visibility(lp.split_chunk(False, lq, Lkp, n, None, S, c), False, lq, Lkp, n, 0, S, c)
+                for s in range(-140, 470, 19):
+                    p = lp.split_chunk(True, lq, Lkp, n, s, S, c)
+                    _chunk_agrees_with_visibility(p, True, lq, Lkp, n, s, S, c)
+                    seen.add("past_len" if p.lk == 0 and 0 < n and c * 64 * T < Lkp else "past_tensor" if c * 64 * T >= Lkp else
+                             "behind_diagonal" if p.n_iters == 0 else "work")
+    assert seen == {"past_len", "past_tensor", "behind_diagonal", "work"}
+
+
+def _split_reach(plans):
+    return [p for p in plans.values() if p.lk > 0 and p.n_iters > 0]
+
+
+def test_split_tables_cover_every_trip_count_and_remainder_in_both_chunks():
+    """The conditions of the sweep of num_splits (tests/test_gpu_split_tile_counts.py), at every Lq of the packed and the unpacked form."""
+    assert lp.split_tiles(lp.LKP_SPLIT, lp.S_SPLIT) == 20
+    for lq in lp.SPLIT_LQS:
+        for causal, cases in ((False, lp.SPLIT_LENS), (True, lp.split_causal_pairs())):
+            plans = lp.split_plans(causal, lq, cases)
+            forms = _split_reach(plans)
+            for chunk in range(lp.S_SPLIT):
+                got = {(p.trips, p.remainder) for (n, s, c), p in plans.items() if c == chunk and p.lk > 0 and p.n_iters > 0}
+                assert got >= set(lp.TRIPS_REM), (lq, causal, chunk, sorted(set(lp.TRIPS_REM) - got))
+            last = {((p.diag_ok if causal else p.tail_ok), p.run > 0) for p in forms}
+            assert last >= {(True, True), (True, False)} | ({(False, True)} if causal else set()), (lq, causal, last)
+            assert any(p.lk == 0 and n > 0 for (n, s, c), p in plans.items()), (lq, causal)                 # a chunk past len_b
+            assert any(0 < p.lk < 64 and p.n_iters == 1 for p in plans.values()), (lq, causal)              # exactly one ragged tile
+            if causal:
+                assert any(p.lk > 0 and p.n_iters == 0 for p in plans.values()), lq                         # a chunk behind the diagonal
+                # every run in front of the pipelined diagonal bodies (aligned offsets) and in front of general tiles (any other)
+                got = {(c, p.trips, p.remainder, p.diag_ok) for (n, s, c), p in plans.items() if p.lk > 0 and p.n_iters > 0}
+                assert got >= {(c, t, r, d) for c in range(lp.S_SPLIT) for t, r in lp.TRIPS_REM for d in (False, True)}, lq
+    # non-causal: chunk 0 and chunk 1 as a partial chunk of every whole-tile count with a whole and with a ragged last tile; chunk 1 empty
+    nc = lp.split_plans(False, 1, lp.SPLIT_LENS)
+    for chunk in range(2):
+        assert {(p.lk // 64, p.lk % 64) for (n, s, c), p in nc.items() if c == chunk} >= {(t, e) for t in range(20) for e in (0, 1, 63)} | {(20, 0)}
+    assert any(p.lk == 0 for (n, s, c), p in nc.items() if c == 1 and n == 1280)
+    # causal: offsets of every kind
+    pairs = lp.split_causal_pairs()
+    assert all(p in pairs for p in lp.SPLIT_CAUSAL_SPECIAL)
+    assert any(s < 0 for n, s in pairs) and any(s >= n > 0 for n, s in pairs) and any(n == 0 for n, s in pairs)
+    assert {s - lp.LKP_SPLIT // 2 for n, s in pairs} >= {-1, 0, 1}                                          # row 0's diagonal on the chunk boundary
+    assert any(s == n - lq for n, s in pairs for lq in lp.SPLIT_LQS) and any(s % 64 == 0 for n, s in pairs) and any(s % 64 for n, s in pairs)
+    assert len(pairs) <= 128, len(pairs)                                                                    # (one call carries the table)
+
+
+def test_split_count_cases_reach_the_chunk_counts():
+    got = {(Lkp, S, lp.split_tiles(Lkp, S)) for Lkp, S, _, _ in lp.SPLIT_COUNT_CASES}
+    assert got == {(2560, 40, 1), (2560, 20, 2), (2560, 13, 4), (2560, 255, 1), (2561, 3, 14)}
+    for Lkp, S, lens, pairs in lp.SPLIT_COUNT_CASES:
+        T, nt = lp.split_tiles(Lkp, S), (Lkp + 63) // 64
+        assert Lkp in lens and any(n % 64 for n in lens) and 0 in lens
+        assert ((S - 1) * T >= nt) == ((Lkp, S) in ((2560, 13), (2560, 255)))                                      # trailing chunks past the tensor
+        for causal, cases in ((False, lens), (True, pairs)):
+            plans = lp.split_plans(causal, 33, cases, Lkp, S)
+            assert all(p.lk == 0 for (n, s, c), p in plans.items() if c * 64 * T >= Lkp)
+            assert any(p.lk > 0 and p.n_iters > 0 for (n, s, c), p in plans.items() if c == min(S, -(-nt // T)) - 1)      # the tensor's last chunk runs
+    assert sum(1 for _, S, _, _ in lp.SPLIT_COUNT_CASES if S == 255) == 1 and 255 * 1 - 40 == 215
+
+
+# ---------------------------------------------------------------------------------------------- the random generator of num_splits
+def test_random_calls_draw_what_they_drew():
+    """``random_call`` keeps its own stream (seed 31000 + seed) beside the second generator: its first draws are that stream's first, it draws no
+    chunk count, and it is a function of the seed alone."""
+    import random
+    for seed in (0, 41, 99):
+        rng = random.Random(31000 + seed)
+        c = lp.random_call(seed)
+        assert (c["D"], c["dtype"], c["layout"]) == (rng.choice((64, 128, 96)), rng.choice(("f16", "bf16")), rng.choice(("HND", "NHD")))
+        assert "S" not in c and lp.random_call(seed) == c
+    drawn = {s: (c["D"], c["Lq"], c["Lk"], tuple(c["lens"]), c["pack_gqa"]) for s, c in ((s, lp.random_call(s)) for s in (0, 41, 99))}
+    assert drawn == {0: (128, 102, 705, (705, 699, 412), False), 41: (96, 304, 1216, (352, 1216, 735), False), 99: (64, 18, 128, (92,), False)}      # (as before the second generator)
+
+
+def test_random_split_calls_mostly_see_keys():
+    """test_random_calls_mostly_see_keys for ``random_split_call``: at least 95 of the first 100 seeds have a sample in which at least half the
+    rows see a key; every chunk count of the list, every kind of offset and pack_gqa are drawn."""
+    good, kinds = 0, set()
+    for seed in range(100):
+        c = lp.random_split_call(seed)
+        assert c["D"] in (64, 128, 96) and 1 <= c["B"] <= 3 and 1 <= c["Hkv"] <= 2 and c["group"] in (1, 2, 4, 5) and 1 <= c["Lq"] <= 128
+        assert c["Lk"] <= lp.LKP_SPLIT and all(0 <= n <= c["Lk"] for n in c["lens"]) and (not c["pack_gqa"] or (c["Lq"] <= 32 and c["group"] >= 2))
+        assert 2 <= c["S"] <= 255 and c["window_size"] is None and c["is_causal"] == (c["offset"] != "none")
+        tiles = (c["Lk"] + 63) // 64
+        assert c["S"] == max(2, {"tiles": tiles, "tiles+3": tiles + 3}.get(c["S_kind"]) or int(c["S_kind"]))
+        share = []
+        for n, s, ws, causal in lp.random_call_geometry(c):
+            assert -c["Lq"] - 5 <= s <= c["Lk"] + 5 or c["causal_align"] == "bottom_right"
+            share.append(float(rw.visible_from_keywords(c["Lq"], c["Lk"], ws, causal, s, n).any(dim=1).float().mean()))
+        good += max(share) >= 0.5
+        kinds.add(("offset", c["offset"]))
+        kinds.add(("S", c["S_kind"]))
+        kinds.add(("pack", c["pack_gqa"]))
+    assert good >= 95, good
+    assert kinds == {("offset", o) for o in lp.SPLIT_RANDOM_OFFSETS} | {("S", k) for k in lp.SPLIT_RANDOM_S} | {("pack", False), ("pack", True)}, kinds
+    assert lp.random_split_call(7) == lp.random_split_call(7)

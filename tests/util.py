@@ -154,3 +154,36 @@ def merge_states_torch(o_acc, lse_acc, o_new, lse_new, tensor_layout="HND", firs
         lse_acc.copy_(lse)
     if out is not None:
         out.copy_((o_acc.transpose(1, 2) if tensor_layout == "NHD" else o_acc).to(out.dtype))
+
+
+# ---- seeded random append schedules of the KV cache (tests/test_gpu_kv_cache.py; what they reach: tests/test_kv_cache_host.py) ----
+APPEND_SCHEDULE_TS = (1, 2, 7, 63, 64, 65, 130)
+APPEND_SCHEDULE_SEEDS = range(8)
+
+
+def random_append_schedule(seed, B, cap):
+    """(final lengths, steps of (T, counts, kind of new_lens)) for ``B`` samples of a cache of capacity ``cap``: T is drawn from
+    APPEND_SCHEDULE_TS, counts from [-3, T + 3] (clamped on the device to [0, T]) and cut so that no sample passes its final length; ``kind`` is
+    "i32", "i64" or "none" (every sample takes all T rows).  Pure Python."""
+    import random
+    rng = random.Random(9100 + seed)
+    final = [rng.choice((cap, rng.randint(0, cap), rng.randint(0, cap), rng.randint(0, 70))) for _ in range(B)]
+    if seed % 4 == 0:
+        final[-1] = 0                                       # a sample that never gets a row
+    have, steps = [0] * B, []
+    while have != final:
+        closing = len(steps) >= 10                          # (then finish in steps of 130 rows)
+        T = 130 if closing else rng.choice(APPEND_SCHEDULE_TS)
+        counts = []
+        for b in range(B):
+            c, left = T if closing else rng.randint(-3, T + 3), final[b] - have[b]
+            counts.append(left if max(0, min(c, T)) > left else c)
+        kind = rng.choice(("i32", "i64", "none"))
+        if kind == "none":
+            if min(f - h for f, h in zip(final, have)) >= T:
+                counts = [T] * B
+            else:
+                kind = "i32"
+        steps.append((T, tuple(counts), kind))
+        have = [h + max(0, min(c, T)) for h, c in zip(have, counts)]
+    return tuple(final), steps
