@@ -16,7 +16,7 @@ import os
 
 import ctypes
 import warnings
-from typing import Any, Optional
+from typing import Any, NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -371,21 +371,7 @@ def _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran: str, pv_accum_dtype:
         raise ValueError(f"kv_lens must have shape [B] = [{B}] (got {tuple(kv_lens.shape)})")
     if kv_lens.device != q.device:
         raise ValueError(f"kv_lens must be on q's device {q.device} (got {kv_lens.device})")
-    if qk_quant_gran != "per_thread":
-        raise ValueError(f"kv_lens needs qk_quant_gran='per_thread' (got {qk_quant_gran!r})")
-    if not kwargs.get("fuse_q_quant", True):
-        raise ValueError("kv_lens needs the fused Q quantiser (fuse_q_quant=False given)")
-    if pv_accum_dtype == "fp32":
-        raise ValueError("kv_lens needs pv_accum_dtype 'fp32+fp32' or 'fp32+fp16' (two-level accumulation)")
-    if ops.fp8_folded(kwargs.get("fp8_scores")):
-        raise ValueError("kv_lens takes the exact score form only (fp8_scores='folded' given)")
-    if smooth_v:
-        raise ValueError("kv_lens does not support smooth_v=True")
-    split = kwargs.get("split_kv")
-    if split is not None and not (split == 0 and not isinstance(split, bool)):
-        raise ValueError(f"kv_lens cannot be combined with split_kv={split!r} (None or 0 only)")
-    if kwargs.get("split_kv_exact", False):
-        raise ValueError("kv_lens cannot be combined with split_kv_exact=True")
+    _offset_route_restrictions("kv_lens", qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     return True
 
 
@@ -460,11 +446,9 @@ def _num_splits_args(num_splits, q, k, tensor_layout, window_size, pack_gqa, qk_
     return num_splits
 
 
-def _window_args(window_size, is_causal: bool, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs):
-    """``window_size=(left, right)`` (FlashAttention's convention, -1 = unbounded on that side) as ``(W, r)``: a row sees ``W`` keys up to and
-    including its diagonal (0: unbounded), the diagonal shifted right by ``r`` keys; None when there is no window.  Its argument errors are
-    checked before any work, on any device.  A window rides on the ``q_start`` route, so that route's restrictions hold, worded for this
-    keyword.  With ``is_causal=False`` and ``right >= 0`` the call runs the causal kernels with the diagonal ``right`` keys further right."""
+def _window_pair(window_size, is_causal: bool):
+    """``window_size`` as the pair ``(left, right)`` (FlashAttention's convention, -1 = unbounded on that side), None when it asks for nothing;
+    the argument errors that the dense and the packed route share, worded once."""
     if window_size is None:
         return None
     ok_int = lambda x: isinstance(x, int) and not isinstance(x, bool)
@@ -477,6 +461,18 @@ def _window_args(window_size, is_causal: bool, qk_quant_gran: str, pv_accum_dtyp
         raise ValueError(f"window_size=({left}, {right}) with is_causal=True: right must be 0 or -1 (a causal row sees no key behind its diagonal)")
     if left == -1 and (is_causal or right == -1):
         return None                        # unbounded: the call without the keyword
+    return left, right
+
+
+def _window_args(window_size, is_causal: bool, qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs):
+    """``window_size=(left, right)`` (FlashAttention's convention, -1 = unbounded on that side) as ``(W, r)``: a row sees ``W`` keys up to and
+    including its diagonal (0: unbounded), the diagonal shifted right by ``r`` keys; None when there is no window.  Its argument errors are
+    checked before any work, on any device.  A window rides on the ``q_start`` route, so that route's restrictions hold, worded for this
+    keyword.  With ``is_causal=False`` and ``right >= 0`` the call runs the causal kernels with the diagonal ``right`` keys further right."""
+    pair = _window_pair(window_size, is_causal)
+    if pair is None:
+        return None
+    left, right = pair
     if not is_causal and right == -1:
         raise ValueError(f"window_size=({left}, -1) with is_causal=False: a bounded look-back needs right >= 0 (or is_causal=True)")
     _offset_route_restrictions("window_size", qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
@@ -543,6 +539,51 @@ def _q_start_tensor(q_start, kv_lens, B: int, Lq: int, Lk: int, device, shift: i
     if q_start.dtype == torch.int64:       # (offsets outside int32 are far outside [-Lq, Lk] either way: clamp before narrowing)
         q_start = q_start.clamp(-2 ** 31, 2 ** 31 - 1)
     return q_start.to(torch.int32).contiguous()
+
+
+class _KvFamily(NamedTuple):
+    """What the keywords of the ``kv_lens`` kernel family ask of a call (:func:`_kv_family_args`)."""
+    is_causal: bool        # the call's, or True under a window
+    window: int            # keys a row sees up to and including its diagonal (0: unbounded)
+    shift: int             # keys the diagonal lies further right (a non-causal window's ``right``)
+    gqa_pack: bool
+    splits: int            # key-range chunks (0: none)
+    with_lens: bool
+    with_start: bool
+    q_start: Any           # the caller's, or 0 under a window without offsets
+
+
+def _kv_family_args(q, k, tensor_layout, is_causal: bool, kv_lens, q_start, causal_align: str, window_size, pack_gqa, num_splits,
+                    qk_quant_gran: str, pv_accum_dtype: str, smooth_v: bool, kwargs) -> _KvFamily:
+    """The keywords of the ``kv_lens`` kernel family, resolved for ``sageattn_qk_int8_pv_fp8_cuda`` and ``sageattn_kvcache`` alike (``k``: K or
+    the cache's INT8 K, for its shape; the cache, which has no ``kv_lens`` keyword, passes None).  Their argument errors, checked before any
+    work and on any device, in this order: ``num_splits``, ``pack_gqa``, ``kv_lens``, ``window_size``, ``q_start`` / ``causal_align`` -- a
+    call that breaks two keywords' rules gets the earlier one's error, and a restriction of the route is worded for the first keyword that
+    asks for the route."""
+    route = (qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
+    splits = _num_splits_args(num_splits, q, k, tensor_layout, window_size, pack_gqa, *route)
+    gqa_pack = _pack_gqa_args(pack_gqa, q, k, tensor_layout, *route)
+    with_lens = _kv_lens_args(kv_lens, q, tensor_layout, *route)
+    win = _window_args(window_size, is_causal, *route)
+    window, shift = win if win is not None else (0, 0)
+    if win is not None:                    # the causal kernels, the diagonal `shift` keys further right; offsets 0 unless the caller places the rows
+        is_causal = True
+        if q_start is None and causal_align == "top_left":
+            q_start = 0
+    with_start = _q_start_args(q_start, causal_align, is_causal, q, *route)
+    return _KvFamily(is_causal, window, shift, gqa_pack, splits, with_lens, with_start, q_start)
+
+
+def _attn_kv_family(call: _KvFamily, q, lens, kv_lens, k_int8, v_image, v_scale, k_scale, tensor_layout, sm_scale, return_lse, head_dim_og,
+                    smooth_k, lse_correction):
+    """The attention of a call on the ``kv_lens`` entry, from its resolved keywords and quantised operands: ``lens`` are the int32 lengths the
+    kernel reads, ``kv_lens`` what ``causal_align='bottom_right'`` forms its offsets from (None: the padded key length).  Nothing here reads a
+    length or an offset on the host."""
+    B, _, Lq = _dims(q, tensor_layout)[:3]
+    start = _q_start_tensor(call.q_start, kv_lens, B, Lq, _dims(k_int8, tensor_layout)[2], q.device, call.shift) if call.with_start else None
+    o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, call.is_causal, _sm_log2(sm_scale), return_lse,
+                           kv_lens=lens, q_start=start, window=call.window, gqa_pack=call.gqa_pack, num_splits=call.splits)
+    return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
 
 
 @torch.compiler.disable
@@ -617,6 +658,17 @@ def _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
     return o
 
 
+def _refuse_kv_family_compiled(kv_lens, q_start, causal_align, window_size, pack_gqa, num_splits, why: str = "") -> None:
+    """The compiled op has no argument for the ``kv_lens`` family's keywords: a compiled call that ignored one would be a trap."""
+    for what, given in (("kv_lens is", kv_lens is not None),
+                        ("q_start / causal_align are", q_start is not None or causal_align != "top_left"),
+                        ("window_size is", window_size is not None),
+                        ("pack_gqa is", pack_gqa),
+                        ("num_splits is", num_splits is not None and num_splits != 1)):
+        if given:
+            raise ValueError(f"{what} not supported under torch.compile{why}")
+
+
 # ------------------------------------------------------------------------------------------------
 def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND", is_causal: bool = False,
              sm_scale: Optional[float] = None, return_lse: bool = False, kv_lens: Optional[torch.Tensor] = None, q_start=None,
@@ -633,16 +685,7 @@ def sageattn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
     See :func:`sageattn_qk_int8_pv_fp8_cuda`."""
     _check_shapes(q, k, v, tensor_layout)      # (again in the entry point called below: this one is in front of the device query)
     if torch.compiler.is_compiling():      # the device query is not traceable; the opaque op checks the device when it runs
-        if kv_lens is not None:            # (the compiled op has no such argument: a compiled call that ignored the lengths would be a trap)
-            raise ValueError("kv_lens is not supported under torch.compile")
-        if q_start is not None or causal_align != "top_left":
-            raise ValueError("q_start / causal_align are not supported under torch.compile")
-        if window_size is not None:
-            raise ValueError("window_size is not supported under torch.compile")
-        if pack_gqa:
-            raise ValueError("pack_gqa is not supported under torch.compile")
-        if num_splits is not None and num_splits != 1:
-            raise ValueError("num_splits is not supported under torch.compile")
+        _refuse_kv_family_compiled(kv_lens, q_start, causal_align, window_size, pack_gqa, num_splits)
         return sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
                                             return_lse=return_lse, pv_accum_dtype="fp32+fp32")
     arch = get_gcn_arch(q.device) if q.is_cuda else "cpu"
@@ -862,20 +905,12 @@ def _varlen_attend_f8(st: _VarlenState, two_level: bool, return_lse: bool):
 
 def _varlen_window_args(window_size, is_causal: bool, causal_align: str, pv_accum_dtype: str, max_seqlen_q, max_seqlen_k, kwargs) -> int:
     """``window_size=(left, right)`` of ``sageattn_qk_int8_pv_fp8_varlen`` as ``W``, the keys a row sees up to and including its bottom-right
-    diagonal (0: no window).  :func:`_window_args`' checks and wording where the two share a rule; the packed route's own restrictions
+    diagonal (0: no window).  The checks it shares with :func:`_window_args` are :func:`_window_pair`'s; the packed route's own restrictions
     behind them.  Checked before any work, on any device."""
-    if window_size is None:
+    pair = _window_pair(window_size, is_causal)
+    if pair is None:
         return 0
-    ok_int = lambda x: isinstance(x, int) and not isinstance(x, bool)
-    if not isinstance(window_size, (tuple, list)) or len(window_size) != 2 or not all(ok_int(x) for x in window_size):
-        raise ValueError(f"window_size must be a pair of ints (left, right), -1 = unbounded on that side (got {window_size!r})")
-    left, right = window_size
-    if left < -1 or right < -1:
-        raise ValueError(f"window_size=({left}, {right}): a side is -1 (unbounded) or a number of keys >= 0")
-    if is_causal and right not in (0, -1):
-        raise ValueError(f"window_size=({left}, {right}) with is_causal=True: right must be 0 or -1 (a causal row sees no key behind its diagonal)")
-    if left == -1 and (is_causal or right == -1):
-        return 0                           # unbounded: the call without the keyword
+    left, right = pair
     if not is_causal:
         raise ValueError(f"window_size=({left}, {right}) with is_causal=False is not supported on packed batches (the packed route has no operand "
                          f"for the diagonal's shift): is_causal=True with right 0 or -1")
@@ -1188,28 +1223,11 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     ValueError naming ``num_splits``, as do ``qo_len > 128``, a ``window_size`` that bounds the look-back, a value that is no int in
     ``[0, 255]`` nor ``"auto"`` and use under torch.compile."""
     if torch.compiler.is_compiling():
-        if kv_lens is not None:
-            raise ValueError("kv_lens is not supported under torch.compile (the compiled op takes the default routes)")
-        if q_start is not None or causal_align != "top_left":
-            raise ValueError("q_start / causal_align are not supported under torch.compile (the compiled op takes the default routes)")
-        if window_size is not None:
-            raise ValueError("window_size is not supported under torch.compile (the compiled op takes the default routes)")
-        if pack_gqa:
-            raise ValueError("pack_gqa is not supported under torch.compile (the compiled op takes the default routes)")
-        if num_splits is not None and num_splits != 1:
-            raise ValueError("num_splits is not supported under torch.compile (the compiled op takes the default routes)")
+        _refuse_kv_family_compiled(kv_lens, q_start, causal_align, window_size, pack_gqa, num_splits, " (the compiled op takes the default routes)")
         return _compiled_call("fp8", q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, pv_accum_dtype, smooth_k, smooth_v, return_lse, kwargs)
     _check_shapes(q, k, v, tensor_layout)
-    splits = _num_splits_args(num_splits, q, k, tensor_layout, window_size, pack_gqa, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
-    gqa_pack = _pack_gqa_args(pack_gqa, q, k, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)      # (in front of kv_lens's checks: its errors name it)
-    with_lens = _kv_lens_args(kv_lens, q, tensor_layout, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
-    win = _window_args(window_size, is_causal, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
-    window, shift = win if win is not None else (0, 0)
-    if win is not None:                    # the causal kernels, the diagonal `shift` keys further right; offsets 0 unless the caller places the rows
-        is_causal = True
-        if q_start is None and causal_align == "top_left":
-            q_start = 0
-    with_start = _q_start_args(q_start, causal_align, is_causal, q, qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
+    call = _kv_family_args(q, k, tensor_layout, is_causal, kv_lens, q_start, causal_align, window_size, pack_gqa, num_splits,
+                           qk_quant_gran, pv_accum_dtype, smooth_v, kwargs)
     exact = _split_exact_args(kwargs, qk_quant_gran, pv_accum_dtype, _dims(k, tensor_layout)[2])
     dtype = q.dtype
     _check_inputs(q, k, v)
@@ -1227,40 +1245,21 @@ def sageattn_qk_int8_pv_fp8_cuda(q, k, v, tensor_layout: str = "HND", is_causal:
     fuse_q = qk_quant_gran == "per_thread" and pv_accum_dtype != "fp32" and kwargs.get("fuse_q_quant", True)
     fused = _fused_prepass_wanted(k, tensor_layout, kwargs.get("fused_prepass"))
     folded = ops.fp8_folded(kwargs.get("fp8_scores"))
-    if with_lens:
-        # per-sample key lengths: the length-aware kernel sequence (mean -> K quantiser -> V statistics -> V image), then the KVLEN kernels;
-        # nothing here reads the lengths on the host (int64 is converted on the device)
-        lens = kv_lens.to(torch.int32).contiguous()
-        B_, _, Lq_ = _dims(q, tensor_layout)[:3]
-        start = _q_start_tensor(q_start, kv_lens, B_, Lq_, _dims(k, tensor_layout)[2], q.device, shift) if with_start else None
-        lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
-                                                                              return_lse, False, kv_lens=lens)
-        o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, q_start=start, window=window, gqa_pack=gqa_pack, num_splits=splits)
-        return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
-    if with_start:
-        # query offsets without key lengths: the plain pre-pass (the one-launch route included) and the same attention entry with lengths
-        # filled with kv_len -- full lengths give the plain call's bits
-        B_, _, Lq_ = _dims(q, tensor_layout)[:3]
-        Lk_ = _dims(k, tensor_layout)[2]
-        start = _q_start_tensor(q_start, None, B_, Lq_, Lk_, q.device, shift)
-        lens = torch.full((B_,), Lk_, dtype=torch.int32, device=q.device)
-        lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
-                                                                              return_lse, fused)
-        o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, q_start=start, window=window, gqa_pack=gqa_pack, num_splits=splits)
-        return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
-    if gqa_pack or splits:
-        # packed GQA groups / key-range chunks without lengths or offsets: the plain pre-pass and the kv_lens attention entry with lengths filled
-        # with kv_len, as above (is_causal: the top-left mask -- the split's causal kernels take offsets, and none means 0)
-        B_ = _dims(q, tensor_layout)[0]
-        lens = torch.full((B_,), _dims(k, tensor_layout)[2], dtype=torch.int32, device=q.device)
-        lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False,
-                                                                              return_lse, fused)
-        packed = dict(gqa_pack=True) if gqa_pack else {}
-        o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, _sm_log2(sm_scale), return_lse,
-                               kv_lens=lens, num_splits=splits, **packed)
-        return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
+    if call.with_lens or call.with_start or call.gqa_pack or call.splits:
+        # the kv_lens attention entry (under a window the call is causal: call.is_causal).  With kv_lens: the length-aware kernel sequence (mean ->
+        # K quantiser -> V statistics -> V image), never the one-launch pre-pass; int64 lengths are converted on the device.  Without (offsets,
+        # packed GQA groups, key-range chunks alone): the plain pre-pass and lengths filled with kv_len -- full lengths give the plain call's
+        # bits; is_causal without offsets is the top-left mask (the split's causal kernels take offsets, and none means 0).
+        if call.with_lens:
+            lens = kv_lens.to(torch.int32).contiguous()
+            prepass = dict(fused=False, kv_lens=lens)
+        else:
+            lens = torch.full((_dims(q, tensor_layout)[0],), _dims(k, tensor_layout)[2], dtype=torch.int32, device=q.device)
+            prepass = dict(fused=fused)
+        lse_correction, _, k_int8, k_scale, v_image, v_scale, _ = _prepass_kv(q, k, v, tensor_layout, "per_thread", 64, smooth_k, False, return_lse,
+                                                                              **prepass)
+        return _attn_kv_family(call, q, lens, kv_lens, k_int8, v_image, v_scale, k_scale, tensor_layout, sm_scale, return_lse, head_dim_og,
+                               smooth_k, lse_correction)
     if fuse_q:
         # default route: Q is quantised inside the attention kernel (same bits, no INT8 copy of Q in HBM).
         # (Running the V pre-pass on a side stream beside the K chain was measured and rejected: the two HBM-bound chains

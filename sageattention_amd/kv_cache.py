@@ -26,8 +26,6 @@ from .quant import _aligned, _dims, _dtype_code, _p, _stream, channel_mean_kvlen
 
 __all__ = ["QuantizedKVCache", "sageattn_kvcache"]
 
-_ROUTE = ("per_thread", "fp32+fp16", False, {})      # what the kv_lens route asks of a call: granularity, accumulation, smooth_v, kwargs
-
 
 def _layout_ok(tensor_layout) -> None:
     if tensor_layout not in ("HND", "NHD"):
@@ -206,24 +204,15 @@ def sageattn_kvcache(q: torch.Tensor, cache: QuantizedKVCache, tensor_layout: st
     if not cache._seeded:
         raise ValueError("the cache has no statistics yet: seed(k_mean, v_amax) or from_prefill(...) first")
     k_int8 = cache.k_int8 if tensor_layout == "HND" else cache.k_int8.permute(0, 2, 1, 3)      # (head-major storage, as the pre-pass's)
-    # the keywords' checks and meanings: sageattn_qk_int8_pv_fp8_cuda's, in its order
-    splits = core._num_splits_args(num_splits, q, k_int8, tensor_layout, window_size, pack_gqa, *_ROUTE)
-    gqa_pack = core._pack_gqa_args(pack_gqa, q, k_int8, tensor_layout, *_ROUTE)
-    win = core._window_args(window_size, is_causal, *_ROUTE)
-    window, shift = win if win is not None else (0, 0)
-    if win is not None:
-        is_causal = True
-        if q_start is None and causal_align == "top_left":
-            q_start = 0
-    with_start = core._q_start_args(q_start, causal_align, is_causal, q, *_ROUTE)
+    # the keywords' checks and meanings are sageattn_qk_int8_pv_fp8_cuda's: one resolver (no kv_lens keyword here; the route's fixed options)
+    call = core._kv_family_args(q, k_int8, tensor_layout, is_causal, None, q_start, causal_align, window_size, pack_gqa, num_splits,
+                                "per_thread", "fp32+fp16", False, {})
     torch.cuda.set_device(q.device)
     if sm_scale is None:
         sm_scale = D ** -0.5
-    start = core._q_start_tensor(q_start, cache.lens, B, Lq, cache.capacity, q.device, shift) if with_start else None
     smooth_k = cache.k_mean is not None
     lse_correction = None
     if smooth_k and return_lse:
         lse_correction = core._lse_correction(q, cache.k_mean.unsqueeze(1 if tensor_layout == "NHD" else 2), tensor_layout)
-    o, lse = core._attn_fused_q(_aligned(q, 8), k_int8, cache.v_image, cache.v_scale, cache.k_scale, tensor_layout, is_causal, core._sm_log2(sm_scale),
-                                return_lse, kv_lens=cache.lens, q_start=start, window=window, gqa_pack=gqa_pack, num_splits=splits)
-    return core._finish(o, lse, D, return_lse, smooth_k, lse_correction, sm_scale)
+    return core._attn_kv_family(call, q, cache.lens, cache.lens, k_int8, cache.v_image, cache.v_scale, cache.k_scale, tensor_layout, sm_scale,
+                                return_lse, D, smooth_k, lse_correction)

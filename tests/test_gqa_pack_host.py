@@ -116,9 +116,15 @@ def test_the_keyword_is_a_named_parameter_and_sageattn_forwards_it():
         assert par["pack_gqa"].default is None and list(par)[-1] == "kwargs"
         assert "pack_gqa" in fn.__doc__
     assert "pack_gqa=pack_gqa" in inspect.getsource(sc.sageattn)
-    src = inspect.getsource(sc.sageattn_qk_int8_pv_fp8_cuda)
-    assert src.index("_pack_gqa_args(") < src.index("_check_inputs(")             # (checked before any work)
-    assert src.count("gqa_pack=gqa_pack") == 2 and src.count("gqa_pack=True") == 1   # the with_lens / with_start branches, the plain one
+    q, k, v = _cpu_qkv(Lq=33)
+    with pytest.raises(ValueError, match="pack_gqa needs qo_len <= 32"):          # (checked before any work: not the input check's "cuda")
+        sc.sageattn_qk_int8_pv_fp8_cuda(q, k, v, pack_gqa=True)
+    q, k, v = _cpu_qkv()
+    for route in ROUTES:                                                          # with lengths, with offsets, alone: every route is told to pack
+        kw = dict(dict(is_causal=False, kv_lens=None, q_start=None, causal_align="top_left", window_size=None), **route)
+        call = sc._kv_family_args(q, k, "HND", kw["is_causal"], kw["kv_lens"], kw["q_start"], kw["causal_align"], kw["window_size"], True, None,
+                                  "per_thread", "fp32+fp16", False, {})
+        assert call.gqa_pack is True
 
 
 # ---------------------------------------------------------------------------------------------- C ABI: the flag

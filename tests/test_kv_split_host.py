@@ -135,8 +135,11 @@ def test_the_keyword_is_a_named_parameter_and_sageattn_forwards_it():
         assert par["num_splits"].default is None and list(par)[-1] == "kwargs"
         assert "num_splits" in fn.__doc__
     assert "num_splits=num_splits" in inspect.getsource(sc.sageattn)
-    src = inspect.getsource(sc.sageattn_qk_int8_pv_fp8_cuda)
-    assert src.index("_num_splits_args(") < src.index("_pack_gqa_args(") < src.index("_check_inputs(")      # checked before any work, first
+    q, k, v = _cpu_qkv(Lq=129)
+    with pytest.raises(ValueError, match="num_splits needs qo_len <= 128"):       # checked before any work (not the input check's "cuda") ...
+        sc.sageattn_qk_int8_pv_fp8_cuda(q, k, v, num_splits=2)
+    with pytest.raises(ValueError, match="num_splits needs qo_len <= 128"):       # ... and first: pack_gqa's rule (qo_len <= 32) is broken too
+        sc.sageattn_qk_int8_pv_fp8_cuda(q, k, v, num_splits=2, pack_gqa=True)
 
 
 def test_the_auto_plan():
