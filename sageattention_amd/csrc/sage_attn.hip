@@ -1,5 +1,5 @@
 // sage_attn.hip -- host-side dispatch of the attention launches: the work order of a launch (sage_work_order.h) and the choice of the
-// instantiation unit (sage_attn_parts.h; the kernels themselves are in sage_attn_kernel.h, compiled by sage_attn_d*_*.hip).
+// instantiation unit (sage_attn_form.h, sage_attn_parts.h; the kernels themselves are in sage_attn_kernel.h, compiled by sage_attn_d*_*.hip).
 #include "sage_common.h"
 #include "sage_kernels.h"
 #include "sage_attn_parts.h"
@@ -51,7 +51,7 @@ static int plan_grid(AttnParams &q, const AttnVariant &v)
     return grid;
 }
 
-// the routes that exist: what a variant asks of the parameter block and of its own fields beyond what the ladders of sage_attn_launch.h match on
+// the routes that exist: what a variant asks of the parameter block and of its own fields beyond what its form (attn_form, sage_attn_form.h) says
 static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLaunchOpts &o)
 {
     const bool varlen = p.cu_q != nullptr, per_thread = v.qf == 1 || v.qf == 2, per_block = v.qf == 3 || v.qf == 4;
@@ -88,20 +88,13 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     if (o.grid_out != nullptr) *o.grid_out = 0;
     if (nwork <= 0) return hipSuccess;
     if (!route_exists(p, v, o)) return hipErrorInvalidValue;
-    // the instantiation unit of (head_dim, PV format, FP8 score form, seeded / kv_lens / q_start / window / packed GQA groups / packed FP8 with the per-block Q quantiser, top-left, bottom-right or bottom-right with a window)
-    const bool d128 = v.head_dim == 128;
-    if (v.seeded && v.kv_lens) return d128 ? launch_attn_f8_kvsplit<128>(p, v, nwork, o) : launch_attn_f8_kvsplit<64>(p, v, nwork, o);
-    if (v.seeded) return d128 ? launch_attn_f8_seeded<128>(p, v, nwork, o) : launch_attn_f8_seeded<64>(p, v, nwork, o);
-    if (v.gqa_pack) return d128 ? launch_attn_f8_gpack<128>(p, v, nwork, o) : launch_attn_f8_gpack<64>(p, v, nwork, o);
-    if (v.window > 0 && v.kv_lens) return d128 ? launch_attn_f8_window<128>(p, v, nwork, o) : launch_attn_f8_window<64>(p, v, nwork, o);
-    if (v.q_start) return d128 ? launch_attn_f8_qstart<128>(p, v, nwork, o) : launch_attn_f8_qstart<64>(p, v, nwork, o);
-    if (v.kv_lens) return d128 ? launch_attn_f8_kvlens<128>(p, v, nwork, o) : launch_attn_f8_kvlens<64>(p, v, nwork, o);
-    if (v.bottom_right && v.window > 0) return d128 ? launch_attn_f8_varlen_br_window<128>(p, v, nwork, o) : launch_attn_f8_varlen_br_window<64>(p, v, nwork, o);
-    if (v.bottom_right) return d128 ? launch_attn_f8_varlen_br<128>(p, v, nwork, o) : launch_attn_f8_varlen_br<64>(p, v, nwork, o);
-    if (v.pv_fp8 && v.qf >= 3) return d128 ? launch_attn_f8_varlen<128>(p, v, nwork, o) : launch_attn_f8_varlen<64>(p, v, nwork, o);
-    if (!v.pv_fp8) return d128 ? launch_attn_part<128, false, true>(p, v, nwork, o) : launch_attn_part<64, false, true>(p, v, nwork, o);
-    if (o.fp8_folded) return d128 ? launch_attn_part<128, true, true>(p, v, nwork, o) : launch_attn_part<64, true, true>(p, v, nwork, o);
-    return d128 ? launch_attn_part<128, true, false>(p, v, nwork, o) : launch_attn_part<64, true, false>(p, v, nwork, o);
+    // the form the launch needs and the unit that holds it (sage_attn_form.h): one launcher per (unit, head size)
+    typedef hipError_t (*unit_launcher)(uint32_t, const AttnParams &, int, const AttnLaunchOpts &);
+#define SAGE_UNIT_ROW(U) {launch_attn_unit<UNIT_##U, 64>, launch_attn_unit<UNIT_##U, 128>},
+    static const unit_launcher launchers[UNIT_COUNT][2] = {SAGE_ATTN_UNITS(SAGE_UNIT_ROW)};
+#undef SAGE_UNIT_ROW
+    const AttnForm f = attn_form(p, v, o);
+    return launchers[unit_of(f)][f.D == 128](pack(f), p, nwork, o);
 }
 
 }  // namespace sage

@@ -1,5 +1,5 @@
-// sage_attn_d128_f16.hip -- instantiation unit of the attention kernel family (sage_attn_kernel.h): launch_attn_part<D, PV_FP8, SFOLD> = <128,false,true>
+// sage_attn_d128_f16.hip -- instantiation unit of the attention kernel family (sage_attn_kernel.h): launch_attn_unit<UNIT_F16, 128>
 #include "sage_attn_launch.h"
 namespace sage {
-template hipError_t launch_attn_part<128,false,true>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+template hipError_t launch_attn_unit<UNIT_F16, 128>(uint32_t, const AttnParams &, int, const AttnLaunchOpts &);
 }

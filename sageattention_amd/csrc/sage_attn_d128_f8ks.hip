@@ -1,7 +1,7 @@
-// sage_attn_d128_f8ks.hip -- instantiation unit of the attention kernel family (sage_attn_kernel.h): launch_attn_f8_kvsplit<128>
+// sage_attn_d128_f8ks.hip -- instantiation unit of the attention kernel family (sage_attn_kernel.h): launch_attn_unit<UNIT_F8KS, 128>
 // (the num_splits route's pass 2: the kv_lens / q_start kernels, unpacked and with packed GQA groups, over one key-range chunk each, seeded
 // running maximum, FP32 partials)
 #include "sage_attn_launch.h"
 namespace sage {
-template hipError_t launch_attn_f8_kvsplit<128>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+template hipError_t launch_attn_unit<UNIT_F8KS, 128>(uint32_t, const AttnParams &, int, const AttnLaunchOpts &);
 }

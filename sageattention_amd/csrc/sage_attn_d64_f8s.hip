@@ -1,6 +1,6 @@
-// sage_attn_d64_f8s.hip -- instantiation unit of the attention kernel family (sage_attn_kernel.h): launch_attn_f8_seeded<64>
+// sage_attn_d64_f8s.hip -- instantiation unit of the attention kernel family (sage_attn_kernel.h): launch_attn_unit<UNIT_F8S, 64>
 // (the exact split-KV route's pass 2: fused per-thread Q, FP8 PV two-level, exact score form, seeded running maximum, FP32 partials)
 #include "sage_attn_launch.h"
 namespace sage {
-template hipError_t launch_attn_f8_seeded<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+template hipError_t launch_attn_unit<UNIT_F8S, 64>(uint32_t, const AttnParams &, int, const AttnLaunchOpts &);
 }

@@ -1,6 +1,6 @@
-// sage_attn_d64_f8v.hip -- instantiation unit of the attention kernel family (sage_attn_kernel.h): launch_attn_f8_varlen<64>
+// sage_attn_d64_f8v.hip -- instantiation unit of the attention kernel family (sage_attn_kernel.h): launch_attn_unit<UNIT_F8V, 64>
 // (FP8 PV over a packed batch, per-block Q quantised in the prologue, the exact score form: sage_attn_*_pv_f8_varlen)
 #include "sage_attn_launch.h"
 namespace sage {
-template hipError_t launch_attn_f8_varlen<64>(const AttnParams &, const AttnVariant &, int, const AttnLaunchOpts &);
+template hipError_t launch_attn_unit<UNIT_F8V, 64>(uint32_t, const AttnParams &, int, const AttnLaunchOpts &);
 }

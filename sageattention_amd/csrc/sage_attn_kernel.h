@@ -37,6 +37,7 @@
 #pragma once
 #include "sage_common.h"
 #include "sage_kernels.h"
+#include "sage_attn_form.h"
 #include "sage_attn_parts.h"
 #include "sage_quant_math.h"
 #include "sage_work_order.h"
@@ -73,13 +74,6 @@
 #ifndef SAGE_ATTN_TRACE      // tools/attn_trace.py: wave 0 of every workgroup records 100 MHz time stamps of its phases
 #define SAGE_ATTN_TRACE 0    // (entry, geometry known, Q ready, first tile landed, key loop done, epilogue barrier, stores issued, stores acknowledged)
 #endif
-
-// __launch_bounds__ waves / SIMD the register allocator must allow: the software-pipelined loops carry two score tiles, which at D = 128 is
-// 2 waves (248 VGPRs); D = 64 fits 3 (167); the attn_mask variants 2.
-#define SAGE_MIN_WAVES(D, MASK) ((MASK) != 0 ? 2 : ((D) == 64 ? 3 : 2))
-// (the packed window's ticket kernel at D = 64 -- WINDOW, QSTART, no KVLEN, CPERS: the general iteration instantiated twice next to the ticket
-//  loop's state -- needs 4 VGPRs more than three waves leave, 172 against 168: it is built for 2 waves rather than with scratch)
-#define SAGE_MIN_WAVES_K(D, MASK, PACKED_WINDOW_TICKETS) (((PACKED_WINDOW_TICKETS) && (D) == 64) ? 2 : SAGE_MIN_WAVES(D, MASK))
 
 // asm text of the pipelined loops: two scores d0 / d1 from the bit patterns s0 / s1 of the QK^T accumulators, d = score * c - m (operands as
 // asm placeholders).  EXACT: the bias of the bit pattern is subtracted first (exact), then the FMA; FOLD (the FP8 opt-in variant): one FMA per
@@ -175,7 +169,6 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // (l = 0: the normalisation factor is 0, and the product is forced to zero so that a NaN in the sample's unused scale slots cannot reach it)
 // and lse = log2(0) + m = -inf.  (An exit of its own in front of the Q fragments -- a second way out of the item loop -- cost the D = 64
 // non-causal instantiations 5-8 spilled VGPRs under their three-waves limit wherever it was placed.)
-// (QSTART stands in front of KVLEN in the parameter list, which therefore still ends with the KVLEN flag.)
 // QSTART (a CAUSAL KVLEN kernel, units sage_attn_d{128,64}_f8q.hip): query row 0 of sample b stands at key position s_b = p.cu_qs[b] clamped to
 // [-p.Lq, p.Lk] (cu_qs is as free in a dense launch as cu_k), so row i attends to key j iff j <= s_b + i and j < len_b: s_b = 0 is the top-left
 // mask, s_b = len_b - Lq the bottom-right one.  It is the split routes' shift of the causal mask into a chunk's key coordinates with
@@ -188,8 +181,7 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // bottom-right alignment: p.cu_q != null, and the offset of sequence b is s_b = Lk_b - Lq_b, formed from the four cu_seqlens words the packed
 // branch has just loaded -- no operand of its own.  Everything above follows from kchunk0 = -s_b as it does for the dense kernels; a query block
 // wholly in front of key 0 (lim = 0) and every block of a sequence without keys run no tile and write o = +0, lse = -inf.
-// WINDOW (a QSTART kernel, units sage_attn_d{128,64}_f8w.hip; stands in front of QSTART in the parameter list, which therefore still ends with the
-// QSTART and KVLEN flags): row i additionally sees only the last W = p.window keys up to its diagonal, s_b + i - W < j <= s_b + i.
+// WINDOW (a QSTART kernel, units sage_attn_d{128,64}_f8w.hip): row i additionally sees only the last W = p.window keys up to its diagonal, s_b + i - W < j <= s_b + i.
 // A work item starts at the 64-key tile that holds the first key its first row sees (kc0: k_off, v_tile0 and ks_ptr shifted as the SEED branch
 // shifts them, Lk and kchunk0 in the shifted coordinates, so that loop bounds, steady tiles and masks follow as they do for QSTART) -- the tiles
 // in front of it are never requested.  Its first `nh` tiles (at most three) are those in which some row of the block is cut on the left: they run
@@ -201,8 +193,7 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // above, W = p.window, the same head tiles, second priming and masks; only the shift of the item's first key is written for the packed layouts
 // (V images and per-block k scales: one per 64-key tile, stride Hkv).  With the ticket loop (CPERS) the next item's ticket is requested behind
 // the LAST tile of the item whichever run that is -- the request stands behind the remainder loop, not inside a run.
-// GPACK (a KVLEN kernel, with or without QSTART / WINDOW; units sage_attn_d{128,64}_f8g.hip; stands behind QF in the parameter list, in front of every
-// flag older kernels' names end with): a decode-shaped call (p.Lq <= 32) packs the query heads of a GQA group four to a workgroup.  A work
+// GPACK (a KVLEN kernel, with or without QSTART / WINDOW; units sage_attn_d{128,64}_f8g.hip): a decode-shaped call (p.Lq <= 32) packs the query heads of a GQA group four to a workgroup.  A work
 // item is (batch b, kv head hk, group block gb); wave w serves query head hk * group + 4 gb + w and takes rows 0 .. Lq - 1 of that head as the
 // rows of its 32-row slab (row0 = 0 in every wave).  The head index and what follows from it alone -- q_off, o_off, the lse index -- are
 // per wave (wave-uniform: SGPRs); everything else is what block 0 of the unpacked call forms from qblk = 0: the loop bounds, the head tiles,
@@ -219,11 +210,33 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // The running maximum starts from the prefix maximum of pass 1's chunk maxima and the FP32 normalised partial and its log2-domain LSE are
 // stored per chunk; a chunk that holds no visible key -- past len_b, behind the block's diagonal, of an empty sample -- requests no tile and
 // gives o = +0, lse = -inf, the weight 0 of the merge.
-template <int D, bool PV_FP8, bool CAUSAL, bool KTHREAD, bool TWO_LEVEL, int NH, int MASK = 0, int QF = 0, bool GPACK = false, bool SFOLD = true,
-          bool CPERS = false, bool VROWS = false, bool SEED = false, bool WINDOW = false, bool QSTART = false, bool KVLEN = false>
-__global__ void __launch_bounds__(256, SAGE_MIN_WAVES_K(D, MASK, WINDOW && QSTART && !KVLEN && CPERS))
+// FORM: pack() of the kernel's AttnForm (sage_attn_form.h), which also holds the rules on which flags may meet, on the waves per SIMD the
+// register allocator must allow and on which kernels carry the ticket loop.
+template <uint32_t FORM>
+__global__ void __launch_bounds__(256, min_waves(unpack(FORM)))
 sage_attn_kernel(const AttnParams p_arg)
 {
+    // The form's fields under the names the body uses.  (static: the body's lambdas capture by reference, and a plain constexpr local that one of
+    // them passes on by reference becomes a captured stack slot -- folded away later, but sixteen D = 128 FP16-PV kernels then allocate their
+    // registers differently, 217 - 229 VGPRs where these give 219 - 226.)
+    static constexpr AttnForm F = unpack(FORM);
+    static_assert(pack(F) == FORM && valid(F), "not a form of the family: form_error() in sage_attn_form.h names the rule it breaks");
+    static constexpr int D = F.D;
+    static constexpr bool PV_FP8 = F.pv_fp8;
+    static constexpr bool CAUSAL = F.causal;
+    static constexpr bool KTHREAD = F.kthread;
+    static constexpr bool TWO_LEVEL = F.two_level;
+    static constexpr int NH = 1;                            // 64-key images per iteration: every member of the family runs 64-key iterations
+    static constexpr int MASK = F.mask;
+    static constexpr int QF = F.qf;
+    static constexpr bool GPACK = F.gpack;
+    static constexpr bool SFOLD = F.sfold;
+    // (F.cpers has no alias: its one reader is ticket_loop(F), PERS_OK below)
+    static constexpr bool VROWS = F.vrows;
+    static constexpr bool SEED = F.seed;
+    static constexpr bool WINDOW = F.window;
+    static constexpr bool QSTART = F.qstart;
+    static constexpr bool KVLEN = F.kvlen;
     // The parameter block is read through the kernarg segment pointer, and inside the persistent loop through a copy of that pointer the
     // compiler cannot see through (an empty asm): otherwise every scalar load of a parameter is hoisted out of the loop and stays live in
     // SGPRs across it (128 SGPRs and 16-400 VGPRs spilled in every instantiation).  AttnParams is the kernel's only explicit argument.
@@ -246,15 +259,6 @@ sage_attn_kernel(const AttnParams p_arg)
     using C = TileCfg<D, PV_FP8, NH>;
     constexpr int KT = C::KT;
     constexpr int NS = 2 * NH;                       // 32-key S^T sub-tiles per iteration
-    static_assert(!SEED || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS),
-                  "the seeded split: FP8 PV, fused per-thread Q, exact score form, dense");
-    static_assert(!KVLEN || (PV_FP8 && KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && (QF == 1 || QF == 2) && !CPERS && !VROWS),
-                  "per-sample key lengths: FP8 PV, fused per-thread Q, exact score form, dense");
-    static_assert(!(SEED && KVLEN) || (!WINDOW && QSTART == CAUSAL), "the kv_lens split: no window, and its causal kernels are the offset kernels");
-    static_assert(!QSTART || (CAUSAL && (KVLEN || (PV_FP8 && !KTHREAD && TWO_LEVEL && !SFOLD && MASK == 0 && QF >= 3 && !VROWS && !SEED))),
-                  "query offsets: the causal kv_lens kernels (dense, p.cu_qs), or a packed launch's bottom-right alignment (FP8 PV, per-block Q, two-level; with or without a window)");
-    static_assert(!WINDOW || QSTART, "the sliding window: the q_start kernels");
-    static_assert(!GPACK || KVLEN, "packed GQA groups: the kv_lens kernels (dense, p.Lq <= 32)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     // (wave index in an SGPR, lane index from v_mbcnt wherever it is needed: nothing derived from threadIdx.x has to stay in a VGPR across
@@ -276,7 +280,7 @@ sage_attn_kernel(const AttnParams p_arg)
     // (round 5: the packed / varlen route's CAUSAL launches over the device-built work list take the route too -- +2.2 ... 2.9 % at C4 -- through
     //  instantiations of their own (CPERS); dense causal launches lose 0.1 ... 7.5 % with tickets and the loop's mere presence costs the dense
     //  Triton-API causal kernel 1.3 %, so their instantiations stay without it: profiles/r5_pers_causal_probe.txt, r5_run_c_qf_pers_ab.txt)
-    constexpr bool PERS_OK = (!CAUSAL || CPERS) && MASK == 0 && !GPACK && !(SEED && KVLEN);      // (the kv_lens split: the ordinary launch alone, as GPACK)
+    constexpr bool PERS_OK = ticket_loop(F);
     const bool pers = PERS_OK && p.sched != nullptr;
     __shared__ int s_ticket[2];                 // (two slots, alternating: a wave may still be reading the previous ticket when wave 0 posts the next)
     int tpar = 0;

@@ -71,7 +71,7 @@ SAGE_HD bool work_item(const WorkOrder &w, int bid, int nwg, int nheads, int nqb
 SAGE_HD int plan_work_order(WorkOrder &w, int nheads, int nqblk, long kv_len, int head_dim, bool pv_fp8, int forced)
 {
     const int hpx = nheads / 8, left = nheads % 8;
-    const int wg_per_cu = head_dim == 64 ? 3 : 2;                 // SAGE_MIN_WAVES of the 128-row kernels
+    const int wg_per_cu = head_dim == 64 ? 3 : 2;                 // min_waves() of the 128-row kernels (sage_attn_form.h)
     const int slots = 32 * wg_per_cu;
     const int g_bal = (2 * slots + nqblk) / (nqblk + 1);
     const long head_bytes = kv_len * head_dim * (pv_fp8 ? 2 : 3);              // INT8 K + FP8 / FP16 V image

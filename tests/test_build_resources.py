@@ -10,7 +10,11 @@ import subprocess
 
 import pytest
 
+import sys
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_form as kf          # noqa: E402  (kernel name <-> the fields of its form, csrc/sage_attn_form.h)
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
@@ -65,11 +69,13 @@ def test_attention_kernels_do_not_spill():
     assert len(kernels) == 2 * (12 + 12 + 33)
     bad = {k: v for k, v in kernels.items() if v["VGPRs Spill"] > 0 or v["ScratchSize"] > 0}
     assert not bad, bad
-    d128 = [v for k, v in kernels.items() if "ILi128E" in k]
+    forms = {k: kf.decode(k) for k in kernels}
+    d128 = [v for k, v in kernels.items() if forms[k]["D"] == 128]
     assert d128 and all(v["Occupancy"] >= 2 for v in d128)
-    d64 = [v for k, v in kernels.items() if "ILi64E" in k]
-    assert d64 and all(v["Occupancy"] >= 3 for v in d64), d64
-    head = [v for k, v in kernels.items() if "ILi128ELb1ELb1ELb1ELb1E" in k]          # D=128, FP8 PV, causal, per-thread, two-level
+    d64 = [v for k, v in kernels.items() if forms[k]["D"] == 64]
+    assert d64 and len(d64) + len(d128) == len(kernels) and all(v["Occupancy"] >= 3 for v in d64), d64
+    head = [v for k, v in kernels.items()
+            if forms[k]["D"] == 128 and forms[k]["pv_fp8"] and forms[k]["causal"] and forms[k]["kthread"] and forms[k]["two_level"]]
     assert len(head) == 6                                                             # INT8 q + fp16 q + bf16 q, folded + exact
 
 

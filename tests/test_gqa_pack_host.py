@@ -233,7 +233,7 @@ def test_the_packed_grid_covers_every_head_once():
 @pytest.mark.skipif(not os.path.exists(tbr.HIPCC), reason="hipcc not installed")
 def test_gpack_units_build_within_the_family_targets():
     """The units are in the Makefile's SRCS; each holds eight kernels -- fp16 / bf16 q x {non-causal lengths, causal lengths, offsets, offsets
-    with a window} -- with the GPACK flag behind QF and the family's tail of flags: zero scratch, no spilled VGPR, D = 128 at two waves per
+    with a window} -- with the GPACK flag on top of the family's form: zero scratch, no spilled VGPR, D = 128 at two waves per
     SIMD, D = 64 at three."""
     mk = open(os.path.join(ROOT, "sageattention_amd", "csrc", "Makefile")).read()
     srcs = re.search(r"^SRCS\s*:=\s*(.*)$", mk, re.M).group(1).split()
@@ -247,14 +247,15 @@ def test_gpack_units_build_within_the_family_targets():
         d128 = "d128" in unit
         forms = set()
         for name, res in mine.items():
-            # D, FP8 PV, causal or not, per-thread k scales, two-level, NH 1, no mask, QF 1 / 2, GPACK, the exact form, no CPERS / VROWS / SEED ... KVLEN
-            m = re.search(r"sage_attn_kernelILi(\d+)ELb1ELb([01])ELb1ELb1ELi1ELi0ELi([12])ELb1ELb0ELb0ELb0ELb0ELb([01])ELb([01])ELb1EEEvNS_10AttnParamsE$", name)
-            assert m and int(m.group(1)) == (128 if d128 else 64), name
-            forms.add((m.group(2), m.group(3), m.group(4), m.group(5)))
+            # D, FP8 PV, causal or not, per-thread k scales, two-level, no mask, QF 1 / 2, GPACK, the exact form, no CPERS / VROWS / SEED ... KVLEN
+            f = tbr.kf.decode(name)
+            assert f["qf"] in (1, 2) and f == tbr.kf.form(128 if d128 else 64, pv_fp8=True, kthread=True, two_level=True, gpack=True, kvlen=True,
+                                                          causal=f["causal"], qf=f["qf"], window=f["window"], qstart=f["qstart"]), name
+            forms.add((f["causal"], f["qf"], f["window"], f["qstart"]))
             assert res["VGPRs Spill"] == 0 and res["ScratchSize"] == 0, (name, res)
             assert res["Occupancy"] >= (2 if d128 else 3) and res["VGPRs"] <= (256 if d128 else 168), (name, res)
         # (causal, QF, WINDOW, QSTART)
-        assert forms == {(c, f, w, s) for f in "12" for c, w, s in (("0", "0", "0"), ("1", "0", "0"), ("1", "0", "1"), ("1", "1", "1"))}, sorted(forms)
+        assert forms == {(c, f, w, s) for f in (1, 2) for c, w, s in ((False, False, False), (True, False, False), (True, False, True), (True, True, True))}, sorted(forms)
 
 
 @pytest.mark.skipif(not os.path.exists(tbr.HIPCC), reason="hipcc not installed")

@@ -131,7 +131,8 @@ def test_kvlens_units_build_within_the_family_targets():
         assert len(mine) == 4, (unit, sorted(mine))
         d128 = "d128" in unit
         for name, res in mine.items():
-            assert ("ILi128E" if d128 else "ILi64E") in name and name.endswith("ELb1EEEvNS_10AttnParamsE"), name      # (the KVLEN flag is the last argument)
+            f = tbr.kf.decode(name)      # (the fused per-thread Q FP8 kernels with KVLEN and nothing else; causal or not, fp16 / bf16 q)
+            assert f["qf"] in (1, 2) and f == tbr.kf.form(128 if d128 else 64, pv_fp8=True, kthread=True, two_level=True, kvlen=True, causal=f["causal"], qf=f["qf"]), name
             assert res["VGPRs Spill"] == 0 and res["ScratchSize"] == 0, (name, res)
             assert res["Occupancy"] >= (2 if d128 else 3) and res["VGPRs"] <= (256 if d128 else 168), (name, res)
 

@@ -377,7 +377,7 @@ def test_pass1_and_pass2_agree_on_the_tiles_of_a_chunk():
 @pytest.mark.skipif(not os.path.exists(tbr.HIPCC), reason="hipcc not installed")
 def test_kv_split_units_build_within_the_family_targets():
     """The units are in the Makefile's SRCS and cross-compile for gfx950; each holds eight kernels -- fp16 / bf16 q x {non-causal lengths, causal
-    offsets} x {unpacked, packed} -- whose names end as the KVLEN kernels' do, with the SEED flag set: zero scratch, no spilled VGPR or SGPR,
+    offsets} x {unpacked, packed} -- whose forms are the KVLEN kernels' with the SEED flag set: zero scratch, no spilled VGPR or SGPR,
     D = 128 at two waves per SIMD, D = 64 at three."""
     mk = open(os.path.join(ROOT, "sageattention_amd", "csrc", "Makefile")).read()
     srcs = re.search(r"^SRCS\s*:=\s*(.*)$", mk, re.M).group(1).split()
@@ -391,14 +391,14 @@ def test_kv_split_units_build_within_the_family_targets():
         d128 = "d128" in unit
         forms = set()
         for name, res in mine.items():
-            # D, FP8 PV, causal or not, per-thread k scales, two-level, NH 1, no mask, QF 1 / 2, GPACK or not, the exact form, no CPERS / VROWS, SEED, no WINDOW, QSTART = causal, KVLEN
-            m = re.search(r"sage_attn_kernelILi(\d+)ELb1ELb([01])ELb1ELb1ELi1ELi0ELi([12])ELb([01])ELb0ELb0ELb0ELb1ELb0ELb([01])ELb1EEEvNS_10AttnParamsE$", name)
-            assert m and int(m.group(1)) == (128 if d128 else 64), name
-            assert m.group(2) == m.group(5), name
-            forms.add((m.group(2), m.group(3), m.group(4)))
+            # D, FP8 PV, causal or not, per-thread k scales, two-level, no mask, QF 1 / 2, GPACK or not, the exact form, no CPERS / VROWS, SEED, no WINDOW, QSTART = causal, KVLEN
+            f = tbr.kf.decode(name)
+            assert f["qf"] in (1, 2) and f == tbr.kf.form(128 if d128 else 64, pv_fp8=True, kthread=True, two_level=True, seed=True, kvlen=True,
+                                                          causal=f["causal"], qstart=f["causal"], qf=f["qf"], gpack=f["gpack"]), name
+            forms.add((f["causal"], f["qf"], f["gpack"]))
             assert res["VGPRs Spill"] == 0 and res["SGPRs Spill"] == 0 and res["ScratchSize"] == 0, (name, res)
             assert res["Occupancy"] >= (2 if d128 else 3) and res["VGPRs"] <= (256 if d128 else 168), (name, res)
-        assert forms == {(c, f, g) for c in "01" for f in "12" for g in "01"}, sorted(forms)       # (causal, QF, GPACK)
+        assert forms == {(c, f, g) for c in (False, True) for f in (1, 2) for g in (False, True)}, sorted(forms)       # (causal, QF, GPACK)
 
 
 @pytest.mark.skipif(not os.path.exists(tbr.HIPCC), reason="hipcc not installed")

@@ -287,15 +287,16 @@ def test_packed_br_units_build_within_the_family_targets():
         mine = {k: v for k, v in rep.items() if "sage_attn_kernel" in k}
         assert len(mine) == 4, (unit, sorted(mine))
         d128 = "d128" in unit
+        forms = {name: tbr.kf.decode(name) for name in mine}
         for name, res in mine.items():
-            # D, FP8 PV, causal, per-block k scales, two-level, NH 1, no mask ... and the last three flags: no WINDOW, QSTART, no KVLEN
-            assert ("ILi128ELb1ELb1ELb0ELb1ELi1ELi0E" if d128 else "ILi64ELb1ELb1ELb0ELb1ELi1ELi0E") in name, name
-            assert name.endswith("ELb0ELb0ELb0ELb1ELb0EEEvNS_10AttnParamsE"), name
+            # D, FP8 PV, causal, per-block k scales, two-level, no mask, the exact form ... no WINDOW, QSTART, no KVLEN; QF 3 / 4 and CPERS or not
+            f = forms[name]
+            assert f == tbr.kf.form(128 if d128 else 64, pv_fp8=True, causal=True, two_level=True, qstart=True, qf=f["qf"], cpers=f["cpers"]), name
             assert res["VGPRs Spill"] == 0 and res["ScratchSize"] == 0, (name, res)
             assert res["Occupancy"] >= (2 if d128 else 3) and res["VGPRs"] <= (256 if d128 else 168), (name, res)
         # QF 3 and 4 (fp16, bf16), the exact score form, each with CPERS and without
-        assert {(("ELi3ELb0" in n), ("ELb0ELb1ELb0ELb0ELb0ELb1ELb0EEEv" in n)) for n in mine} == {(a, b) for a in (True, False) for b in (True, False)}, sorted(mine)
-        assert all(("ELi3ELb0" in n) != ("ELi4ELb0" in n) for n in mine), sorted(mine)
+        assert {(f["qf"] == 3, f["cpers"]) for f in forms.values()} == {(a, b) for a in (True, False) for b in (True, False)}, sorted(mine)
+        assert all((f["qf"] == 3) != (f["qf"] == 4) for f in forms.values()), sorted(mine)
 
 
 @pytest.mark.skipif(not os.path.exists(tbr.HIPCC), reason="hipcc not installed")

@@ -267,12 +267,14 @@ def test_window_units_build_within_the_family_targets():
         mine = {k: v for k, v in rep.items() if "sage_attn_kernel" in k}
         assert len(mine) == 2, (unit, sorted(mine))
         d128 = "d128" in unit
+        forms = {name: tbr.kf.decode(name) for name in mine}
         for name, res in mine.items():
-            # D, FP8 PV, causal, per-thread, two-level ... and the last three flags: WINDOW, QSTART, KVLEN
-            assert ("ILi128ELb1ELb1ELb1ELb1E" if d128 else "ILi64ELb1ELb1ELb1ELb1E") in name and name.endswith("ELb0ELb1ELb1ELb1EEEvNS_10AttnParamsE"), name
+            # D, FP8 PV, causal, per-thread, two-level, the exact form ... WINDOW, QSTART, KVLEN and nothing else
+            assert forms[name] == tbr.kf.form(128 if d128 else 64, pv_fp8=True, causal=True, kthread=True, two_level=True, window=True, qstart=True,
+                                              kvlen=True, qf=forms[name]["qf"]), name
             assert res["VGPRs Spill"] == 0 and res["ScratchSize"] == 0, (name, res)
             assert res["Occupancy"] >= (2 if d128 else 3) and res["VGPRs"] <= (256 if d128 else 168), (name, res)
-        assert {("ELi1ELb0" in n, "ELi2ELb0" in n) for n in mine} == {(True, False), (False, True)}, sorted(mine)      # (QF 1 and 2: fp16, bf16)
+        assert {f["qf"] for f in forms.values()} == {1, 2}, sorted(mine)      # (QF 1 and 2: fp16, bf16)
 
 
 @pytest.mark.skipif(not os.path.exists(tbr.HIPCC), reason="hipcc not installed")
