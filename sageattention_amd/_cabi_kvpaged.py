@@ -1,0 +1,45 @@
+"""ctypes binding of the paged KV cache's entry points (include/sage_kvpaged_gfx950.h), exported by the same ``libsage_gfx950.so``.
+
+A binding of its own beside :mod:`_cabi` and :mod:`_cabi_kvcache`, whose symbol tables and ABI versions stay what their headers say.  This one
+loads after ``_cabi.load()`` (one library handle) and, like them, raises if the library does not match -- there is no fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+from ctypes import c_float, c_int, c_int64, c_void_p
+
+from . import _cabi
+
+ABI_VERSION = 1       # SAGE_KVPAGED_ABI_VERSION
+
+# every symbol include/sage_kvpaged_gfx950.h declares: name -> (restype, argtypes)
+_P, _I, _L, _F = c_void_p, c_int, c_int64, c_float
+SYMBOLS = {
+    "sage_kvpaged_abi_version": (c_int, []),
+    "sage_kvpaged_append": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _I,
+                                    _P, _L, _I, _I, _I, _P]),
+    "sage_kvpaged_attn": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I,
+                                  _L, _L, _L, _L, _L, _L, _L, _L, _L, _I, _F, _I, _I, _P, _P]),
+}
+
+_bound = False
+
+
+def load() -> ctypes.CDLL:
+    """The library of ``_cabi.load()`` with the paged cache's entry points bound (once)."""
+    global _bound
+    lib = _cabi.load()
+    if _bound:
+        return lib
+    for name, (res, args) in SYMBOLS.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise _cabi.SageLibraryError(f"{_cabi.LIB_PATH} does not export {name}") from e
+        fn.restype = res
+        fn.argtypes = args
+    got = lib.sage_kvpaged_abi_version()
+    if got != ABI_VERSION:
+        raise _cabi.SageLibraryError(f"paged KV cache ABI version mismatch: library {got}, binding {ABI_VERSION}")
+    _bound = True
+    return lib

@@ -78,6 +78,10 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
     // packed GQA groups: the kv_lens family (above: fused per-thread Q, FP8 PV, the exact score form, dense, no split), a group to pack and
     // no more query rows than one wave's slab holds
     if (v.gqa_pack && (!v.kv_lens || p.Lq > 32 || p.group < 2 || p.nqblk != 1)) return false;
+    // a pool of pages behind a block table: the kv_lens family without the split; whole pages of 64 << page_shift keys, p.Lk the logical capacity
+    if (v.paged != nullptr && (!v.kv_lens || v.seeded || p.kv_split > 1 || v.paged->block_table == nullptr || v.paged->page_shift < 0 ||
+                               v.paged->page_shift > 20 || v.paged->num_pages < 1 || v.paged->max_pages < 1 ||
+                               (long)p.Lk != ((long)v.paged->max_pages << (6 + v.paged->page_shift)) || p.nks != (4 << v.paged->page_shift))) return false;
     return true;
 }
 
@@ -94,6 +98,11 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     static const unit_launcher launchers[UNIT_COUNT][2] = {SAGE_ATTN_UNITS(SAGE_UNIT_ROW)};
 #undef SAGE_UNIT_ROW
     const AttnForm f = attn_form(p, v, o);
+    if (v.paged != nullptr) {     // the paged kernel of the same form: same grid, the ordinary dispatch
+        p.sched = nullptr;
+        return f.gpack ? (f.D == 128 ? launch_attn_paged_units<128, SAGE_PAGED_G_UNITS> : launch_attn_paged_units<64, SAGE_PAGED_G_UNITS>)(pack(f), p, *v.paged, nwork, o)
+                       : (f.D == 128 ? launch_attn_paged_units<128, SAGE_PAGED_UNITS> : launch_attn_paged_units<64, SAGE_PAGED_UNITS>)(pack(f), p, *v.paged, nwork, o);
+    }
     return launchers[unit_of(f)][f.D == 128](pack(f), p, nwork, o);
 }
 

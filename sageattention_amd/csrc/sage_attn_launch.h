@@ -13,8 +13,9 @@ namespace sage {
 // workgroups the device holds of THIS kernel is probed once per kernel and device (both lock-free: a race repeats the idempotent probe).
 constexpr int kPersistMinRounds = 12;
 
-template <auto KERN>
-static hipError_t launch_kernel(int lds, const AttnParams &p, int nwork, const AttnLaunchOpts &l, bool persist_ok)
+// (extra: kernel arguments behind the parameter block -- the paged kernels' PagedArgs)
+template <auto KERN, class... Extra>
+static hipError_t launch_kernel(int lds, const AttnParams &p, int nwork, const AttnLaunchOpts &l, bool persist_ok, const Extra &...extra)
 {
     static std::atomic<unsigned long long> lds_done{0};      // bit per device ordinal (mod 64)
     static std::atomic<int> slots_of[64];                    // per device ordinal (mod 64): 0 = not probed yet, else 1 + resident workgroups
@@ -61,7 +62,7 @@ static hipError_t launch_kernel(int lds, const AttnParams &p, int nwork, const A
         }
     }
     if (l.grid_out != nullptr) *l.grid_out = grid;
-    hipLaunchKernelGGL(KERN, dim3(grid), dim3(256), lds, l.stream, pp);
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(256), lds, l.stream, pp, extra...);
     return hipGetLastError();
 }
 
@@ -88,6 +89,22 @@ template <AttnUnit U, int D>
 hipError_t launch_attn_unit(uint32_t form, const AttnParams &p, int nwork, const AttnLaunchOpts &l)
 {
     return launch_among(typename UnitForms<U, D>::type{}, form, p, nwork, l);
+}
+
+// The paged units sage_attn_d{128,64}_{f8p,f8pg}.hip: the paged kernels (sage_attn_paged_kernel) of exactly the forms of the named units' lists --
+// instantiated from those lists, nothing restated -- through the same launch path; never the ticket route (AttnParams::sched is ignored).
+template <uint32_t... F>
+static bool launch_paged_among(Forms<F...>, uint32_t want, const AttnParams &p, const PagedArgs &g, int nwork, const AttnLaunchOpts &l, hipError_t &e)
+{
+    return ((want == F && ((e = launch_kernel<sage_attn_paged_kernel<F>>(TileCfg<unpack(F).D, unpack(F).pv_fp8, 1>::LDS_BYTES, p, nwork, l, false, g)), true)) || ...);
+}
+
+template <int D, AttnUnit... U>
+hipError_t launch_attn_paged_units(uint32_t form, const AttnParams &p, const PagedArgs &g, int nwork, const AttnLaunchOpts &l)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)(launch_paged_among(typename UnitForms<U, D>::type{}, form, p, g, nwork, l, e) || ...);
+    return e;
 }
 
 }  // namespace sage

@@ -70,6 +70,13 @@
                 cs[0] = sm26 * (qsc * ksc[0][0]);
                 cs[1] = KTHREAD ? sm26 * (qsc * ksc[0][1]) : cs[0];
                 float alpha_p = 1.0f;            // rescale owed to O before the pending PV (kept out of the iteration's main block)
+                // (PAGED) the pages of tiles it + 1 (its K scales are loaded in the body) and it + 2 (its DMA is issued at the body's top), in SGPRs: one
+                // lookup per tile, issued a tile ahead of its first use -- next to the scale loads -- so that the wait at the top of the next body covers it
+                [[maybe_unused]] int pg_n1 = 0, pg_n2 = 0;
+                if constexpr (PAGED) {
+                    pg_n1 = page_of(it + 1 < ntk_all ? it + 1 : ntk_all - 1);
+                    pg_n2 = page_of(it + 2 < ntk_all ? it + 2 : ntk_all - 1);
+                }
                 [[maybe_unused]] int cmy_row_d = 0;                      // DIAG_PIPE: the lane's row in the chunk's key coordinates, formed behind the loops
                 constexpr int kMaskedScore = (int)0xFF000000;           // bit pattern of a score behind the diagonal: below every INT32 score pattern, -1.7e38 as a float
                 auto rescale = [&]() {
@@ -102,8 +109,14 @@
                         // inst_offset advances the global and the LDS address together, so piece 1 reuses piece 0's M0.
                         // (KIND 3: piece 1's clamped offset minus its inst_offset can be negative, and the VGPR offset of the SGPR-base form is unsigned:
                         //  base 1 KiB down, offsets 1 KiB up)
-                        const unsigned char *ktp = kbase + (long)(it + 2) * KT * p.k_sl - (KIND == 3 ? 1024 : 0);
-                        const unsigned char *vtp = vbase + (v_tile0 + (long)(it + 2) * v_tstride) * (long)C::V_IMG_BYTES + wave * (VP / 4) * 1024;
+                        const unsigned char *ktp, *vtp;
+                        if constexpr (PAGED) {
+                            ktp = k_tile(it + 2, pg_n2) - (KIND == 3 ? 1024 : 0);
+                            vtp = vbase + v_tile(it + 2, pg_n2) * (long)C::V_IMG_BYTES + wave * (VP / 4) * 1024;
+                        } else {
+                        ktp = kbase + (long)(it + 2) * KT * p.k_sl - (KIND == 3 ? 1024 : 0);
+                        vtp = vbase + (v_tile0 + (long)(it + 2) * v_tstride) * (long)C::V_IMG_BYTES + wave * (VP / 4) * 1024;
+                        }
                         const unsigned ldk = lds_base + nn * C::STAGE_BYTES + wave * (KP / 4) * 1024;
                         const unsigned ldv = lds_base + nn * C::STAGE_BYTES + C::K_TILE_BYTES + wave * (VP / 4) * 1024;
                         unsigned keep;
@@ -116,6 +129,10 @@
                             k0 = k0 + 1024u - (unsigned)((r0 > rmax ? r0 - rmax : 0) * (int)p.k_sl);
                             if constexpr (KP / 4 == 2) k1m = k1m + 1024u - (unsigned)((r1 > rmax ? r1 - rmax : 0) * (int)p.k_sl);
                         }
+                        // (PAGED: the bases are fresh scalar arithmetic on a loaded page id; should the compiler form a part of it on the VALU and move
+                        //  it over, a VMEM instruction reading that SGPR needs five wait states, which nothing pads inside a string: a statement of
+                        //  nops that takes both bases as operands, so that they are in their SGPRs in front of it)
+                        if constexpr (PAGED) asm volatile("s_nop 4" : : "s"(ktp), "s"(vtp));
                         if constexpr (KP / 4 == 2)
                             asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\t"
                                          "global_load_lds_dwordx4 %1, %3\n\tglobal_load_lds_dwordx4 %2, %3 offset:1024\n\t"
@@ -144,9 +161,18 @@
                     [[maybe_unused]] float ks4[4];
                     if constexpr (!HAS_NEXT) {
                     } else if constexpr (KTHREAD && SAGE_KSEL) {
-                        const long tb = (long)((it + 1) >> p.ks_shift) * ks_tstride;      // (whole tiles only in this loop: it + 1 < ntk_all)
+                        long tb;
+                        if constexpr (PAGED) tb = ks_slot(it + 1, pg_n1);
+                        else
+                        tb = (long)((it + 1) >> p.ks_shift) * ks_tstride;      // (whole tiles only in this loop: it + 1 < ntk_all)
                         ks4[0] = ks_c[tb]; ks4[1] = ks_c[tb + 1]; ks4[2] = ks_c[tb + 2]; ks4[3] = ks_c[tb + 3];
                     } else load_kscales(it + 1, ksc_next);
+                    // (PAGED tested on its own, outside the conditions that depend on `kind`: what a generic lambda names under a condition that
+                    //  depends on its parameter is captured whatever the condition turns out to be, and the unpaged kernels' closure must not grow)
+                    if constexpr (PAGED) {
+                        if constexpr (HAS_NEXT) pg_n1 = pg_n2;
+                        if constexpr (HAS_NEXT && HAS_DMA) pg_n2 = page_of(it + 3 < ntk_all ? it + 3 : ntk_all - 1);
+                    }
                     v4i kfa[C::KSTEPS], kfb[C::KSTEPS];
                     if constexpr (HAS_NEXT) {
 #pragma unroll
@@ -312,6 +338,7 @@
                         cs[0] = sm26 * (qsc * ksc_next[0][0]);
                         cs[1] = KTHREAD ? sm26 * (qsc * ksc_next[0][1]) : cs[0];
                     }
+                    if constexpr (PAGED) if constexpr (HAS_DMA) asm volatile("" : "+s"(pg_n2));      // (the entry is in its SGPR here, where the K scales are waited for: not sunk to its use behind the next body's top)
                     alpha_p = alpha;
                     it++;
                 };
@@ -382,7 +409,10 @@
                 rescale();
 #pragma unroll
                 for (int dt = 0; dt < C::DT; dt++) A_PV(o[dt], vf[dt], pA);
-                if (it < n_iters) load_kscales(it, ksc);           // (the loop carried the products, not the k scales: the general iterations start from these)
+                // (PAGED: fetched whether or not an iteration follows -- load_kscales clamps to the last tile there is, whose table entry is one the
+                //  item may read -- so that the prologue's two VGPRs of k scales are dead across the loop: under a condition they stay live as far as
+                //  the compiler can tell, and the D = 64 paged kernels have no register to spare under their three-waves limit)
+                if (PAGED || it < n_iters) load_kscales(it, ksc);           // (the loop carried the products, not the k scales: the general iterations start from these)
                 asm volatile("s_nop 15\n\ts_nop 15\n\ts_waitcnt lgkmcnt(0)" : "+v"(sA[0]), "+v"(sA[1])::"memory");   // (sA as operand: its readers stay below)
                 __builtin_amdgcn_s_barrier();
             }

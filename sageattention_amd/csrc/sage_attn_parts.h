@@ -16,4 +16,15 @@ hipError_t launch_attn_unit(uint32_t form, const AttnParams &p, int nwork, const
 SAGE_ATTN_UNITS(SAGE_UNIT_EXTERN)
 #undef SAGE_UNIT_EXTERN
 
+// the paged kernels of the forms of units U... (sage_attn_launch.h): sage_attn_d{128,64}_f8p.hip holds those of F8K / F8Q / F8W,
+// sage_attn_d{128,64}_f8pg.hip those of F8G; hipErrorInvalidValue if none of the lists holds `form`
+template <int D, AttnUnit... U>
+hipError_t launch_attn_paged_units(uint32_t form, const AttnParams &p, const PagedArgs &g, int nwork, const AttnLaunchOpts &l);
+#define SAGE_PAGED_UNITS UNIT_F8K, UNIT_F8Q, UNIT_F8W
+#define SAGE_PAGED_G_UNITS UNIT_F8G
+extern template hipError_t launch_attn_paged_units<128, SAGE_PAGED_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_paged_units<64, SAGE_PAGED_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_paged_units<128, SAGE_PAGED_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_paged_units<64, SAGE_PAGED_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
+
 }  // namespace sage

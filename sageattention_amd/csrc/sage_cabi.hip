@@ -1,6 +1,7 @@
 // sage_cabi.hip -- extern "C" entry points declared in include/sage_gfx950.h.
 // Validates arguments, fills the kernel parameter blocks, launches on the caller's stream.
 #include "../../include/sage_gfx950.h"
+#include "../../include/sage_kvpaged_gfx950.h"
 #include "sage_common.h"
 #include "sage_kernels.h"
 #include "sage_work_order.h"
@@ -141,6 +142,7 @@ struct AttnCall {
                                      // (sage_attn_fused_q_pv_f8_kvlens) that takes per-sample query offsets: those arrive in the attributes
                                      // (SageLaunchAttr::q_start, read by attn_run), so they have no field here
     int kv_split;                    // > 1: the (inexact) split, the chunks folded into Hq / Hkv by the entry point
+    const sage::PagedArgs *paged;    // sage_kvpaged_attn: k / v / k_scale are a pool of pages behind a block table (with kv_lens; Lk = the logical capacity)
     int is_causal, gran, q_warp, pv_accum, q_dtype, out_dtype;
     float sm_scale_log2, q_premul;
     void *stream; const SageLaunchAttr *attr;
@@ -252,7 +254,15 @@ int attn_run(const AttnCall &c)
     const bool int8q = c.q_form == Q_INT8, per_thread = c.q_form == Q_FUSED_THREAD, per_block = c.q_form == Q_FUSED_BLOCK;
     const bool fp8 = c.pv_fp8, varlen = c.varlen, split = c.kv_split > 1;
     LaunchAttr la;
-    if (const int rc = read_attr(c.attr, c.stream, c.mask == nullptr && !split, la)) return rc;     // (masked and split launches take no launch workspace)
+    // (a pool of pages: what it does not take is refused by name, in front of everything else about the attributes)
+    if (c.paged != nullptr && c.attr != nullptr && c.attr->struct_bytes >= 8) {
+        const unsigned f = c.attr->flags;
+        SAGE_REQUIRE(!(f & (SAGE_ATTR_KV_SPLIT | (0xffu << SAGE_ATTR_KV_SPLIT_SHIFT))),
+                     "sage_kvpaged_attn: SAGE_ATTR_KV_SPLIT is not supported on a paged cache (pass 1 and the split's kernels do not look pages up)");
+        SAGE_REQUIRE(!(f & SAGE_ATTR_FP8_FOLDED_SCORES), "sage_kvpaged_attn: SAGE_ATTR_FP8_FOLDED_SCORES is not supported on a paged cache (the exact score form only)");
+        SAGE_REQUIRE(!(f & SAGE_ATTR_FORCE_PERSISTENT), "sage_kvpaged_attn: SAGE_ATTR_FORCE_PERSISTENT is not supported on a paged cache (the ordinary dispatch only)");
+    }
+    if (const int rc = read_attr(c.attr, c.stream, c.mask == nullptr && !split && c.paged == nullptr, la)) return rc;     // (masked, split and paged launches take no launch workspace)
     // ---- the routes a Q form admits
     if (c.kv_lens == nullptr) SAGE_REFUSE_KV_SPLIT(la);
     SAGE_REQUIRE(la.kv_split_flag || la.kv_split == 0, "SAGE_ATTR_KV_SPLIT: a chunk count (%d in flags bits 16-23) without the bit", la.kv_split);
@@ -328,6 +338,7 @@ int attn_run(const AttnCall &c)
     p.sched = la.ws; p.trace = la.trace; p.trace_wgs = la.trace_wgs;
     if (c.mask != nullptr) { p.mask = c.mask->ptr; p.m_sb = c.mask->sb; p.m_sh = c.mask->sh; p.m_sq = c.mask->sq; p.m_sk = c.mask->sk; v.mask_kind = c.mask->kind; }
     if (c.kv_lens != nullptr) { p.cu_k = c.kv_lens; v.kv_lens = true; }
+    if (c.paged != nullptr) { v.paged = c.paged; p.nks = 4 << c.paged->page_shift; }      // (the scale slots of ONE page; p.Lk is the logical capacity)
     if (la.q_start != nullptr) { p.cu_qs = la.q_start; v.q_start = true; }
     p.window = v.window = la.window;
     v.bottom_right = la.bottom_right;
@@ -338,7 +349,7 @@ int attn_run(const AttnCall &c)
     v.qf = int8q ? 0 : sage::attn_qf(per_block, c.q_dtype);
     if (la.kv_split_flag) return kv_split_run(c, la, p, v);
     return check_launch(sage::launch_attention(p, v, la.opts), int8q ? "sage_attn launch" : per_block ? "sage_attn_fused_qblock launch" :
-                        c.kv_lens != nullptr ? "sage_attn_fused_q_pv_f8_kvlens launch" : "sage_attn_fused_q launch");
+                        c.paged != nullptr ? "sage_kvpaged_attn launch" : c.kv_lens != nullptr ? "sage_attn_fused_q_pv_f8_kvlens launch" : "sage_attn_fused_q launch");
 }
 
 }  // namespace
@@ -1034,6 +1045,36 @@ SAGE_API int sage_attn_fused_q_pv_f8_kvlens(const void *q, const int8_t *k, cons
     c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
     c.q = q; c.k = k; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.v_mean = v_mean; c.kv_lens = kv_lens;
     c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = Lk; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
+}
+
+// sage_attn_fused_q_pv_f8_kvlens on a pool of pages (include/sage_kvpaged_gfx950.h): the same call, Lk = the logical capacity, the paged kernels
+SAGE_KVPAGED_API int sage_kvpaged_attn(const void *q, const int8_t *k_int8, const void *v_image, void *o, float *lse,
+                                       const float *k_scale, const float *v_scale, const int32_t *kv_lens,
+                                       const int32_t *block_table, int64_t bt_stride, int num_pages, int page_size, int max_pages_per_seq,
+                                       int B, int Hq, int Hkv, int Lq, int D,
+                                       int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                       int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                                       int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
+{
+    SAGE_REQUIRE(q && k_int8 && v_image && o && k_scale && v_scale, "sage_kvpaged_attn: null tensor pointer (only lse may be null)");
+    SAGE_REQUIRE(kv_lens, "sage_kvpaged_attn: null kv_lens");
+    SAGE_REQUIRE(block_table, "sage_kvpaged_attn: null block_table");
+    const int shift = sage::paged_shift(page_size);
+    SAGE_REQUIRE(shift >= 0, "sage_kvpaged_attn: page_size must be 64 * 2^k (got %d)", page_size);
+    SAGE_REQUIRE(num_pages >= 1, "sage_kvpaged_attn: num_pages must be at least 1 (got %d)", num_pages);
+    SAGE_REQUIRE(max_pages_per_seq >= 1 && (int64_t)max_pages_per_seq * page_size <= ((int64_t)1 << 30) && bt_stride >= max_pages_per_seq,
+                 "sage_kvpaged_attn: max_pages_per_seq must be at least 1, max_pages_per_seq * page_size at most 2^30 and bt_stride at least "
+                 "max_pages_per_seq (got %d, page_size %d, bt_stride %lld)", max_pages_per_seq, page_size, (long long)bt_stride);
+    SAGE_REQUIRE(B > 0 && B <= 65535 && Hkv > 0 && Hkv <= 65535, "sage_kvpaged_attn: B and Hkv must be in [1, 65535] (got %d, %d)", B, Hkv);
+    SAGE_REQUIRE((reinterpret_cast<uintptr_t>(block_table) & 3u) == 0, "sage_kvpaged_attn: block_table must be 4-byte aligned");
+    const sage::PagedArgs g{block_table, (long)bt_stride, shift, num_pages, max_pages_per_seq};
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
+    c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = max_pages_per_seq * page_size; c.D = D;
     c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
     c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
     return attn_run(c);

@@ -67,6 +67,20 @@ struct AttnParams {
                               // its size and the offsets of the hidden arguments behind it are what they were)
 };
 
+// The operands of a PAGED launch (AttnVariant::paged; sage_attn_paged_kernel): a second kernel argument behind the parameter block, whose size
+// and offsets stay what they are.  k / v / k_scale of AttnParams are then a pool of num_pages pages of 64 << page_shift keys, laid out as the
+// tensors of a call with B = num_pages and Lk = the page size (k_sb: the page stride, nks: the scale slots of one page), and p.Lk is the logical
+// capacity max_pages * (64 << page_shift).  Logical 64-key tile t of sample b lies in page block_table[b * bt_stride + (t >> page_shift)], at
+// tile t & ((1 << page_shift) - 1) of it; an id is clamped to [0, num_pages - 1] by the kernel before it forms an address.
+struct PagedArgs {
+    const int32_t *block_table;   // int32 [B, max_pages] in device memory, row stride bt_stride (elements)
+    long bt_stride;
+    int page_shift;               // page size = 64 << page_shift keys
+    int num_pages;                // >= 1
+    int max_pages;                // table entries per sample
+};
+constexpr long kPagedArgsOffset = (long)((sizeof(AttnParams) + alignof(PagedArgs) - 1) / alignof(PagedArgs) * alignof(PagedArgs));      // of the second argument in the kernarg segment
+
 // launch attributes of an attention call that are not kernel parameters (the C ABI's SageLaunchAttr, include/sage_gfx950.h)
 struct AttnLaunchOpts {
     hipStream_t stream;
@@ -103,6 +117,8 @@ struct AttnVariant {
     bool gqa_pack;      // a decode-shaped kv_lens launch (p.Lq <= 32, p.group >= 2; with or without q_start / window) whose work item is (batch, kv head,
                         // block of four query heads of the group), one wave per head over one shared K / V ring: B * Hkv * ceil(group / 4) workgroups,
                         // the bits of the launch without it (SAGE_ATTR_GQA_PACK); no operand, AttnParams is what it is without
+    const PagedArgs *paged; // non-null (host memory, read by the launcher): a kv_lens launch (no split) whose K / V image / K scales are a pool of pages
+                        // reached through a block table -- the paged kernel of the same form, same grid, ordinary dispatch (never the ticket route)
 };
 constexpr int attn_qf(bool per_block, int q_dtype) { return (per_block ? 3 : 1) + (q_dtype == 0 ? 0 : 1); }   // q_dtype: DT_F16 (0) / DT_BF16
 // the one attention launcher: plans the work order, checks that the route exists (hipErrorInvalidValue) and launches the variant's kernel.
@@ -318,5 +334,7 @@ hipError_t launch_chunk_max_lens(const ChunkMaxLensParams &p, hipStream_t stream
 // ---- the C ABI's error channel for entry points defined outside sage_cabi.hip (sage_kv_cache.hip): stores the thread-local message that
 // sage_last_error() returns and hands `code` back
 int set_last_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// page_size = 64 * 2^k -> k, or -1 (sage_kv_paged.hip)
+int paged_shift(int page_size);
 
 }  // namespace sage

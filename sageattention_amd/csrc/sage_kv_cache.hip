@@ -19,124 +19,17 @@
 #include "sage_kernels.h"
 #include "sage_quant_math.h"
 #include "sage_kv_block.h"
+#include "sage_kv_cache.h"
 
 namespace sage {
-
-struct KvCacheParams {
-    int8_t *k_int8;             // [B,H,cap,D]
-    float *k_scale;             // [B,H,cap/64*4]
-    unsigned char *v_image;     // [B,H,cap/64,D,64]
-    float *v_scale;             // [B,H,D]
-    const float *v_amax;        // [B,H,D]
-    const uint16_t *k_mean;     // nullable [B,H,D]
-    uint16_t *k_tail, *v_tail;  // [B,H,64,D]
-    int32_t *lens;              // [B]
-    const uint16_t *k_new, *v_new;   // [B,H,T,D], strides below
-    const int32_t *new_lens;    // nullable [B]
-    int B, H, cap, T, D;
-    long k_sb, k_sh, k_sl;
-    long v_sb, v_sh, v_sl;
-    float scale_max;            // 448 (e4m3)
-};
-
-// rows sample b holds (clamped to [0, cap]) and rows this call gives it: clamped to [0, T], then to what still fits
-__device__ __forceinline__ void append_range(const KvCacheParams &p, int b, int &len0, int &t)
-{
-    const int l = p.lens[b];
-    len0 = l < 0 ? 0 : (l > p.cap ? p.cap : l);
-    int n = p.new_lens != nullptr ? p.new_lens[b] : p.T;
-    n = n < 0 ? 0 : (n > p.T ? p.T : n);
-    t = n < p.cap - len0 ? n : p.cap - len0;
-}
 
 template <int D, int DT>
 __global__ void __launch_bounds__(256)
 kvcache_append_kernel(const KvCacheParams p)
 {
-    constexpr int CPR = D / 16;                 // 16-element chunks per row
-    constexpr int NCH = BLKK * CPR / 256;       // chunks per thread
-    constexpr int LDT = D + 8;                  // padded row (16-B aligned), as prep_v_kernel
-    __shared__ unsigned gmax[4];
-    __shared__ __attribute__((aligned(16))) uint16_t tile[BLKK * LDT];
-
-    const int tid = threadIdx.x;
-    const int j = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const long bh = (long)b * p.H + h;
-    int len0, t;
-    append_range(p, b, len0, t);
-    // the scales of the frozen abs-max (every call: the same bytes; a sample that never gets a row has them too)
-    if (j == 0 && tid < D) p.v_scale[bh * D + tid] = fp8_v_scale(p.v_amax[bh * D + tid], p.scale_max);
-    const int len1 = len0 + t;                  // <= cap
-    const int blk = len0 / BLKK + j;
-    const int row0 = blk * BLKK;
-    if (row0 >= len1) return;                   // no new row for this block (t == 0 included); row0 < len1 <= cap: the block exists
-    const int valid = len1 - row0 < BLKK ? len1 - row0 : BLKK;
-    const int old = len0 - row0;                // rows r < old of the block are the tails' (j = 0), the rest k_new's / v_new's
-    const uint16_t *k_new = p.k_new + (long)b * p.k_sb + (long)h * p.k_sh + (long)(row0 - len0) * p.k_sl;     // row r of the block
-    const uint16_t *v_new = p.v_new + (long)b * p.v_sb + (long)h * p.v_sh + (long)(row0 - len0) * p.v_sl;
-    const uint16_t *k_tail = p.k_tail + bh * (BLKK * D);
-    const uint16_t *v_tail = p.v_tail + bh * (BLKK * D);
-
-    if (tid < 4) gmax[tid] = 0u;
-    // V rows -> LDS, zero behind the last valid token
-    constexpr int TPR = D / 8;
-#pragma unroll
-    for (int i = 0; i < BLKK * TPR / 256; i++) {
-        const int piece = tid + 256 * i;
-        const int r = piece / TPR, c8 = (piece % TPR) * 8;
-        v4u raw = {0u, 0u, 0u, 0u};
-        if (r < valid) raw = *reinterpret_cast<const v4u *>(r < old ? v_tail + r * D + c8 : v_new + (long)r * p.v_sl + c8);
-        *reinterpret_cast<v4u *>(&tile[r * LDT + c8]) = raw;
-    }
-    __syncthreads();
-
-    // ---- INT8 K: quant_int8_kernel for GR_THREAD_K / QS_TRITON_THREAD over the block's valid rows
-    const uint16_t *mean = p.k_mean != nullptr ? p.k_mean + bh * D : nullptr;
-    float v[NCH][16];
-#pragma unroll
-    for (int i = 0; i < NCH; i++) {
-        const int c = tid + 256 * i;
-        const int r = c / CPR, col = (c % CPR) * 16;
-        if (r < valid) {
-            const v4u *src = reinterpret_cast<const v4u *>(r < old ? k_tail + r * D + col : k_new + (long)r * p.k_sl + col);
-            v4u raw[2] = {src[0], src[1]};
-            v4u mraw[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-            if (mean != nullptr) {
-                const v4u *ms = reinterpret_cast<const v4u *>(mean + col);
-                mraw[0] = ms[0];
-                mraw[1] = ms[1];
-            }
-            const float amax = quant_load16<DT>(raw, mraw, mean != nullptr, QS_TRITON_THREAD, 1.0f, v[i]);
-            atomicMax(&gmax[group_of_row(r, GR_THREAD_K, BLKK)], __float_as_uint(amax));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 16; e++) v[i][e] = 0.0f;
-        }
-    }
-    __syncthreads();
-
-    if (tid < 4) p.k_scale[bh * (p.cap / BLKK * 4) + blk * 4 + tid] = quant_scale(__uint_as_float(gmax[tid]), QS_TRITON_THREAD);
-    int8_t *k_out = p.k_int8 + (bh * p.cap + row0) * D;
-#pragma unroll
-    for (int i = 0; i < NCH; i++) {
-        const int c = tid + 256 * i;
-        const int r = c / CPR, col = (c % CPR) * 16;
-        if (r >= valid) continue;
-        const float am = __uint_as_float(gmax[group_of_row(r, GR_THREAD_K, BLKK)]);
-        const v4u pk = quant_pack16(v[i], am, QS_TRITON_THREAD);
-        *reinterpret_cast<v4u *>(k_out + r * D + col) = pk;        // (the attention call that follows reads it: no non-temporal hint)
-    }
-
-    // ---- FP8 V: the block's whole tile image, prep_v_kernel<.., FP8> with am = v_amax
-    const float *amx = p.v_amax + bh * D;
-    unsigned char *out = p.v_image + (bh * (p.cap / BLKK) + blk) * (long)(D * 64);
-#pragma unroll
-    for (int i = 0; i < D * 4 / 256; i++) {
-        const int piece = tid + 256 * i;
-        const int d = piece >> 2, pc = piece & 3;
-        const v4u pk = fp8_v_image_piece<DT, LDT>(tile, d, pc, 0.0f, fp8_v_recp(amx[d], p.scale_max), false, valid);
-        *reinterpret_cast<v4u *>(out + d * 64 + pc * 16) = pk;
-    }
+#define SAGE_KV_APPEND_PAGED 0
+#include "sage_kv_append_body.h"
+#undef SAGE_KV_APPEND_PAGED
 }
 
 // launch 2: the raw rows of the block the NEXT append opens, then the new length
@@ -167,6 +60,12 @@ kvcache_commit_kernel(const KvCacheParams p)
     if (tid == 0) p.lens[b] = len1;
 }
 
+hipError_t launch_kvcache_commit(const KvCacheParams &p, hipStream_t s)
+{
+    hipLaunchKernelGGL(kvcache_commit_kernel, dim3(p.B), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 static hipError_t launch_kvcache_append(const KvCacheParams &p, int dtype, hipStream_t s)
 {
     const dim3 grid((63 + p.T + BLKK - 1) / BLKK, p.H, p.B);
@@ -176,8 +75,7 @@ static hipError_t launch_kvcache_append(const KvCacheParams &p, int dtype, hipSt
     else return hipErrorInvalidValue;
 #undef SAGE_KVC
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kvcache_commit_kernel, dim3(p.B), dim3(256), 0, s, p);
-    return hipGetLastError();
+    return launch_kvcache_commit(p, s);
 }
 
 }  // namespace sage

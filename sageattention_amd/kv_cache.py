@@ -177,16 +177,22 @@ class QuantizedKVCache:
 
 
 @torch.compiler.disable
-def sageattn_kvcache(q: torch.Tensor, cache: QuantizedKVCache, tensor_layout: str = "HND", is_causal: bool = False, causal_align: str = "top_left",
+def sageattn_kvcache(q: torch.Tensor, cache, tensor_layout: str = "HND", is_causal: bool = False, causal_align: str = "top_left",
                      q_start=None, window_size=None, pack_gqa=False, num_splits=None, sm_scale: Optional[float] = None, return_lse: bool = False):
     """Attention of ``q`` (``[B, Hq, Lq, D]`` HND / ``[B, Lq, Hq, D]`` NHD, the cache's dtype) to the cache's first ``cache.lens[b]`` keys per
     sample: ``sageattn_qk_int8_pv_fp8_cuda(q, k, v, kv_lens=cache.lens, ...)`` without its pre-pass.  ``is_causal``, ``causal_align``,
     ``q_start``, ``window_size``, ``pack_gqa``, ``num_splits``, ``sm_scale`` and ``return_lse`` mean what they mean there and raise the same
-    ValueErrors; the padded key length of the call is ``cache.capacity``.  Nothing reads the lengths on the host."""
+    ValueErrors; the padded key length of the call is ``cache.capacity``.  Nothing reads the lengths on the host.
+
+    ``cache`` may also be a :class:`~sageattention_amd.paged_kv_cache.PagedQuantizedKVCache`: the same call through its block table
+    (``sage_kvpaged_attn``), bit for bit the result on a contiguous cache of the same content; ``num_splits`` other than None is refused
+    there."""
+    from .paged_kv_cache import PagedQuantizedKVCache, _attend      # (imports this module)
+    paged = isinstance(cache, PagedQuantizedKVCache)
     if torch.compiler.is_compiling():
         raise ValueError("sageattn_kvcache is not supported under torch.compile")
-    if not isinstance(cache, QuantizedKVCache):
-        raise ValueError(f"cache must be a QuantizedKVCache (got {type(cache).__name__})")
+    if not paged and not isinstance(cache, QuantizedKVCache):
+        raise ValueError(f"cache must be a QuantizedKVCache or a PagedQuantizedKVCache (got {type(cache).__name__})")
     _layout_ok(tensor_layout)
     if not isinstance(q, torch.Tensor) or q.dim() != 4:
         raise ValueError(f"q must be a 4-D tensor (got {type(q).__name__} {list(getattr(q, 'shape', ()))})")
@@ -203,6 +209,8 @@ def sageattn_kvcache(q: torch.Tensor, cache: QuantizedKVCache, tensor_layout: st
         raise ValueError("Last dim of q must be contiguous.")
     if not cache._seeded:
         raise ValueError("the cache has no statistics yet: seed(k_mean, v_amax) or from_prefill(...) first")
+    if paged:
+        return _attend(q, cache, tensor_layout, is_causal, causal_align, q_start, window_size, pack_gqa, num_splits, sm_scale, return_lse)
     k_int8 = cache.k_int8 if tensor_layout == "HND" else cache.k_int8.permute(0, 2, 1, 3)      # (head-major storage, as the pre-pass's)
     # the keywords' checks and meanings are sageattn_qk_int8_pv_fp8_cuda's: one resolver (no kv_lens keyword here; the route's fixed options)
     call = core._kv_family_args(q, k_int8, tensor_layout, is_causal, None, q_start, causal_align, window_size, pack_gqa, num_splits,

@@ -8,6 +8,8 @@ import re
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sageattention_amd", "csrc", "sage_attn_form.h")
 _NAME = re.compile(r"^_ZN4sage16sage_attn_kernelILj(\d+)EEEvNS_10AttnParamsE$")
+# a paged kernel is `sage::sage_attn_paged_kernel<FORM>`: the same form, its tiles reached through a block table (a second argument, no form bit)
+_PAGED_NAME = re.compile(r"^_ZN4sage22sage_attn_paged_kernelILj(\d+)EEEvNS_10AttnParamsENS_9PagedArgsE$")
 _INTS = ("mask", "qf")                    # every other field is a flag
 _RANGE = {"mask": 3, "qf": 4}             # (form_error() of the header: the largest value of a field whose bits hold more)
 
@@ -69,6 +71,18 @@ def decode(name):
     if not m:
         raise ValueError(f"not a name of sage_attn_kernel<FORM>: {name}")
     return unpack(int(m.group(1)))
+
+
+def decode_paged(name):
+    """reported name of a paged kernel -> its form; ValueError on anything else (decode() does not accept these names, nor this one those)"""
+    m = _PAGED_NAME.match(name)
+    if not m:
+        raise ValueError(f"not a name of sage_attn_paged_kernel<FORM>: {name}")
+    return unpack(int(m.group(1)))
+
+
+def encode_paged(f):
+    return f"_ZN4sage22sage_attn_paged_kernelILj{pack(f)}EEEvNS_10AttnParamsENS_9PagedArgsE"
 
 
 def encode(f):

@@ -38,6 +38,9 @@ UNITS_PACKED_WINDOW = ("sage_attn_d128_f8vbw.hip", "sage_attn_d64_f8vbw.hip")
 UNITS_GQA_PACK = ("sage_attn_d128_f8g.hip", "sage_attn_d64_f8g.hip")
 # the num_splits route's pass 2 (the kv_lens family's exact split: seeded KVLEN kernels, unpacked and packed), eight kernels each; a list of their own likewise
 UNITS_KV_SPLIT = ("sage_attn_d128_f8ks.hip", "sage_attn_d64_f8ks.hip")
+# the paged kernels (sage_attn_paged_kernel: the kv_lens / q_start / window forms and the pack_gqa forms with their tiles through a block table),
+# eight kernels each; a list of their own likewise
+UNITS_PAGED = ("sage_attn_d128_f8p.hip", "sage_attn_d64_f8p.hip", "sage_attn_d128_f8pg.hip", "sage_attn_d64_f8pg.hip")
 NEED = {"v_mfma_f32_32x32x64_f8f6f4": 19, "v_mfma_scale_f32_32x32x64_f8f6f4": 19}        # 16 passes; everything else used here: 8 passes
 NEED_DEFAULT = 11
 PASSES = {k: 16 for k in NEED}
@@ -193,7 +196,7 @@ def lint(asm_text):
 
 
 def main(argv):
-    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW + UNITS_PACKED_BR + UNITS_PACKED_WINDOW + UNITS_GQA_PACK + UNITS_KV_SPLIT
+    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW + UNITS_PACKED_BR + UNITS_PACKED_WINDOW + UNITS_GQA_PACK + UNITS_KV_SPLIT + UNITS_PAGED
     total = 0
     for u in units:
         f, n = lint(listing(u))
