@@ -179,6 +179,25 @@ class SageKernelError(RuntimeError):
 _lib = None
 
 
+def bind(lib: ctypes.CDLL, symbols, version_symbol: str, version: int, what: str) -> None:
+    """Bind one header's symbol table to ``lib`` (once per library) and check that header's ABI version: ``_cabi_kvcache`` and
+    ``_cabi_kvpaged`` bind theirs through here, as :func:`load` does.  ``what`` words the mismatch ("ABI", "KV cache ABI", ...)."""
+    bound = lib.__dict__.setdefault("_sage_bound", set())       # the version symbols of the tables this library has bound
+    if version_symbol in bound:
+        return
+    for name, (res, args) in symbols.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise SageLibraryError(f"{LIB_PATH} does not export {name}") from e
+        fn.restype = res
+        fn.argtypes = args
+    got = getattr(lib, version_symbol)()
+    if got != version:
+        raise SageLibraryError(f"{what} version mismatch: library {got}, binding {version}")
+    bound.add(version_symbol)
+
+
 def load() -> ctypes.CDLL:
     """Load the HIP library (once); raise loudly if it is absent -- no fallback path exists."""
     global _lib
@@ -190,16 +209,7 @@ def load() -> ctypes.CDLL:
             "Run `python __graft_entry__.py` (or `make -C sageattention_amd/csrc`). "
             "sageattention_amd has no CPU/PyTorch fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SageLibraryError(f"{LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    got = lib.sage_abi_version()
-    if got != ABI_VERSION:
-        raise SageLibraryError(f"ABI version mismatch: library {got}, binding {ABI_VERSION}")
+    bind(lib, SYMBOLS, "sage_abi_version", ABI_VERSION, "ABI")
     _lib = lib
     return lib
 

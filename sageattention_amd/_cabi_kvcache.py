@@ -19,24 +19,9 @@ SYMBOLS = {
     "sage_kvcache_append": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _I, _P]),
 }
 
-_bound = False
-
 
 def load() -> ctypes.CDLL:
-    """The library of ``_cabi.load()`` with the cache's entry points bound (once)."""
-    global _bound
+    """The library of ``_cabi.load()`` with the cache's entry points bound (once, by ``_cabi.bind``)."""
     lib = _cabi.load()
-    if _bound:
-        return lib
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise _cabi.SageLibraryError(f"{_cabi.LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    got = lib.sage_kvcache_abi_version()
-    if got != ABI_VERSION:
-        raise _cabi.SageLibraryError(f"KV cache ABI version mismatch: library {got}, binding {ABI_VERSION}")
-    _bound = True
+    _cabi.bind(lib, SYMBOLS, "sage_kvcache_abi_version", ABI_VERSION, "KV cache ABI")
     return lib

@@ -21,7 +21,7 @@ from typing import Any, NamedTuple, Optional
 import torch
 import torch.nn.functional as F
 
-from . import _cabi, ops
+from . import _cabi, _cabi_kvpaged, ops
 from .quant import (LOG2E, _aligned, _cu_blocks, _dims, _p, _quant, _squeeze_km, _stream, channel_mean, channel_mean_kvlens, channel_mean_packed,
                     per_block_int8, per_block_int8_varlen, per_channel_fp8, per_channel_fp8_kvlens, per_channel_fp8_varlen, per_thread_int8_k_kvlens, prep_v_fp16, prep_v_fp16_varlen, prepass_fused_ok, prepass_kv_fp8, prepass_kv_varlen,
                     prepass_varlen_fused_ok, sub_mean, varlen_plan)
@@ -151,7 +151,7 @@ def _v_rows_wanted(q, k, v, tensor_layout: str, is_causal: bool, override) -> bo
 
 @torch.compiler.disable
 def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal, sm_scale_log2, return_lse, v_mean=None, folded_scores=False,
-                  v_rows=False, kv_lens=None, q_start=None, window=0, gqa_pack=False, num_splits=0):
+                  v_rows=False, kv_lens=None, q_start=None, window=0, gqa_pack=False, num_splits=0, paged=None):
     """FP8-PV two-level attention with the per-thread Q quantisation done in the kernel prologue
     (``sage_attn_fused_q_pv_f8``): bit-identical to ``per_thread_int8`` + the attention op, one launch and
     3 B/element of HBM traffic less.  ``v_rows`` (FP16 PV): ``v_image`` is the fp16 V tensor itself, read in place.
@@ -160,7 +160,9 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
     causal; a Python int): the number of keys a row sees up to and including its diagonal, 0 = unbounded (``SageLaunchAttr.window``);
     ``gqa_pack`` (with ``kv_lens``, ``Lq <= 32``, ``Hq / Hkv >= 2``): the query heads of a GQA group four to a workgroup (``SAGE_ATTR_GQA_PACK``);
     ``num_splits`` (with ``kv_lens``, ``Lq <= 128``, no window; 0 or 2 .. 255): that many key-range chunks, exactly (``SAGE_ATTR_KV_SPLIT``; the
-    split workspace is allocated here, from the shapes alone)."""
+    split workspace is allocated here, from the shapes alone); ``paged`` (with ``kv_lens``, no split; a ``PagedQuantizedKVCache``): ``k_int8`` /
+    ``v_image`` / ``k_scale`` are its pool of pages and the call goes through its block table (``sage_kvpaged_attn``), which takes the offsets,
+    the window and the packing flag and nothing else of the attributes."""
     B, Hq, Lq, D, q_sb, q_sh, q_sl = _dims(q, tensor_layout)
     _, Hkv, Lk, _, k_sb, k_sh, k_sl = _dims(k_int8, tensor_layout)
     assert Hq % Hkv == 0, "num_qo_heads must be divisible by num_kv_heads"
@@ -173,8 +175,12 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
     assert not gqa_pack or kv_lens is not None
     assert not num_splits or (kv_lens is not None and not window and Lq <= 128)
     split_ws = torch.empty((_cabi.kv_split_ws_bytes(B, Hq, Lq, D, num_splits) // 4,), dtype=torch.float32, device=q.device) if num_splits else None
-    attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None, q_start=q_start, window=window,
-                         gqa_pack=gqa_pack, kv_split=num_splits, split_ws=split_ws)
+    if paged is not None:          # (no launch workspace, no trace buffer, no forced ticket route: the C entry's ordinary dispatch)
+        assert kv_lens is not None and not num_splits
+        attr = _cabi.launch_attr(grid_out=ops._hooks.grid_probe, q_start=q_start, window=window, gqa_pack=gqa_pack)
+    else:
+        attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None, q_start=q_start, window=window,
+                             gqa_pack=gqa_pack, kv_split=num_splits, split_ws=split_ws)
     if v_rows:                     # FP16 PV on fp16 inputs: V rows in place, no tile image (sage_attn_fused_q_pv_f16_vrows)
         assert v_scale is None and v_mean is None
         _, _, _, _, v_sb, v_sh, v_sl = _dims(v_image, tensor_layout)
@@ -193,6 +199,14 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
         return o, lse
     if kv_lens is not None:
         assert v_scale is not None and not folded_scores and not v_rows
+        if paged is not None:      # the same call on a pool of pages: Lk is the logical capacity, the K strides are a page's
+            rc = _cabi_kvpaged.load().sage_kvpaged_attn(
+                _p(q), _p(k_int8), _p(v_image), _p(o), _p(lse), _p(k_scale), _p(v_scale), _p(kv_lens),
+                _p(paged.block_table), paged.block_table.stride(0), paged.num_pages, paged.page_size, paged.max_pages_per_seq,
+                B, Hq, Hkv, Lq, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl,
+                int(is_causal), float(sm_scale_log2), code, code, _stream(q), _cabi.attr_arg(attr))
+            ops.attn_check(rc, "sage_kvpaged_attn", attr, q.device)
+            return o, lse
         rc = _cabi.load().sage_attn_fused_q_pv_f8_kvlens(
             _p(q), _p(k_int8), _p(v_image), _p(o), _p(lse), _p(k_scale), _p(v_scale), _p(v_mean), _p(kv_lens),
             B, Hq, Hkv, Lq, Lk, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl,
@@ -575,14 +589,16 @@ def _kv_family_args(q, k, tensor_layout, is_causal: bool, kv_lens, q_start, caus
 
 
 def _attn_kv_family(call: _KvFamily, q, lens, kv_lens, k_int8, v_image, v_scale, k_scale, tensor_layout, sm_scale, return_lse, head_dim_og,
-                    smooth_k, lse_correction):
+                    smooth_k, lse_correction, paged=None):
     """The attention of a call on the ``kv_lens`` entry, from its resolved keywords and quantised operands: ``lens`` are the int32 lengths the
-    kernel reads, ``kv_lens`` what ``causal_align='bottom_right'`` forms its offsets from (None: the padded key length).  Nothing here reads a
-    length or an offset on the host."""
+    kernel reads, ``kv_lens`` what ``causal_align='bottom_right'`` forms its offsets from (None: the padded key length).  ``paged``: the
+    ``PagedQuantizedKVCache`` whose pool the operands are (its ``capacity`` is then the padded key length).  Nothing here reads a length or an
+    offset on the host."""
     B, _, Lq = _dims(q, tensor_layout)[:3]
-    start = _q_start_tensor(call.q_start, kv_lens, B, Lq, _dims(k_int8, tensor_layout)[2], q.device, call.shift) if call.with_start else None
+    Lk = paged.capacity if paged is not None else _dims(k_int8, tensor_layout)[2]
+    start = _q_start_tensor(call.q_start, kv_lens, B, Lq, Lk, q.device, call.shift) if call.with_start else None
     o, lse = _attn_fused_q(_aligned(q, 8), k_int8, v_image, v_scale, k_scale, tensor_layout, call.is_causal, _sm_log2(sm_scale), return_lse,
-                           kv_lens=lens, q_start=start, window=call.window, gqa_pack=call.gqa_pack, num_splits=call.splits)
+                           kv_lens=lens, q_start=start, window=call.window, gqa_pack=call.gqa_pack, num_splits=call.splits, paged=paged)
     return _finish(o, lse, head_dim_og, return_lse, smooth_k, lse_correction, sm_scale)
 
 

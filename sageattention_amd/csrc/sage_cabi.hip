@@ -5,6 +5,8 @@
 #include "sage_common.h"
 #include "sage_kernels.h"
 #include "sage_work_order.h"
+#include "sage_host_checks.h"
+#include "sage_kv_cache.h"
 
 #include <cstdarg>
 #include <cstddef>
@@ -12,20 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 
-namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-}  // namespace
+static thread_local char g_err[512] = "";
 
 int sage::set_last_error(int code, const char *fmt, ...)
 {
@@ -38,22 +27,17 @@ int sage::set_last_error(int code, const char *fmt, ...)
 
 namespace {
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+using sage::aligned16, sage::aligned16_strides, sage::multiples_of;      // (sage_host_checks.h, with SAGE_REQUIRE)
 
 int check_launch(hipError_t e, const char *what)
 {
-    if (e != hipSuccess) return fail(SAGE_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return sage::set_last_error(SAGE_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
     return SAGE_OK;
 }
-
-#define SAGE_REQUIRE(cond, ...) do { if (!(cond)) return fail(SAGE_EINVAL, __VA_ARGS__); } while (0)
 
 // the argument checks that come back in every entry point
 #define SAGE_REQUIRE_HEAD_DIM(D, hint) SAGE_REQUIRE((D) == 64 || (D) == 128, "head_dim must be 64 or 128 (got %d)" hint, D)
 #define SAGE_REQUIRE_DTYPE(t, name) SAGE_REQUIRE((t) == SAGE_DTYPE_F16 || (t) == SAGE_DTYPE_BF16, "bad " name " %d", t)
-inline bool multiples_of(int n, int64_t a, int64_t b, int64_t c = 0) { return a % n == 0 && b % n == 0 && c % n == 0; }
-// 16-byte aligned, strides in multiples of n elements
-inline bool aligned16_strides(const void *p, int n, int64_t a, int64_t b, int64_t c = 0) { return aligned16(p) && multiples_of(n, a, b, c); }
 inline int64_t stats_slabs(int64_t L) { return (L + sage::kStatsSlab - 1) / sage::kStatsSlab; }       // 512-token slabs of a sequence of L tokens
 
 struct Strides { int64_t sb, sh, sl; };         // element strides of a [batch, head, row, D] view (packed tensors: sb = 0)
@@ -361,7 +345,7 @@ SAGE_API const char *sage_last_error(void) { return g_err; }
 // host-side views of sage_work_order.h (the code the kernels and launchers run), for tests without a GPU
 SAGE_API int sage_debug_work_order_plan(int nheads, int nqblk, int64_t kv_len, int head_dim, int pv_fp8, int forced, int *group, int *fold, int *left)
 {
-    if (nheads <= 0 || nqblk <= 0 || group == nullptr || fold == nullptr || left == nullptr) return fail(SAGE_EINVAL, "sage_debug_work_order_plan: bad argument");
+    if (nheads <= 0 || nqblk <= 0 || group == nullptr || fold == nullptr || left == nullptr) return sage::set_last_error(SAGE_EINVAL, "sage_debug_work_order_plan: bad argument");
     sage::WorkOrder w;
     const int grid = sage::plan_work_order(w, nheads, nqblk, (long)kv_len, head_dim, pv_fp8 != 0, forced);
     *group = w.group; *fold = w.fold; *left = w.left;
@@ -371,7 +355,7 @@ SAGE_API int sage_debug_work_item(int bid, int nwg, int nheads, int nqblk, int g
 {
     if (head == nullptr || qrank == nullptr || nwg <= 0 || bid < 0 || bid >= nwg || nheads <= 0 || nqblk <= 0 || group < 0 || fold < 0 || fold > 1 ||
         left < 0 || left >= 8 || left > nheads)
-        return fail(SAGE_EINVAL, "sage_debug_work_item: bad argument");
+        return sage::set_last_error(SAGE_EINVAL, "sage_debug_work_item: bad argument");
     const sage::WorkOrder w = {group, fold, left};
     return sage::work_item(w, bid, nwg, nheads, nqblk, *head, *qrank) ? 1 : 0;
 }
@@ -417,7 +401,7 @@ static int quant_common(const void *x, const void *mean, int8_t *out, float *sca
         p.gran = is_key ? sage::GR_THREAD_K : sage::GR_THREAD_Q;
         slots = (blk / warp) * (is_key ? 4 : 8);
         SAGE_REQUIRE(slots <= 64, "too many scale groups per block (%d)", slots);
-    } else return fail(SAGE_EINVAL, "bad qk_quant_gran %d", gran);
+    } else return sage::set_last_error(SAGE_EINVAL, "bad qk_quant_gran %d", gran);
     p.nscale = ((L + blk - 1) / blk) * slots;
     p.kv_lens = kv_lens;
     return check_launch(sage::launch_quant_int8(p, static_cast<hipStream_t>(stream)), "sage_quant_qk_int8 launch");
@@ -507,18 +491,18 @@ SAGE_API int sage_debug_varlen_items(const int32_t *lq, const int32_t *lk, int n
 {
     if (lq == nullptr || lk == nullptr || items_out == nullptr || hdr_out == nullptr || nseq <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 ||
         (head_dim != 64 && head_dim != 128))
-        return fail(SAGE_EINVAL, "sage_debug_varlen_items: bad argument");
+        return sage::set_last_error(SAGE_EINVAL, "sage_debug_varlen_items: bad argument");
     int nitems = 0, max_lk = 0;
     for (int s = 0; s < nseq; s++) {
-        if (lq[s] < 0 || lk[s] < 0) return fail(SAGE_EINVAL, "sage_debug_varlen_items: negative length");
+        if (lq[s] < 0 || lk[s] < 0) return sage::set_last_error(SAGE_EINVAL, "sage_debug_varlen_items: negative length");
         nitems += (lq[s] + 127) / 128;
         max_lk = lk[s] > max_lk ? lk[s] : max_lk;
     }
-    if (nitems > items_cap) return fail(SAGE_EINVAL, "sage_debug_varlen_items: %d items do not fit %d", nitems, items_cap);
+    if (nitems > items_cap) return sage::set_last_error(SAGE_EINVAL, "sage_debug_varlen_items: %d items do not fit %d", nitems, items_cap);
     for (int s = 0; s < nseq; s++)
         for (int j = 0; j < (lq[s] + 127) / 128; j++) {
             const int r = sage::varlen_item_rank(lq, lk, nseq, s, j, is_causal == 2 ? 2 : (is_causal ? 1 : 0));
-            if (r < 0 || r >= nitems) return fail(SAGE_ELAUNCH, "sage_debug_varlen_items: rank %d out of range", r);
+            if (r < 0 || r >= nitems) return sage::set_last_error(SAGE_ELAUNCH, "sage_debug_varlen_items: rank %d out of range", r);
             items_out[2 * r] = s; items_out[2 * r + 1] = j;
         }
     sage::WorkOrder w;
@@ -736,7 +720,7 @@ SAGE_API int sage_host_word_alloc(void **host_ptr, void **device_ptr)
     void *h = nullptr, *d = nullptr;
     hipError_t e = hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocPortable);
     if (e == hipSuccess) e = hipHostGetDevicePointer(&d, h, 0);
-    if (e != hipSuccess) { if (h) (void)hipHostFree(h); return fail(SAGE_ELAUNCH, "sage_host_word_alloc: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { if (h) (void)hipHostFree(h); return sage::set_last_error(SAGE_ELAUNCH, "sage_host_word_alloc: %s", hipGetErrorString(e)); }
     *static_cast<volatile uint32_t *>(h) = 0u;
     *host_ptr = h; *device_ptr = d;
     return SAGE_OK;
@@ -745,7 +729,7 @@ SAGE_API int sage_host_word_free(void *host_ptr)
 {
     if (host_ptr == nullptr) return SAGE_OK;
     const hipError_t e = hipHostFree(host_ptr);
-    return e == hipSuccess ? SAGE_OK : fail(SAGE_ELAUNCH, "sage_host_word_free: %s", hipGetErrorString(e));
+    return e == hipSuccess ? SAGE_OK : sage::set_last_error(SAGE_ELAUNCH, "sage_host_word_free: %s", hipGetErrorString(e));
 }
 
 SAGE_API int sage_prepass_max_seqlen_stream(void *stream)
@@ -757,17 +741,17 @@ SAGE_API int sage_prepass_max_seqlen_stream(void *stream)
 
 SAGE_API int sage_prepass_failed_heads(const uint32_t *sync, int B, int H, void *stream)
 {
-    if (!sync || B <= 0 || H <= 0) return fail(SAGE_EINVAL, "bad arguments");
+    if (!sync || B <= 0 || H <= 0) return sage::set_last_error(SAGE_EINVAL, "bad arguments");
     const size_t words = (size_t)2 * B * H * sage::kPrepassSyncStride;
     uint32_t *host = static_cast<uint32_t *>(malloc(words * sizeof(uint32_t)));
-    if (!host) return fail(SAGE_ELAUNCH, "out of host memory");
+    if (!host) return sage::set_last_error(SAGE_ELAUNCH, "out of host memory");
     hipError_t e = hipMemcpyAsync(host, sync, words * sizeof(uint32_t), hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream));
     if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
     int n = 0;
     if (e == hipSuccess)
         for (size_t i = 0; i < (size_t)2 * B * H; i++) n += host[i * sage::kPrepassSyncStride + 2] != 0;
     free(host);
-    if (e != hipSuccess) return fail(SAGE_ELAUNCH, "sage_prepass_failed_heads: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return sage::set_last_error(SAGE_ELAUNCH, "sage_prepass_failed_heads: %s", hipGetErrorString(e));
     return n;
 }
 
@@ -807,7 +791,7 @@ SAGE_API int sage_prepass_kv(const void *k, const void *v, void *k_mean, int8_t 
         SAGE_REQUIRE(k_style != sage::QS_TRITON || qk_quant_gran == SAGE_GRAN_PER_BLOCK, "the Triton per-block convention goes with per-block scales");
         if (qk_quant_gran == SAGE_GRAN_PER_BLOCK) p.k_gran = sage::GR_BLOCK;
         else if (qk_quant_gran == SAGE_GRAN_PER_THREAD) p.k_gran = sage::GR_THREAD_K;
-        else return fail(SAGE_EINVAL, "bad k granularity %d (per-block or per-thread)", qk_quant_gran);
+        else return sage::set_last_error(SAGE_EINVAL, "bad k granularity %d (per-block or per-thread)", qk_quant_gran);
     }
     if (v) {
         SAGE_REQUIRE(v_image && (v_scale || v_fp16), "V part needs v_image (and v_scale for the FP8 image)");
@@ -1061,16 +1045,11 @@ SAGE_KVPAGED_API int sage_kvpaged_attn(const void *q, const int8_t *k_int8, cons
 {
     SAGE_REQUIRE(q && k_int8 && v_image && o && k_scale && v_scale, "sage_kvpaged_attn: null tensor pointer (only lse may be null)");
     SAGE_REQUIRE(kv_lens, "sage_kvpaged_attn: null kv_lens");
-    SAGE_REQUIRE(block_table, "sage_kvpaged_attn: null block_table");
-    const int shift = sage::paged_shift(page_size);
-    SAGE_REQUIRE(shift >= 0, "sage_kvpaged_attn: page_size must be 64 * 2^k (got %d)", page_size);
-    SAGE_REQUIRE(num_pages >= 1, "sage_kvpaged_attn: num_pages must be at least 1 (got %d)", num_pages);
-    SAGE_REQUIRE(max_pages_per_seq >= 1 && (int64_t)max_pages_per_seq * page_size <= ((int64_t)1 << 30) && bt_stride >= max_pages_per_seq,
-                 "sage_kvpaged_attn: max_pages_per_seq must be at least 1, max_pages_per_seq * page_size at most 2^30 and bt_stride at least "
-                 "max_pages_per_seq (got %d, page_size %d, bt_stride %lld)", max_pages_per_seq, page_size, (long long)bt_stride);
-    SAGE_REQUIRE(B > 0 && B <= 65535 && Hkv > 0 && Hkv <= 65535, "sage_kvpaged_attn: B and Hkv must be in [1, 65535] (got %d, %d)", B, Hkv);
-    SAGE_REQUIRE((reinterpret_cast<uintptr_t>(block_table) & 3u) == 0, "sage_kvpaged_attn: block_table must be 4-byte aligned");
-    const sage::PagedArgs g{block_table, (long)bt_stride, shift, num_pages, max_pages_per_seq};
+    const char *const e = "sage_kvpaged_attn";
+    sage::PagedArgs g;
+    if (const int rc = sage::paged_args(e, block_table, bt_stride, num_pages, page_size, max_pages_per_seq, g)) return rc;
+    if (const int rc = sage::kv_check_batch(e, B, Hkv)) return rc;
+    if (const int rc = sage::paged_check_table_aligned(e, block_table)) return rc;
     AttnCall c{};
     c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
     c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g;

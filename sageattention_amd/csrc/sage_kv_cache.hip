@@ -80,8 +80,6 @@ static hipError_t launch_kvcache_append(const KvCacheParams &p, int dtype, hipSt
 
 }  // namespace sage
 
-#define KVC_REQUIRE(cond, ...) do { if (!(cond)) return sage::set_last_error(SAGE_EINVAL, __VA_ARGS__); } while (0)
-
 extern "C" {
 
 SAGE_KVCACHE_API int sage_kvcache_abi_version(void) { return SAGE_KVCACHE_ABI_VERSION; }
@@ -94,29 +92,17 @@ SAGE_KVCACHE_API int sage_kvcache_append(int8_t *k_int8, float *k_scale, void *v
                                          int64_t v_sb, int64_t v_sh, int64_t v_sl,
                                          int dtype, void *stream)
 {
-    auto a16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    KVC_REQUIRE(k_int8 && k_scale && v_image && v_scale && v_amax && k_tail && v_tail && lens,
-                "sage_kvcache_append: null cache pointer (only k_mean may be null)");
-    KVC_REQUIRE(k_new && v_new, "sage_kvcache_append: null k_new / v_new pointer");
-    KVC_REQUIRE(head_dim == 64 || head_dim == 128, "sage_kvcache_append: head_dim must be 64 or 128 (got %d)", head_dim);
-    KVC_REQUIRE(T >= 1, "sage_kvcache_append: T must be at least 1 (got %d)", T);
-    KVC_REQUIRE(capacity > 0 && capacity % 64 == 0, "sage_kvcache_append: capacity must be a positive multiple of 64 (got %d)", capacity);
-    KVC_REQUIRE(B > 0 && B <= 65535 && Hkv > 0 && Hkv <= 65535, "sage_kvcache_append: B and Hkv must be in [1, 65535] (got %d, %d)", B, Hkv);
-    KVC_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "sage_kvcache_append: bad dtype %d", dtype);
-    KVC_REQUIRE(a16(k_int8) && a16(k_scale) && a16(v_image) && a16(k_tail) && a16(v_tail) && a16(k_new) && a16(v_new) && (!k_mean || a16(k_mean)),
-                "sage_kvcache_append: k_int8 / k_scale / v_image / k_mean / k_tail / v_tail / k_new / v_new must be 16-byte aligned");
-    KVC_REQUIRE(k_sb % 8 == 0 && k_sh % 8 == 0 && k_sl % 8 == 0 && v_sb % 8 == 0 && v_sh % 8 == 0 && v_sl % 8 == 0,
-                "sage_kvcache_append: k_new / v_new strides must be multiples of 8 elements");
-    sage::KvCacheParams p{};
-    p.k_int8 = k_int8; p.k_scale = k_scale; p.v_image = static_cast<unsigned char *>(v_image); p.v_scale = v_scale; p.v_amax = v_amax;
-    p.k_mean = static_cast<const uint16_t *>(k_mean);
-    p.k_tail = static_cast<uint16_t *>(k_tail); p.v_tail = static_cast<uint16_t *>(v_tail); p.lens = lens;
-    p.k_new = static_cast<const uint16_t *>(k_new); p.v_new = static_cast<const uint16_t *>(v_new); p.new_lens = new_lens;
-    p.B = B; p.H = Hkv; p.cap = capacity; p.T = T; p.D = head_dim;
-    p.k_sb = k_sb; p.k_sh = k_sh; p.k_sl = k_sl; p.v_sb = v_sb; p.v_sh = v_sh; p.v_sl = v_sl;
-    p.scale_max = 448.0f;
-    const hipError_t e = sage::launch_kvcache_append(p, dtype, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return sage::set_last_error(SAGE_ELAUNCH, "sage_kvcache_append launch: %s", hipGetErrorString(e));
+    const char *const e = "sage_kvcache_append";
+    const sage::KvCacheParams p = sage::kv_append_params(k_int8, k_scale, v_image, v_scale, v_amax, k_mean, k_tail, v_tail, lens, k_new, v_new, new_lens,
+                                                         B, Hkv, capacity, T, head_dim, k_sb, k_sh, k_sl, v_sb, v_sh, v_sl);
+    if (const int rc = sage::kv_check_pointers(e, p)) return rc;
+    if (const int rc = sage::kv_check_rows(e, p)) return rc;
+    SAGE_REQUIRE(capacity > 0 && capacity % 64 == 0, "%s: capacity must be a positive multiple of 64 (got %d)", e, capacity);
+    if (const int rc = sage::kv_check_batch(e, B, Hkv)) return rc;
+    if (const int rc = sage::kv_check_dtype_aligned(e, p, dtype)) return rc;
+    if (const int rc = sage::kv_check_strides(e, p)) return rc;
+    const hipError_t err = sage::launch_kvcache_append(p, dtype, static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return sage::set_last_error(SAGE_ELAUNCH, "%s launch: %s", e, hipGetErrorString(err));
     return SAGE_OK;
 }
 

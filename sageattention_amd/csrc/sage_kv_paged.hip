@@ -50,8 +50,6 @@ int paged_shift(int page_size)
 
 }  // namespace sage
 
-#define KVP_REQUIRE(cond, ...) do { if (!(cond)) return sage::set_last_error(SAGE_EINVAL, __VA_ARGS__); } while (0)
-
 extern "C" {
 
 SAGE_KVPAGED_API int sage_kvpaged_abi_version(void) { return SAGE_KVPAGED_ABI_VERSION; }
@@ -66,37 +64,20 @@ SAGE_KVPAGED_API int sage_kvpaged_append(int8_t *k_int8, float *k_scale, void *v
                                          const int32_t *block_table, int64_t bt_stride, int num_pages, int page_size, int max_pages_per_seq,
                                          void *stream)
 {
-    auto a16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    KVP_REQUIRE(k_int8 && k_scale && v_image && v_scale && v_amax && k_tail && v_tail && lens,
-                "sage_kvpaged_append: null cache pointer (only k_mean may be null)");
-    KVP_REQUIRE(k_new && v_new, "sage_kvpaged_append: null k_new / v_new pointer");
-    KVP_REQUIRE(block_table, "sage_kvpaged_append: null block_table");
-    const int shift = sage::paged_shift(page_size);
-    KVP_REQUIRE(shift >= 0, "sage_kvpaged_append: page_size must be 64 * 2^k (got %d)", page_size);
-    KVP_REQUIRE(num_pages >= 1, "sage_kvpaged_append: num_pages must be at least 1 (got %d)", num_pages);
-    KVP_REQUIRE(max_pages_per_seq >= 1 && (int64_t)max_pages_per_seq * page_size <= ((int64_t)1 << 30) && bt_stride >= max_pages_per_seq,
-                "sage_kvpaged_append: max_pages_per_seq must be at least 1, max_pages_per_seq * page_size at most 2^30 and bt_stride at least "
-                "max_pages_per_seq (got %d, page_size %d, bt_stride %lld)", max_pages_per_seq, page_size, (long long)bt_stride);
-    KVP_REQUIRE(B > 0 && B <= 65535 && Hkv > 0 && Hkv <= 65535, "sage_kvpaged_append: B and Hkv must be in [1, 65535] (got %d, %d)", B, Hkv);
-    KVP_REQUIRE(head_dim == 64 || head_dim == 128, "sage_kvpaged_append: head_dim must be 64 or 128 (got %d)", head_dim);
-    KVP_REQUIRE(T >= 1, "sage_kvpaged_append: T must be at least 1 (got %d)", T);
-    KVP_REQUIRE(dtype == SAGE_DTYPE_F16 || dtype == SAGE_DTYPE_BF16, "sage_kvpaged_append: bad dtype %d", dtype);
-    KVP_REQUIRE(a16(k_int8) && a16(k_scale) && a16(v_image) && a16(k_tail) && a16(v_tail) && a16(k_new) && a16(v_new) && (!k_mean || a16(k_mean)),
-                "sage_kvpaged_append: k_int8 / k_scale / v_image / k_mean / k_tail / v_tail / k_new / v_new must be 16-byte aligned");
-    KVP_REQUIRE((reinterpret_cast<uintptr_t>(block_table) & 3u) == 0, "sage_kvpaged_append: block_table must be 4-byte aligned");
-    KVP_REQUIRE(k_sb % 8 == 0 && k_sh % 8 == 0 && k_sl % 8 == 0 && v_sb % 8 == 0 && v_sh % 8 == 0 && v_sl % 8 == 0,
-                "sage_kvpaged_append: k_new / v_new strides must be multiples of 8 elements");
-    sage::KvCacheParams p{};
-    p.k_int8 = k_int8; p.k_scale = k_scale; p.v_image = static_cast<unsigned char *>(v_image); p.v_scale = v_scale; p.v_amax = v_amax;
-    p.k_mean = static_cast<const uint16_t *>(k_mean);
-    p.k_tail = static_cast<uint16_t *>(k_tail); p.v_tail = static_cast<uint16_t *>(v_tail); p.lens = lens;
-    p.k_new = static_cast<const uint16_t *>(k_new); p.v_new = static_cast<const uint16_t *>(v_new); p.new_lens = new_lens;
-    p.B = B; p.H = Hkv; p.cap = max_pages_per_seq * page_size; p.T = T; p.D = head_dim;
-    p.k_sb = k_sb; p.k_sh = k_sh; p.k_sl = k_sl; p.v_sb = v_sb; p.v_sh = v_sh; p.v_sl = v_sl;
-    p.scale_max = 448.0f;
-    const sage::PagedArgs g{block_table, (long)bt_stride, shift, num_pages, max_pages_per_seq};
-    const hipError_t e = sage::launch_kvpaged_append(p, g, dtype, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return sage::set_last_error(SAGE_ELAUNCH, "sage_kvpaged_append launch: %s", hipGetErrorString(e));
+    const char *const e = "sage_kvpaged_append";
+    sage::KvCacheParams p = sage::kv_append_params(k_int8, k_scale, v_image, v_scale, v_amax, k_mean, k_tail, v_tail, lens, k_new, v_new, new_lens,
+                                                   B, Hkv, 0, T, head_dim, k_sb, k_sh, k_sl, v_sb, v_sh, v_sl);
+    sage::PagedArgs g;
+    if (const int rc = sage::kv_check_pointers(e, p)) return rc;
+    if (const int rc = sage::paged_args(e, block_table, bt_stride, num_pages, page_size, max_pages_per_seq, g)) return rc;
+    p.cap = max_pages_per_seq * page_size;          // (the logical capacity: at most 2^30, checked above)
+    if (const int rc = sage::kv_check_batch(e, B, Hkv)) return rc;
+    if (const int rc = sage::kv_check_rows(e, p)) return rc;
+    if (const int rc = sage::kv_check_dtype_aligned(e, p, dtype)) return rc;
+    if (const int rc = sage::paged_check_table_aligned(e, block_table)) return rc;
+    if (const int rc = sage::kv_check_strides(e, p)) return rc;
+    const hipError_t err = sage::launch_kvpaged_append(p, g, dtype, static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return sage::set_last_error(SAGE_ELAUNCH, "%s launch: %s", e, hipGetErrorString(err));
     return SAGE_OK;
 }
 
