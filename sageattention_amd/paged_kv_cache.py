@@ -12,8 +12,12 @@ Device rules: attention reads the table entries of tiles that hold a key it requ
 advance).  A bad table gives wrong numbers, never an access outside the pool.  Two sequences that append into one page are the caller's error
 and are not detected; there is no allocator here.
 
-Only what paging adds is written here -- the pool's shapes, the block table, ``seed(slots=...)``, the C call of an append, the table of
-``from_prefill`` and what :func:`~sageattention_amd.kv_cache.sageattn_kvcache` asks a paged cache for; the rest is the base class of
+Sequences share pages through :meth:`PagedQuantizedKVCache.fork`: the child's table names the parent's closed pages, the
+parent's open page is copied into a page of the child's own, and the child takes the parent's frozen statistics -- which is what makes the
+shared bytes exactly the child's own.
+
+Only what paging adds is written here -- the pool's shapes, the block table, ``seed(slots=...)``, the C call of an append, ``fork``, the table
+of ``from_prefill`` and what :func:`~sageattention_amd.kv_cache.sageattn_kvcache` asks a paged cache for; the rest is the base class of
 :mod:`~sageattention_amd.kv_cache`, and the ``sage_kvpaged_attn`` call is a branch of ``core._attn_fused_q``.
 
 Import from here (``from sageattention_amd.paged_kv_cache import PagedQuantizedKVCache``); the names are not part of the package's
@@ -25,7 +29,7 @@ from typing import Optional
 
 import torch
 
-from . import _cabi, _cabi_kvpaged
+from . import _cabi, _cabi_kvfork, _cabi_kvpaged
 from .kv_cache import _KVCacheBase, _is_int
 from .quant import _dtype_code, _p, _stream
 
@@ -105,6 +109,77 @@ class PagedQuantizedKVCache(_KVCacheBase):
             _p(self.lens), _p(k_new), _p(v_new), _p(new_lens), self.B, self.Hkv, T, self.D, *k_strides, *v_strides, _dtype_code(k_new),
             _p(self.block_table), self.block_table.stride(0), self.num_pages, self.page_size, self.max_pages_per_seq, _stream(k_new))
         _cabi.check(rc, "sage_kvpaged_append")
+
+    def _fork_index(self, name, x, limit, what):
+        """One index argument of :meth:`fork` as (int32 tensor ``[n]`` on the device, the list of ints it was given as or None).  A sequence of
+        ints is checked here (``limit``: the values lie in ``[0, limit)``; None: any int, clamped to int32); a tensor is never read."""
+        if isinstance(x, torch.Tensor):
+            if x.dtype not in (torch.int32, torch.int64) or x.dim() != 1 or x.device != self.device:
+                raise ValueError(f"{name} must be a 1-D int32 / int64 tensor on {self.device} or a sequence of ints "
+                                 f"(got {x.dtype} {list(x.shape)} on {x.device})")
+            if x.dtype == torch.int64:
+                x = x.clamp(-2 ** 31, 2 ** 31 - 1)
+            return x.to(torch.int32).contiguous(), None
+        if not isinstance(x, (list, tuple)) or not all(_is_int(s) for s in x):
+            raise ValueError(f"{name} must be a 1-D int32 / int64 tensor or a sequence of ints (got {x!r})")
+        if limit is not None and any(not 0 <= s < limit for s in x):
+            raise ValueError(f"{name} must be {what} in [0, {limit}) (got {list(x)!r})")
+        values = [max(-2 ** 31, min(2 ** 31 - 1, s)) for s in x]
+        return torch.tensor(values, dtype=torch.int32, device=self.device), values
+
+    @torch.compiler.disable
+    def fork(self, src_slots, dst_slots, new_pages, prefix_lens=None) -> None:
+        """Make sequence slot ``dst_slots[i]`` a copy of slot ``src_slots[i]`` that SHARES its closed pages, for ``n`` forks in one launch
+        (``sage_kvfork``): one system prompt under many requests, ``n > 1`` samples of one prompt, beam search, a scratch copy to
+        verify draft tokens on.  With ``L = clamp(lens[s], 0, capacity)`` and ``P = L`` (or, with ``prefix_lens``, ``P = clamp(prefix_lens[i],
+        0, L)``), on the device:
+
+        * ``block_table[d]`` takes the entries of ``block_table[s]`` for the ``P // page_size`` whole pages, as they stand, and behind them
+          ``new_pages[i]`` -- the child's first own page (written whenever the table has an entry there, also when ``P`` ends on a page
+          boundary: the child's next append goes there);
+        * if ``P`` ends inside a page, the tiles of the parent's open page that hold keys are copied into ``new_pages[i]`` (copy-on-write;
+          nothing of the pool is written when either id lies outside ``[0, num_pages)``, the append's rule);
+        * ``v_scale`` / ``v_amax`` / ``k_mean``, the raw rows of the open 64-key block in ``k_tail`` / ``v_tail`` and ``lens`` of ``d`` become
+          those of ``s`` (``lens[d] = P``).
+
+        **A prefix shorter than the parent is rounded down to a multiple of 64 keys** (``P &= ~63`` when ``P < L``): only on a block boundary
+        are the parent's bytes exactly the prefix's own -- its open block was quantised over more rows, and the raw rows of a closed block are
+        gone.  The child takes the parent's frozen statistics, so every shared block is byte for byte what the child would have produced, and
+        :func:`~sageattention_amd.kv_cache.sageattn_kvcache` on the child returns bit for bit what it returns on the parent; afterwards the
+        two append independently.  A fork whose source or destination lies outside ``[0, B)``, or whose source is its destination, is skipped.
+
+        ``src_slots`` / ``dst_slots`` / ``new_pages`` (and ``prefix_lens``, or None): each a 1-D int32 / int64 tensor on the cache's device
+        (int64 is clamped and converted; never read on the host) or a sequence of ints, all of one length ``n >= 1``.  The contract:
+        ``dst_slots`` are distinct and disjoint from ``src_slots`` (one source may fork to many destinations in one call); ``new_pages`` are
+        distinct and named by no live table entry.  Sequences of ints are checked against it here, together with their ranges (ValueError);
+        tensors are not -- a violation gives wrong numbers, never an access outside a tensor.  There is no allocator and there are no
+        reference counts: which pages are free is the caller's to know.
+
+        One launch on the current stream, no host read, no synchronisation: with tensor arguments the call captures into a HIP graph and a
+        replay follows their, the lengths' and the table's contents."""
+        if not self._seeded:
+            raise ValueError("the cache has no statistics yet: seed(k_mean, v_amax) or from_prefill(...) before the first fork")
+        src, src_l = self._fork_index("src_slots", src_slots, self.B, "slot indices")
+        dst, dst_l = self._fork_index("dst_slots", dst_slots, self.B, "slot indices")
+        pages, pages_l = self._fork_index("new_pages", new_pages, self.num_pages, "page ids")
+        prefix = None if prefix_lens is None else self._fork_index("prefix_lens", prefix_lens, None, None)[0]
+        n = int(src.shape[0])
+        if n < 1 or any(t is not None and t.shape[0] != n for t in (dst, pages, prefix)):
+            raise ValueError(f"src_slots, dst_slots, new_pages and prefix_lens must have one length n >= 1 "
+                             f"(got {[int(t.shape[0]) for t in (src, dst, pages, prefix) if t is not None]})")
+        if n > 65535:
+            raise ValueError(f"at most 65535 forks per call (got {n})")
+        if dst_l is not None and len(set(dst_l)) != n:
+            raise ValueError(f"dst_slots must be distinct (got {dst_l!r})")
+        if dst_l is not None and src_l is not None and set(dst_l) & set(src_l):
+            raise ValueError(f"dst_slots must be disjoint from src_slots (got {src_l!r} -> {dst_l!r})")
+        if pages_l is not None and len(set(pages_l)) != n:
+            raise ValueError(f"new_pages must be distinct (got {pages_l!r})")
+        rc = _cabi_kvfork.load().sage_kvfork(
+            _p(self.k_int8), _p(self.k_scale), _p(self.v_image), _p(self.v_scale), _p(self.v_amax), _p(self.k_mean), _p(self.k_tail), _p(self.v_tail),
+            _p(self.lens), _p(self.block_table), self.block_table.stride(0), self.num_pages, self.page_size, self.max_pages_per_seq,
+            self.B, self.Hkv, self.D, _dtype_code(self.k_tail), _p(src), _p(dst), _p(pages), _p(prefix), n, _stream(self.k_int8))
+        _cabi.check(rc, "sage_kvfork")
 
     @classmethod
     @torch.compiler.disable
