@@ -82,7 +82,8 @@ SAGE_KVPAGED_API int sage_kvpaged_append(int8_t *k_int8, float *k_scale, void *v
  * max_pages_per_seq * page_size.  `attr` is that entry's SageLaunchAttr with the same meaning of q_start, window, SAGE_ATTR_GQA_PACK and
  * grid_out; the grid is the unpaged call's.  Refused by name: SAGE_ATTR_KV_SPLIT (pass 1 and the split's kernels do not look pages up), the
  * folded score form (SAGE_ATTR_FP8_FOLDED_SCORES) and SAGE_ATTR_FORCE_PERSISTENT (a paged launch takes the ordinary dispatch; a launch
- * workspace is accepted and ignored).
+ * workspace is accepted and ignored).  The exact split on a pool is an entry of its own, sage_kvpsplit_attn (include/sage_kvpsplit_gfx950.h),
+ * with this argument list.
  */
 SAGE_KVPAGED_API int sage_kvpaged_attn(const void *q, const int8_t *k_int8, const void *v_image, void *o, float *lse,
                                        const float *k_scale, const float *v_scale, const int32_t *kv_lens,

@@ -21,7 +21,7 @@ from typing import Any, NamedTuple, Optional
 import torch
 import torch.nn.functional as F
 
-from . import _cabi, _cabi_kvpaged, ops
+from . import _cabi, _cabi_kvpaged, _cabi_kvpsplit, ops
 from .quant import (LOG2E, _aligned, _cu_blocks, _dims, _p, _quant, _squeeze_km, _stream, channel_mean, channel_mean_kvlens, channel_mean_packed,
                     per_block_int8, per_block_int8_varlen, per_channel_fp8, per_channel_fp8_kvlens, per_channel_fp8_varlen, per_thread_int8_k_kvlens, prep_v_fp16, prep_v_fp16_varlen, prepass_fused_ok, prepass_kv_fp8, prepass_kv_varlen,
                     prepass_varlen_fused_ok, sub_mean, varlen_plan)
@@ -160,9 +160,10 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
     causal; a Python int): the number of keys a row sees up to and including its diagonal, 0 = unbounded (``SageLaunchAttr.window``);
     ``gqa_pack`` (with ``kv_lens``, ``Lq <= 32``, ``Hq / Hkv >= 2``): the query heads of a GQA group four to a workgroup (``SAGE_ATTR_GQA_PACK``);
     ``num_splits`` (with ``kv_lens``, ``Lq <= 128``, no window; 0 or 2 .. 255): that many key-range chunks, exactly (``SAGE_ATTR_KV_SPLIT``; the
-    split workspace is allocated here, from the shapes alone); ``paged`` (with ``kv_lens``, no split; a ``PagedQuantizedKVCache``): ``k_int8`` /
+    split workspace is allocated here, from the shapes alone); ``paged`` (with ``kv_lens``; a ``PagedQuantizedKVCache``): ``k_int8`` /
     ``v_image`` / ``k_scale`` are its pool of pages and the call goes through its block table (``sage_kvpaged_attn``), which takes the offsets,
-    the window and the packing flag and nothing else of the attributes."""
+    the window and the packing flag and nothing else of the attributes -- or, with ``num_splits``, ``sage_kvpsplit_attn``, the exact split
+    on the pool, which takes the offsets, the packing flag, the chunk count and the split workspace."""
     B, Hq, Lq, D, q_sb, q_sh, q_sl = _dims(q, tensor_layout)
     _, Hkv, Lk, _, k_sb, k_sh, k_sl = _dims(k_int8, tensor_layout)
     assert Hq % Hkv == 0, "num_qo_heads must be divisible by num_kv_heads"
@@ -176,8 +177,8 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
     assert not num_splits or (kv_lens is not None and not window and Lq <= 128)
     split_ws = torch.empty((_cabi.kv_split_ws_bytes(B, Hq, Lq, D, num_splits) // 4,), dtype=torch.float32, device=q.device) if num_splits else None
     if paged is not None:          # (no launch workspace, no trace buffer, no forced ticket route: the C entry's ordinary dispatch)
-        assert kv_lens is not None and not num_splits
-        attr = _cabi.launch_attr(grid_out=ops._hooks.grid_probe, q_start=q_start, window=window, gqa_pack=gqa_pack)
+        assert kv_lens is not None
+        attr = _cabi.launch_attr(launch_ws=split_ws, grid_out=ops._hooks.grid_probe, q_start=q_start, window=window, gqa_pack=gqa_pack, kv_split=num_splits)
     else:
         attr = ops.attn_attr(q.device, is_causal, B * Hq * ((Lq + 127) // 128), folded_scores and v_scale is not None, q_start=q_start, window=window,
                              gqa_pack=gqa_pack, kv_split=num_splits, split_ws=split_ws)
@@ -199,6 +200,14 @@ def _attn_fused_q(q, k_int8, v_image, v_scale, k_scale, tensor_layout, is_causal
         return o, lse
     if kv_lens is not None:
         assert v_scale is not None and not folded_scores and not v_rows
+        if paged is not None and num_splits:      # the exact split on a pool of pages: the same three launches through the block table
+            rc = _cabi_kvpsplit.load().sage_kvpsplit_attn(
+                _p(q), _p(k_int8), _p(v_image), _p(o), _p(lse), _p(k_scale), _p(v_scale), _p(kv_lens),
+                _p(paged.block_table), paged.block_table.stride(0), paged.num_pages, paged.page_size, paged.max_pages_per_seq,
+                B, Hq, Hkv, Lq, D, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, o_sb, o_sh, o_sl,
+                int(is_causal), float(sm_scale_log2), code, code, _stream(q), _cabi.attr_arg(attr))
+            ops.attn_check(rc, "sage_kvpsplit_attn", attr, q.device)
+            return o, lse
         if paged is not None:      # the same call on a pool of pages: Lk is the logical capacity, the K strides are a page's
             rc = _cabi_kvpaged.load().sage_kvpaged_attn(
                 _p(q), _p(k_int8), _p(v_image), _p(o), _p(lse), _p(k_scale), _p(v_scale), _p(kv_lens),

@@ -78,8 +78,10 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
     // packed GQA groups: the kv_lens family (above: fused per-thread Q, FP8 PV, the exact score form, dense, no split), a group to pack and
     // no more query rows than one wave's slab holds
     if (v.gqa_pack && (!v.kv_lens || p.Lq > 32 || p.group < 2 || p.nqblk != 1)) return false;
-    // a pool of pages behind a block table: the kv_lens family without the split; whole pages of 64 << page_shift keys, p.Lk the logical capacity
-    if (v.paged != nullptr && (!v.kv_lens || v.seeded || p.kv_split > 1 || v.paged->block_table == nullptr || v.paged->page_shift < 0 ||
+    // a pool of pages behind a block table: the kv_lens family, or its split's pass 2 (seeded with kv_lens, checked above: the chunks folded into
+    // p.Hkv, the pool's heads p.Hkv / p.kv_split); whole pages of 64 << page_shift keys, p.Lk the logical capacity
+    if (v.paged != nullptr && (!v.kv_lens || (v.seeded ? (p.kv_split < 2 || p.Hkv % p.kv_split != 0) : p.kv_split > 1) ||
+                               v.paged->block_table == nullptr || v.paged->page_shift < 0 ||
                                v.paged->page_shift > 20 || v.paged->num_pages < 1 || v.paged->max_pages < 1 ||
                                (long)p.Lk != ((long)v.paged->max_pages << (6 + v.paged->page_shift)) || p.nks != (4 << v.paged->page_shift))) return false;
     return true;
@@ -100,6 +102,7 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     const AttnForm f = attn_form(p, v, o);
     if (v.paged != nullptr) {     // the paged kernel of the same form: same grid, the ordinary dispatch
         p.sched = nullptr;
+        if (f.seed) return (f.D == 128 ? launch_attn_paged_units<128, SAGE_PAGED_KS_UNITS> : launch_attn_paged_units<64, SAGE_PAGED_KS_UNITS>)(pack(f), p, *v.paged, nwork, o);
         return f.gpack ? (f.D == 128 ? launch_attn_paged_units<128, SAGE_PAGED_G_UNITS> : launch_attn_paged_units<64, SAGE_PAGED_G_UNITS>)(pack(f), p, *v.paged, nwork, o)
                        : (f.D == 128 ? launch_attn_paged_units<128, SAGE_PAGED_UNITS> : launch_attn_paged_units<64, SAGE_PAGED_UNITS>)(pack(f), p, *v.paged, nwork, o);
     }

@@ -23,7 +23,7 @@
     static constexpr bool WINDOW = F.window;
     static constexpr bool QSTART = F.qstart;
     static constexpr bool KVLEN = F.kvlen;
-    static_assert(!PAGED || (KVLEN && !SEED && PV_FP8), "paged tiles: the kv_lens family without the split");
+    static_assert(!PAGED || (KVLEN && PV_FP8), "paged tiles: the kv_lens family, its split (SEED with KVLEN) included");
     // The parameter block is read through the kernarg segment pointer, and inside the persistent loop through a copy of that pointer the
     // compiler cannot see through (an empty asm): otherwise every scalar load of a parameter is hoisted out of the loop and stays live in
     // SGPRs across it (128 SGPRs and 16-400 VGPRs spilled in every instantiation).  AttnParams is the kernel's only explicit argument.
@@ -222,6 +222,8 @@
     int qs_stride, ks_tstride;
     // (PAGED) the item's first logical tile (a window's kc0w / 64)
     [[maybe_unused]] int pt0 = 0;
+    // (PAGED with SEED) the chunk is folded into the kv heads, the pool is not: the unsplit kv head hk0 and the pool's heads per page, p.Hkv / S
+    [[maybe_unused]] int phk = 0, pnh = 0;
     if (p.cu_q != nullptr) {              // varlen: packed [sum L, H, D]
         // the prefix arrays are read-only here and the sequence index is wave-uniform: scalar loads, requested together (as vector loads they
         // were a memory round trip of their own behind the work list's; measured neutral at C4, profiles/r4_run_p_attention_phase_trace.txt)
@@ -274,14 +276,24 @@
         const int left = lenb - kc0;
         Lk = left < 0 ? 0 : (left < p.kv_base ? left : p.kv_base);
         q_off = (long)b * p.q_sb + (long)(hk0 * p.group + (h - hk * p.group)) * p.q_sh;
+        if constexpr (PAGED) k_off = (long)hk0 * p.k_sh;             // (the page's p.k_sb and the tile inside it come per tile: k_tile, through pt0)
+        else
         k_off = (long)b * p.k_sb + (long)hk0 * p.k_sh + (long)kc0 * p.k_sl;
         o_off = (long)b * p.o_sb + (long)h * p.o_sh;
         v_tile0 = bh0 * (p.nks >> 2) + (kc0 >> 6);      // (per-thread k scales: four per 64-key tile, so nks / 4 tiles per head of the tensor)
         v_tstride = 1;
         qs_ptr = nullptr;
         qs_stride = 0;
+        if constexpr (PAGED) ks_ptr = p.k_scale;                     // (the slots of (page, kv head hk0): ks_slot)
+        else
         ks_ptr = p.k_scale + bh0 * p.nks + (kc0 >> 6) * 4;
         ks_tstride = 4;
+        if constexpr (PAGED) {
+            // a chunk need not start on a page boundary: its tile t is logical tile pt0 + t, as a window's
+            pt0 = kc0 >> 6;
+            phk = hk0;
+            pnh = p.Hkv / p.kv_split;
+        }
     } else if constexpr (SEED) {
         // exact split (pass 2): chunk `chunk` of kv head hk0 starts at key kc0; q, k, its scales and the V image are the unsplit call's
         const int hk0 = hk / p.kv_split, kc0 = p.kv_base + (hk - hk0 * p.kv_split) * Lk;
@@ -475,11 +487,19 @@
         else return nullptr;
     };
     [[maybe_unused]] auto v_tile = [&]([[maybe_unused]] int t, [[maybe_unused]] int pg) -> long {     // the V image's index
-        if constexpr (PAGED) return ((long)pg * p.Hkv + hk) * (p.nks >> 2) + tile_in_page(t);
+        if constexpr (PAGED) {
+            if constexpr (SEED) return ((long)pg * pnh + phk) * (p.nks >> 2) + tile_in_page(t);
+            else
+            return ((long)pg * p.Hkv + hk) * (p.nks >> 2) + tile_in_page(t);
+        }
         else return 0;
     };
     [[maybe_unused]] auto ks_slot = [&]([[maybe_unused]] int t, [[maybe_unused]] int pg) -> long {    // the tile's first K scale slot
-        if constexpr (PAGED) return ((long)pg * p.Hkv + hk) * p.nks + tile_in_page(t) * 4;
+        if constexpr (PAGED) {
+            if constexpr (SEED) return ((long)pg * pnh + phk) * p.nks + tile_in_page(t) * 4;
+            else
+            return ((long)pg * p.Hkv + hk) * p.nks + tile_in_page(t) * 4;
+        }
         else return 0;
     };
     int lane_g = lane;                      // the lane index as the ragged tile loads see it (laundered behind the pipelined loops, see there)
@@ -620,8 +640,8 @@
         else slot = (rin >> 5) * 8 + (rin & 7);      // per-thread: quant_per_thread.py:27-37
         qsc = qs_ptr[slot * qs_stride];
     } else {
-        // Fused Q quantisation.  (The per-thread form has two restatements that must stay bit-equal, in sage_split_exact.hip: chunk_max_kernel's
-        // prologue and cm_quant_q.)  The lane holds channels [32 ks + 16 g, +16) of its row for every ks -- the layout of
+        // Fused Q quantisation.  (The per-thread form has two restatements that must stay bit-equal: chunk_max_kernel's
+        // prologue in sage_split_exact.hip and cm_quant_q in sage_chunk_max.h.)  The lane holds channels [32 ks + 16 g, +16) of its row for every ks -- the layout of
         // the MFMA B operand -- so it quantises exactly the bytes it needs.  A per-thread group is the rows
         // r, r+8, r+16, r+24 of the wave's 32-row tile, all 128 channels: lanes n = r (mod 8), both halves g.
         constexpr int QDT = (QF == 1 || QF == 3) ? DT_F16 : DT_BF16;

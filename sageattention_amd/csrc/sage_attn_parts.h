@@ -22,6 +22,9 @@ template <int D, AttnUnit... U>
 hipError_t launch_attn_paged_units(uint32_t form, const AttnParams &p, const PagedArgs &g, int nwork, const AttnLaunchOpts &l);
 #define SAGE_PAGED_UNITS UNIT_F8K, UNIT_F8Q, UNIT_F8W
 #define SAGE_PAGED_G_UNITS UNIT_F8G
+#define SAGE_PAGED_KS_UNITS UNIT_F8KS      // sage_attn_d{128,64}_f8pks.hip: pass 2 of the kv_lens family's split on a paged cache
+extern template hipError_t launch_attn_paged_units<128, SAGE_PAGED_KS_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_paged_units<64, SAGE_PAGED_KS_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_paged_units<128, SAGE_PAGED_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_paged_units<64, SAGE_PAGED_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_paged_units<128, SAGE_PAGED_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);

@@ -2,6 +2,7 @@
 // Validates arguments, fills the kernel parameter blocks, launches on the caller's stream.
 #include "../../include/sage_gfx950.h"
 #include "../../include/sage_kvpaged_gfx950.h"
+#include "../../include/sage_kvpsplit_gfx950.h"
 #include "sage_common.h"
 #include "sage_kernels.h"
 #include "sage_work_order.h"
@@ -127,6 +128,7 @@ struct AttnCall {
                                      // (SageLaunchAttr::q_start, read by attn_run), so they have no field here
     int kv_split;                    // > 1: the (inexact) split, the chunks folded into Hq / Hkv by the entry point
     const sage::PagedArgs *paged;    // sage_kvpaged_attn: k / v / k_scale are a pool of pages behind a block table (with kv_lens; Lk = the logical capacity)
+    bool paged_split;                // sage_kvpsplit_attn (with paged): the exact split on that pool -- SAGE_ATTR_KV_SPLIT is required instead of refused
     int is_causal, gran, q_warp, pv_accum, q_dtype, out_dtype;
     float sm_scale_log2, q_premul;
     void *stream; const SageLaunchAttr *attr;
@@ -189,15 +191,24 @@ void fill_geometry(const AttnCall &c, bool kthread, sage::AttnParams &p)
 inline int64_t r128(int64_t x) { return (x + 127) / 128 * 128; }
 inline int64_t kv_split_ws_bytes(int64_t B, int64_t Hq, int64_t Lq, int64_t D, int64_t S) { return 2 * r128(4 * B * Hq * S * Lq) + r128(4 * B * Hq * S * Lq * D); }
 
+// the split workspace of a call of S chunks (`who`: the prefix of the message, the flag or the entry that requires it)
+int kv_split_ws_check(const char *who, const void *ws, int64_t ws_bytes, int64_t B, int64_t Hq, int64_t Lq, int64_t D, int64_t S)
+{
+    const int64_t need = kv_split_ws_bytes(B, Hq, Lq, D, S);
+    SAGE_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 127u) == 0 && ws_bytes >= need,
+                 "%s: launch_ws is the split workspace, %lld bytes of device memory, 128-byte aligned (got %lld bytes at %p)",
+                 who, (long long)need, (long long)ws_bytes, ws);
+    return SAGE_OK;
+}
+
 // The kv_lens family's exact split (sage_attn_fused_q_pv_f8_kvlens with SAGE_ATTR_KV_SPLIT; the call is validated -- v_mean null --, p / v describe
 // the unsplit launch): pass 1 (the chunk maxima), pass 2 (the chunks folded into the kv heads, seeded, FP32 partials) and the merge, on the call's stream.
+// (sage_kvpsplit_attn, c.paged set: the same three launches, pass 1 and pass 2 through the block table; Lk is the logical capacity)
 int kv_split_run(const AttnCall &c, const LaunchAttr &la, const sage::AttnParams &p0, const sage::AttnVariant &v0)
 {
     const int S = la.kv_split, tiles = ((c.Lk + 63) / 64 + S - 1) / S;      // T = ceil(ceil(Lk / 64) / S), from the padded Lk
-    const int64_t need = kv_split_ws_bytes(c.B, c.Hq, c.Lq, c.D, S);
-    SAGE_REQUIRE(la.split_ws != nullptr && (reinterpret_cast<uintptr_t>(la.split_ws) & 127u) == 0 && la.split_ws_bytes >= need,
-                 "SAGE_ATTR_KV_SPLIT: launch_ws is the split workspace, %lld bytes of device memory, 128-byte aligned (got %lld bytes at %p)",
-                 (long long)need, (long long)la.split_ws_bytes, la.split_ws);
+    if (const int rc = kv_split_ws_check(c.paged != nullptr ? "sage_kvpsplit_attn: SAGE_ATTR_KV_SPLIT" : "SAGE_ATTR_KV_SPLIT", la.split_ws, la.split_ws_bytes,
+                                         c.B, c.Hq, c.Lq, c.D, S)) return rc;
     SAGE_REQUIRE((int64_t)c.B * c.Hq * S < ((int64_t)1 << 31), "SAGE_ATTR_KV_SPLIT: grid too large");
     const int64_t rows = (int64_t)c.B * c.Hq * S * c.Lq;
     float *chunk_max = static_cast<float *>(la.split_ws);
@@ -211,6 +222,9 @@ int kv_split_run(const AttnCall &c, const LaunchAttr &la, const sage::AttnParams
     m.S = S; m.tiles = tiles; m.nks = p0.nks;
     m.q_sb = c.qs.sb; m.q_sh = c.qs.sh; m.q_sl = c.qs.sl; m.k_sb = c.ks.sb; m.k_sh = c.ks.sh; m.k_sl = c.ks.sl;
     m.sm_scale_log2 = c.sm_scale_log2; m.q_dtype = c.q_dtype; m.causal = c.is_causal != 0;
+    if (c.paged != nullptr) {
+        if (const int rc = check_launch(sage::launch_chunk_max_lens_paged(m, *c.paged, stream), "sage_kvpsplit_attn pass 1 launch")) return rc;
+    } else
     if (const int rc = check_launch(sage::launch_chunk_max_lens(m, stream), "sage_attn_fused_q_pv_f8_kvlens (SAGE_ATTR_KV_SPLIT) pass 1 launch")) return rc;
 
     // pass 2: the unsplit call's operands read in place, the chunks folded into the kv-head dimension (kv head hk0 * S + chunk); FP32 partials
@@ -223,13 +237,15 @@ int kv_split_run(const AttnCall &c, const LaunchAttr &la, const sage::AttnParams
     p.seed_max = chunk_max; p.seed_chunks = S; p.seed_first = 0;
     p.sched = nullptr;
     v.seeded = true;
-    if (const int rc = check_launch(sage::launch_attention(p, v, la.opts), "sage_attn_fused_q_pv_f8_kvlens (SAGE_ATTR_KV_SPLIT) pass 2 launch")) return rc;
+    if (const int rc = check_launch(sage::launch_attention(p, v, la.opts), c.paged != nullptr ? "sage_kvpsplit_attn pass 2 launch" :
+                                    "sage_attn_fused_q_pv_f8_kvlens (SAGE_ATTR_KV_SPLIT) pass 2 launch")) return rc;
 
     sage::SplitMergeParams g{};
     g.o_part = o_part; g.lse_part = lse_part; g.o_tail = nullptr; g.lse_tail = nullptr; g.o_out = c.o; g.lse_out = c.lse;
     g.B = c.B; g.S = S; g.H = c.Hq; g.L = c.Lq; g.D = c.D; g.group = c.Hq / c.Hkv;
     g.o_sb = c.os.sb; g.o_sh = c.os.sh; g.o_sl = c.os.sl; g.dtype = c.out_dtype;
-    return check_launch(sage::launch_merge_split_f32(g, stream), "sage_attn_fused_q_pv_f8_kvlens (SAGE_ATTR_KV_SPLIT) merge launch");
+    return check_launch(sage::launch_merge_split_f32(g, stream), c.paged != nullptr ? "sage_kvpsplit_attn merge launch" :
+                        "sage_attn_fused_q_pv_f8_kvlens (SAGE_ATTR_KV_SPLIT) merge launch");
 }
 
 // validates the call, fills the kernel parameter block, launches
@@ -239,6 +255,24 @@ int attn_run(const AttnCall &c)
     const bool fp8 = c.pv_fp8, varlen = c.varlen, split = c.kv_split > 1;
     LaunchAttr la;
     // (a pool of pages: what it does not take is refused by name, in front of everything else about the attributes)
+    if (c.paged != nullptr && c.paged_split) {
+        // sage_kvpsplit_attn: what the split needs of the attributes, by the entry's name and in front of everything else about them -- the flag,
+        // S, one query block, no window, the exact score form, the ordinary dispatch, the workspace (the shapes it is sized by are checked below)
+        const char *const e = "sage_kvpsplit_attn";
+        SageLaunchAttr a{};
+        if (c.attr != nullptr && c.attr->struct_bytes >= 8) memcpy(&a, c.attr, c.attr->struct_bytes > sizeof(a) ? sizeof(a) : c.attr->struct_bytes);
+        if (c.attr != nullptr && c.attr->struct_bytes < offsetof(SageLaunchAttr, window) + sizeof(a.window)) a.window = 0;
+        const int S = (int)((a.flags >> SAGE_ATTR_KV_SPLIT_SHIFT) & 0xffu);
+        SAGE_REQUIRE(c.attr != nullptr && c.attr->struct_bytes >= 8 && (a.flags & SAGE_ATTR_KV_SPLIT) != 0,
+                     "%s: attr must carry SAGE_ATTR_KV_SPLIT (the unsplit call on a paged cache is sage_kvpaged_attn)", e);
+        SAGE_REQUIRE(S >= 2 && S <= 255, "%s: a chunk count of 2 .. 255 in flags bits 16-23 (got %d)", e, S);
+        SAGE_REQUIRE(c.Lq <= 128, "%s: Lq <= 128, one query block (got %d)", e, c.Lq);
+        SAGE_REQUIRE(a.window == 0, "%s: no window with a split (got %d)", e, a.window);
+        SAGE_REQUIRE(!(a.flags & SAGE_ATTR_FP8_FOLDED_SCORES), "%s: SAGE_ATTR_FP8_FOLDED_SCORES is not supported on a paged cache (the exact score form only)", e);
+        SAGE_REQUIRE(!(a.flags & SAGE_ATTR_FORCE_PERSISTENT), "%s: SAGE_ATTR_FORCE_PERSISTENT is not supported (the split takes the ordinary dispatch only)", e);
+        if (const int rc = kv_split_ws_check("sage_kvpsplit_attn: SAGE_ATTR_KV_SPLIT", a.launch_ws, a.launch_ws_bytes, c.B, c.Hq > 0 ? c.Hq : 0, c.Lq > 0 ? c.Lq : 0,
+                                             c.D > 0 ? c.D : 0, S)) return rc;
+    } else
     if (c.paged != nullptr && c.attr != nullptr && c.attr->struct_bytes >= 8) {
         const unsigned f = c.attr->flags;
         SAGE_REQUIRE(!(f & (SAGE_ATTR_KV_SPLIT | (0xffu << SAGE_ATTR_KV_SPLIT_SHIFT))),
@@ -1053,6 +1087,34 @@ SAGE_KVPAGED_API int sage_kvpaged_attn(const void *q, const int8_t *k_int8, cons
     AttnCall c{};
     c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
     c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = max_pages_per_seq * page_size; c.D = D;
+    c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
+}
+
+// sage_kvpaged_attn as the exact split (include/sage_kvpsplit_gfx950.h): SAGE_ATTR_KV_SPLIT required, pass 1 / pass 2 / merge through the table
+SAGE_KVPSPLIT_API int sage_kvpsplit_abi_version(void) { return SAGE_KVPSPLIT_ABI_VERSION; }
+
+SAGE_KVPSPLIT_API int sage_kvpsplit_attn(const void *q, const int8_t *k_int8, const void *v_image, void *o, float *lse,
+                                         const float *k_scale, const float *v_scale, const int32_t *kv_lens,
+                                         const int32_t *block_table, int64_t bt_stride, int num_pages, int page_size, int max_pages_per_seq,
+                                         int B, int Hq, int Hkv, int Lq, int D,
+                                         int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                         int64_t o_sb, int64_t o_sh, int64_t o_sl,
+                                         int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
+{
+    SAGE_REQUIRE(q && k_int8 && v_image && o && k_scale && v_scale, "sage_kvpsplit_attn: null tensor pointer (only lse may be null)");
+    SAGE_REQUIRE(kv_lens, "sage_kvpsplit_attn: null kv_lens");
+    const char *const e = "sage_kvpsplit_attn";
+    sage::PagedArgs g;
+    if (const int rc = sage::paged_args(e, block_table, bt_stride, num_pages, page_size, max_pages_per_seq, g)) return rc;
+    if (const int rc = sage::kv_check_batch(e, B, Hkv)) return rc;
+    if (const int rc = sage::paged_check_table_aligned(e, block_table)) return rc;
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
+    c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g;
+    c.paged_split = true;
     c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = Lq; c.Lk = max_pages_per_seq * page_size; c.D = D;
     c.qs = {q_sb, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {o_sb, o_sh, o_sl};
     c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;

@@ -330,6 +330,8 @@ struct ChunkMaxLensParams {
     int q_dtype, causal;
 };
 hipError_t launch_chunk_max_lens(const ChunkMaxLensParams &p, hipStream_t stream);
+// ... over a paged cache (sage_split_paged.hip): k / k_scale / k_sb / Hkv / nks describe the pool of pages, Lk is the logical capacity, g the table
+hipError_t launch_chunk_max_lens_paged(const ChunkMaxLensParams &p, const PagedArgs &g, hipStream_t stream);
 
 // ---- the C ABI's error channel for entry points defined outside sage_cabi.hip (sage_kv_cache.hip): stores the thread-local message that
 // sage_last_error() returns and hands `code` back

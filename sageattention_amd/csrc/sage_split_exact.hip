@@ -17,12 +17,10 @@
 #include "sage_common.h"
 #include "sage_kernels.h"
 #include "sage_quant_math.h"
+#include "sage_chunk_max.h"
 #include <climits>
 
 namespace sage {
-
-// c/d register r of a 32x32 MFMA tile -> row index inside the tile (lane half g), as sage_attn_kernel.h's crow
-__device__ __forceinline__ int cm_crow(int r, int g) { return (r & 3) + 8 * (r >> 2) + 4 * g; }
 
 template <int D, int QDT, bool CAUSAL>
 __global__ void __launch_bounds__(256, 2)
@@ -44,7 +42,7 @@ chunk_max_kernel(const ChunkMaxParams p)
     if (row0 >= p.Lq) return;                   // (waves are independent: no LDS, no barrier)
 
     // ---- Q: the fused-Q prologue of sage_attn_kernel (QF 1 / 2), per-thread groups = rows r, r+8, r+16, r+24 of the wave, both halves ----
-    // (one of THREE copies of this quantiser that must stay bit-equal: sage_attn_kernel.h's fused-Q prologue, this one, and cm_quant_q below)
+    // (one of THREE copies of this quantiser that must stay bit-equal: sage_attn_kernel.h's fused-Q prologue, this one, and cm_quant_q of sage_chunk_max.h)
     v4i qf[KSTEPS];
     float qsc;
     {
@@ -159,47 +157,6 @@ hipError_t launch_chunk_max(const ChunkMaxParams &p_in, hipStream_t stream)
     SAGE_CM(64, DT_F16, false)  SAGE_CM(64, DT_F16, true)  SAGE_CM(64, DT_BF16, false)  SAGE_CM(64, DT_BF16, true)
 #undef SAGE_CM
     return hipErrorInvalidValue;
-}
-
-// chunk_max_kernel's Q prologue as a function (that kernel keeps its own copy: its instruction stream stays what it was; with
-// sage_attn_kernel.h's fused-Q prologue that makes THREE copies that must stay bit-equal -- change one, change all) -- the fused-Q
-// prologue of sage_attn_kernel (QF 1 / 2) for the lane's row `qrow` (ok: the row exists, else zeros): per-thread groups = rows
-// r, r+8, r+16, r+24 of the wave, both lane halves; the lane's INT8 fragments (channels 32 ks + 16 g .. + 15) and its group's scale
-template <int D, int QDT>
-__device__ __forceinline__ void cm_quant_q(const uint16_t *qrow, bool ok, int g, v4i (&qf)[D / 32], float &qsc)
-{
-    constexpr int KSTEPS = D / 32;
-    float x[KSTEPS][16];
-    float amax = 0.0f;
-#pragma unroll
-    for (int ks = 0; ks < KSTEPS; ks++) {
-        v4u raw[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-        if (ok) {
-            raw[0] = *reinterpret_cast<const v4u *>(qrow + 32 * ks + 16 * g);
-            raw[1] = *reinterpret_cast<const v4u *>(qrow + 32 * ks + 16 * g + 8);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const unsigned w = raw[j >> 3][(j & 7) >> 1];
-            const float f = ld16<QDT>((uint16_t)((j & 1) ? (w >> 16) : (w & 0xffffu)));
-            x[ks][j] = f;
-            amax = fmaxf(amax, fabsf(f));
-        }
-    }
-    amax = fmaxf(amax, __shfl_xor(amax, 8));
-    amax = fmaxf(amax, __shfl_xor(amax, 16));
-    amax = fmaxf(amax, __shfl_xor(amax, 32));
-    const float sc = quant_scale(amax, QS_TRITON_THREAD);
-    const float y = quant_recip(sc);
-    qsc = sc;
-#pragma unroll
-    for (int ks = 0; ks < KSTEPS; ks++) {
-        int q8[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) q8[j] = quant_round_triton_nz(x[ks][j], sc, y);
-#pragma unroll
-        for (int w = 0; w < 4; w++) qf[ks][w] = (int)pack_int8x4(q8[4 * w], q8[4 * w + 1], q8[4 * w + 2], q8[4 * w + 3]);
-    }
 }
 
 // The same for the kv_lens family's split (ChunkMaxLensParams): sample b's keys end at len_b = clamp(kv_lens[b], 0, Lk) and, causal, row i sees

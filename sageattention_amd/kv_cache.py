@@ -246,19 +246,12 @@ class QuantizedKVCache(_KVCacheBase):
         return cache._prefill(k, v, cls._prefill_lens(kv_lens, B, L, k.device), tensor_layout, smooth_k, v_headroom)
 
 
-@torch.compiler.disable
-def sageattn_kvcache(q: torch.Tensor, cache, tensor_layout: str = "HND", is_causal: bool = False, causal_align: str = "top_left",
-                     q_start=None, window_size=None, pack_gqa=False, num_splits=None, sm_scale: Optional[float] = None, return_lse: bool = False):
-    """Attention of ``q`` (``[B, Hq, Lq, D]`` HND / ``[B, Lq, Hq, D]`` NHD, the cache's dtype) to the cache's first ``cache.lens[b]`` keys per
-    sample: ``sageattn_qk_int8_pv_fp8_cuda(q, k, v, kv_lens=cache.lens, ...)`` without its pre-pass.  ``is_causal``, ``causal_align``,
-    ``q_start``, ``window_size``, ``pack_gqa``, ``num_splits``, ``sm_scale`` and ``return_lse`` mean what they mean there and raise the same
-    ValueErrors; the padded key length of the call is ``cache.capacity``.  Nothing reads the lengths on the host.
-
-    ``cache`` may also be a :class:`~sageattention_amd.paged_kv_cache.PagedQuantizedKVCache`: the same call through its block table
-    (``sage_kvpaged_attn``), bit for bit the result on a contiguous cache of the same content; ``num_splits`` other than None is refused
-    there."""
+def _attend(name, q, cache, tensor_layout, is_causal, causal_align, q_start, window_size, pack_gqa, num_splits, sm_scale, return_lse,
+            paged_split: bool):
+    """What :func:`sageattn_kvcache` and :func:`~sageattention_amd.paged_kv_split.sageattn_kvcache_split` do (``name``: the caller's, for the
+    messages).  ``paged_split``: a paged cache takes ``num_splits`` (the second name) instead of refusing it (the first)."""
     if torch.compiler.is_compiling():
-        raise ValueError("sageattn_kvcache is not supported under torch.compile")
+        raise ValueError(f"{name} is not supported under torch.compile")
     if not isinstance(cache, _KVCacheBase):
         raise ValueError(f"cache must be a QuantizedKVCache or a PagedQuantizedKVCache (got {type(cache).__name__})")
     _layout_ok(tensor_layout)
@@ -277,7 +270,8 @@ def sageattn_kvcache(q: torch.Tensor, cache, tensor_layout: str = "HND", is_caus
         raise ValueError("Last dim of q must be contiguous.")
     if not cache._seeded:
         raise ValueError("the cache has no statistics yet: seed(k_mean, v_amax) or from_prefill(...) first")
-    cache._refuse_keywords(num_splits)
+    if not paged_split:
+        cache._refuse_keywords(num_splits)
     # the keywords' checks and meanings are sageattn_qk_int8_pv_fp8_cuda's: one resolver (no kv_lens keyword here; the route's fixed options)
     call = core._kv_family_args(q, cache._k_logical(tensor_layout), tensor_layout, is_causal, None, q_start, causal_align, window_size, pack_gqa,
                                 num_splits, "per_thread", "fp32+fp16", False, {})
@@ -290,3 +284,18 @@ def sageattn_kvcache(q: torch.Tensor, cache, tensor_layout: str = "HND", is_caus
         lse_correction = core._lse_correction(q, cache.k_mean.unsqueeze(1 if tensor_layout == "NHD" else 2), tensor_layout)
     return core._attn_kv_family(call, q, cache.lens, cache.lens, cache._k_operand(tensor_layout), cache.v_image, cache.v_scale, cache.k_scale,
                                 tensor_layout, sm_scale, return_lse, D, smooth_k, lse_correction, paged=cache if cache._paged else None)
+
+
+@torch.compiler.disable
+def sageattn_kvcache(q: torch.Tensor, cache, tensor_layout: str = "HND", is_causal: bool = False, causal_align: str = "top_left",
+                     q_start=None, window_size=None, pack_gqa=False, num_splits=None, sm_scale: Optional[float] = None, return_lse: bool = False):
+    """Attention of ``q`` (``[B, Hq, Lq, D]`` HND / ``[B, Lq, Hq, D]`` NHD, the cache's dtype) to the cache's first ``cache.lens[b]`` keys per
+    sample: ``sageattn_qk_int8_pv_fp8_cuda(q, k, v, kv_lens=cache.lens, ...)`` without its pre-pass.  ``is_causal``, ``causal_align``,
+    ``q_start``, ``window_size``, ``pack_gqa``, ``num_splits``, ``sm_scale`` and ``return_lse`` mean what they mean there and raise the same
+    ValueErrors; the padded key length of the call is ``cache.capacity``.  Nothing reads the lengths on the host.
+
+    ``cache`` may also be a :class:`~sageattention_amd.paged_kv_cache.PagedQuantizedKVCache`: the same call through its block table
+    (``sage_kvpaged_attn``), bit for bit the result on a contiguous cache of the same content; ``num_splits`` other than None is refused
+    there (:func:`~sageattention_amd.paged_kv_split.sageattn_kvcache_split` takes it)."""
+    return _attend("sageattn_kvcache", q, cache, tensor_layout, is_causal, causal_align, q_start, window_size, pack_gqa, num_splits, sm_scale,
+                   return_lse, False)
