@@ -84,6 +84,10 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
                                v.paged->block_table == nullptr || v.paged->page_shift < 0 ||
                                v.paged->page_shift > 20 || v.paged->num_pages < 1 || v.paged->max_pages < 1 ||
                                (long)p.Lk != ((long)v.paged->max_pages << (6 + v.paged->page_shift)) || p.nks != (4 << v.paged->page_shift))) return false;
+    // packed query rows on that pool: the paged q_start / window kernels (no packed GQA groups, no split); the prefix array is the third kernel
+    // argument, p.cu_q stays null -- the dense grid and the dense branches of the kernel -- and the packed lse needs its head stride
+    if (v.ragged != nullptr && (v.paged == nullptr || !v.q_start || !v.causal || v.gqa_pack || v.seeded || varlen || v.ragged->cu_q == nullptr ||
+                                v.ragged->total_q < 1 || (p.lse != nullptr && p.lse_sh < v.ragged->total_q))) return false;
     return true;
 }
 
@@ -102,6 +106,8 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     const AttnForm f = attn_form(p, v, o);
     if (v.paged != nullptr) {     // the paged kernel of the same form: same grid, the ordinary dispatch
         p.sched = nullptr;
+        if (v.ragged != nullptr)      // packed query rows: the ragged paged kernel of the form (the q_start / window forms, route_exists)
+            return (f.D == 128 ? launch_attn_ragged_units<128, SAGE_RAGGED_UNITS> : launch_attn_ragged_units<64, SAGE_RAGGED_UNITS>)(pack(f), p, *v.paged, *v.ragged, nwork, o);
         if (f.seed) return (f.D == 128 ? launch_attn_paged_units<128, SAGE_PAGED_KS_UNITS> : launch_attn_paged_units<64, SAGE_PAGED_KS_UNITS>)(pack(f), p, *v.paged, nwork, o);
         return f.gpack ? (f.D == 128 ? launch_attn_paged_units<128, SAGE_PAGED_G_UNITS> : launch_attn_paged_units<64, SAGE_PAGED_G_UNITS>)(pack(f), p, *v.paged, nwork, o)
                        : (f.D == 128 ? launch_attn_paged_units<128, SAGE_PAGED_UNITS> : launch_attn_paged_units<64, SAGE_PAGED_UNITS>)(pack(f), p, *v.paged, nwork, o);

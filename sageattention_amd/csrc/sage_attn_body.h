@@ -1,7 +1,8 @@
-// sage_attn_body.h -- the body of sage_attn_kernel<FORM> and of sage_attn_paged_kernel<FORM> (sage_attn_kernel.h, which documents the flags): a code
-// fragment, included INSIDE the two kernel functions with SAGE_ATTN_BODY_PAGED defined as false / true.  Not a header of its own: no include
-// guard, no declarations.
+// sage_attn_body.h -- the body of sage_attn_kernel<FORM>, of sage_attn_paged_kernel<FORM> and of sage_attn_paged_varlen_kernel<FORM>
+// (sage_attn_kernel.h, which documents the flags): a code fragment, included INSIDE the three kernel functions with SAGE_ATTN_BODY_PAGED defined
+// as false / true / true and SAGE_ATTN_BODY_RAGGED as false / false / true.  Not a header of its own: no include guard, no declarations.
     static constexpr bool PAGED = SAGE_ATTN_BODY_PAGED;
+    static constexpr bool RAGGED = SAGE_ATTN_BODY_RAGGED;
     // The form's fields under the names the body uses.  (static: the body's lambdas capture by reference, and a plain constexpr local that one of
     // them passes on by reference becomes a captured stack slot -- folded away later, but sixteen D = 128 FP16-PV kernels then allocate their
     // registers differently, 217 - 229 VGPRs where these give 219 - 226.)
@@ -24,6 +25,7 @@
     static constexpr bool QSTART = F.qstart;
     static constexpr bool KVLEN = F.kvlen;
     static_assert(!PAGED || (KVLEN && PV_FP8), "paged tiles: the kv_lens family, its split (SEED with KVLEN) included");
+    static_assert(!RAGGED || (PAGED && CAUSAL && QSTART && !SEED && !GPACK), "packed query rows: the paged q_start / window kernels");
     // The parameter block is read through the kernarg segment pointer, and inside the persistent loop through a copy of that pointer the
     // compiler cannot see through (an empty asm): otherwise every scalar load of a parameter is hoisted out of the loop and stays live in
     // SGPRs across it (128 SGPRs and 16-400 VGPRs spilled in every instantiation).  AttnParams is the kernel's only explicit argument.
@@ -311,6 +313,18 @@
         // split-KV (p.kv_split = S > 1): the key range is folded into the kv-head dimension, kv head hk = hk0 * S + chunk and query
         // head h = hk * group + g; the query rows are those of head hk0 * group + g (read in place, no per-chunk copy of Q)
         const int hq = p.kv_split > 1 ? (hk / p.kv_split) * p.group + (h - hk * p.group) : h;
+        // (RAGGED) the sample's rows of the packed q / o / lse: the two prefix words through scalar loads (wave-uniform index), clamped before
+        // anything is formed from them (ragged_rows: 0 <= rq0 <= rq0 + Lq <= total_q, Lq <= p.Lq = max_seqlen_q); a query block past the
+        // sample's last row leaves as the packed route's does
+        [[maybe_unused]] int rq0 = 0;
+        if constexpr (RAGGED) {
+            typedef const __attribute__((address_space(4))) int *cint_p;
+            typedef const __attribute__((address_space(4))) RaggedArgs *kragged_t;
+            const kragged_t r = (kragged_t)((const __attribute__((address_space(4))) char *)kp + kRaggedArgsOffset);
+            const int bu = __builtin_amdgcn_readfirstlane(b);
+            ragged_rows(((cint_p)r->cu_q)[bu], ((cint_p)r->cu_q)[bu + 1], r->total_q, p.Lq, rq0, Lq);
+            if (qblk * BLKQ >= Lq) break;
+        }
         if constexpr (KVLEN) {             // the sample's key count: wave-uniform index, one scalar load (as the packed route's prefix arrays)
             typedef const __attribute__((address_space(4))) int *cint_p;
             const int len = ((cint_p)p.cu_k)[__builtin_amdgcn_readfirstlane(b)];
@@ -319,18 +333,27 @@
                 if constexpr (WINDOW) {
                     const int w = p.window, s = p.cu_qs != nullptr ? ((cint_p)p.cu_qs)[__builtin_amdgcn_readfirstlane(b)] : 0;
                     wwin = w < 1 ? 1 : (w < (1 << 30) ? w : (1 << 30));
-                    const int sl = s < -p.Lq ? -p.Lq : s;                 // (the lower clamp first: sl - p.Lk cannot overflow)
+                    int sl;
+                    if constexpr (RAGGED) sl = s < -Lq ? -Lq : s;         // (the sample's own row count where the dense kernel has the call's)
+                    else
+                    sl = s < -p.Lq ? -p.Lq : s;                 // (the lower clamp first: sl - p.Lk cannot overflow)
                     qstart = sl - p.Lk > wwin ? p.Lk + wwin : sl;       // (above p.Lk + W no row sees a key either way)
                 } else {
                 const int s = ((cint_p)p.cu_qs)[__builtin_amdgcn_readfirstlane(b)];
+                if constexpr (RAGGED) qstart = s < -Lq ? -Lq : (s < p.Lk ? s : p.Lk);
+                else
                 qstart = s < -p.Lq ? -p.Lq : (s < p.Lk ? s : p.Lk);
                 }
             }
         }
+        if constexpr (RAGGED) q_off = (long)rq0 * p.q_sl + (long)hq * p.q_sh;
+        else
         q_off = (long)b * p.q_sb + (long)hq * p.q_sh;
         if constexpr (PAGED) k_off = (long)hk * p.k_sh;              // (the page's p.k_sb comes per tile: k_tile)
         else
         k_off = (long)b * p.k_sb + (long)hk * p.k_sh;
+        if constexpr (RAGGED) o_off = (long)rq0 * p.o_sl + (long)h * p.o_sh;
+        else
         o_off = (long)b * p.o_sb + (long)h * p.o_sh;
         const int ntk = ((KVLEN ? p.Lk : Lk) + BLKK - 1) / BLKK;      // (images per head of the tensor)
         v_tile0 = ((long)b * p.Hkv + hk) * ntk;
@@ -1075,7 +1098,21 @@
     const float l_tot = pair_sum(l_run);
     const float inv = l_tot > 0.0f ? __builtin_amdgcn_rcpf(l_tot) : 0.0f;
     if (p.lse != nullptr && g == 0 && my_row < Lq_w) {
-        long lidx = (p.cu_q != nullptr) ? ((long)h * p.lse_sh + p.cu_q[b] + my_row)
+        long lidx;
+        if constexpr (RAGGED) {
+            // the packed index, from the clamped first row: the two words are read and clamped again here (a pointer the compiler cannot see
+            // through) instead of a value kept in an SGPR across the key loop
+            typedef const __attribute__((address_space(4))) int *cint_p;
+            typedef const __attribute__((address_space(4))) RaggedArgs *kragged_t;
+            kparams_t k3 = kp;
+            asm volatile("" : "+s"(k3));
+            const kragged_t r = (kragged_t)((const __attribute__((address_space(4))) char *)k3 + kRaggedArgsOffset);
+            const int bu = __builtin_amdgcn_readfirstlane(b);
+            int q0e, lqe;
+            ragged_rows(((cint_p)r->cu_q)[bu], ((cint_p)r->cu_q)[bu + 1], r->total_q, p.Lq, q0e, lqe);
+            lidx = (long)h * p.lse_sh + q0e + my_row;
+        } else
+        lidx = (p.cu_q != nullptr) ? ((long)h * p.lse_sh + p.cu_q[b] + my_row)
                                         : ((long)b * p.Hq + h) * (long)p.Lq + my_row;
         p.lse[lidx] = __builtin_amdgcn_logf(l_tot) + m_run;   // v_log_f32 is log2
     }

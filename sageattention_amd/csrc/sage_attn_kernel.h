@@ -1,7 +1,8 @@
 // sage_attn_kernel.h -- fused INT8-QK^T / online-softmax / FP8-or-FP16-PV attention for gfx950: the kernel family and its launcher.
 // Included by the instantiation units sage_attn_d{128,64}_{f8,f8f,f16}.hip (one per head size, PV format and FP8 score form, so that they
-// compile in parallel); sage_attn.hip holds the host-side dispatch.  The kernel's BODY is the fragment sage_attn_body.h, included by the two
-// entries at the end of this file: sage_attn_kernel<FORM> and its paged twin sage_attn_paged_kernel<FORM>.
+// compile in parallel); sage_attn.hip holds the host-side dispatch.  The kernel's BODY is the fragment sage_attn_body.h, included by the three
+// entries at the end of this file: sage_attn_kernel<FORM>, its paged twin sage_attn_paged_kernel<FORM> and that one's ragged
+// twin sage_attn_paged_varlen_kernel<FORM>.
 //
 // Replaces (behaviourally, not textually) the reference kernels
 //   csrc/qattn/qk_int_sv_f8_cuda_sm89.cuh:46-704   (INT8 QK, FP8 PV, two-level accumulation)
@@ -42,6 +43,7 @@
 #include "sage_attn_parts.h"
 #include "sage_quant_math.h"
 #include "sage_work_order.h"
+#include "sage_ragged.h"
 #include <atomic>
 #include <climits>
 #include <cstdlib>
@@ -213,6 +215,7 @@ __device__ __forceinline__ v16i mfma_i8_first(v4i a, v4i b)
 // gives o = +0, lse = -inf, the weight 0 of the merge.
 // FORM: pack() of the kernel's AttnForm (sage_attn_form.h), which also holds the rules on which flags may meet, on the waves per SIMD the
 // register allocator must allow and on which kernels carry the ticket loop.
+// RAGGED (sage_attn_paged_varlen_kernel below, a PAGED kernel of a causal QSTART form): packed query rows behind a prefix array -- not a form bit either.
 // PAGED (sage_attn_paged_kernel below; a KVLEN kernel without SEED: DESIGN.md 3.18): K, the V image and the K scales are a POOL of pages of
 // 64 << page_shift keys, laid out as the tensors of a call with B = num_pages and Lk = the page size, and logical 64-key tile t of sample b lies
 // in page block_table[b][t >> page_shift] at tile t & (2^page_shift - 1) of it.  Not a form bit: the paged kernel of form F is form F with its
@@ -225,7 +228,9 @@ __global__ void __launch_bounds__(256, min_waves(unpack(FORM)))
 sage_attn_kernel(const AttnParams p_arg)
 {
 #define SAGE_ATTN_BODY_PAGED false
+#define SAGE_ATTN_BODY_RAGGED false
 #include "sage_attn_body.h"
+#undef SAGE_ATTN_BODY_RAGGED
 #undef SAGE_ATTN_BODY_PAGED
 }
 
@@ -238,7 +243,28 @@ sage_attn_paged_kernel(const AttnParams p_arg, const PagedArgs g_arg)
 {
     (void)g_arg;
 #define SAGE_ATTN_BODY_PAGED true
+#define SAGE_ATTN_BODY_RAGGED false
 #include "sage_attn_body.h"
+#undef SAGE_ATTN_BODY_RAGGED
+#undef SAGE_ATTN_BODY_PAGED
+}
+
+// the paged kernel of form FORM (causal with QSTART: the q_start / window forms) over PACKED query rows: q / o [total_q, Hq, D], lse [Hq, total_q],
+// sample b's rows cu_q[b] .. cu_q[b + 1] - 1.  The ragged operands are a third argument behind the two unchanged ones.  A work
+// item is the dense one, (b, h, qblk) over nqblk = ceil(max_seqlen_q / 128) blocks; its prologue reads and clamps the two prefix words
+// (ragged_rows, sage_ragged.h), takes Lq, q_off and o_off from them and leaves when the block lies past the sample's last row -- from there on
+// it runs what the paged kernel runs for a call of that sample's own Lq, and its LSE goes to the packed route's index.  The form's own
+// launch bound holds: the new state is wave-uniform (SGPRs), the eight kernels take 158 - 168 VGPRs at D = 64 and 232 - 238 at D = 128, no scratch.
+template <uint32_t FORM>
+__global__ void __launch_bounds__(256, min_waves(unpack(FORM)))
+sage_attn_paged_varlen_kernel(const AttnParams p_arg, const PagedArgs g_arg, const RaggedArgs r_arg)
+{
+    (void)g_arg;
+    (void)r_arg;
+#define SAGE_ATTN_BODY_PAGED true
+#define SAGE_ATTN_BODY_RAGGED true
+#include "sage_attn_body.h"
+#undef SAGE_ATTN_BODY_RAGGED
 #undef SAGE_ATTN_BODY_PAGED
 }
 

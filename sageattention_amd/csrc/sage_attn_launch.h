@@ -107,4 +107,21 @@ hipError_t launch_attn_paged_units(uint32_t form, const AttnParams &p, const Pag
     return e;
 }
 
+// The ragged paged units sage_attn_d{128,64}_f8pr.hip: the ragged paged kernels (sage_attn_paged_varlen_kernel) of the forms of the named units'
+// lists, as above; the ragged operands follow the paged ones behind the parameter block.
+template <uint32_t... F>
+static bool launch_ragged_among(Forms<F...>, uint32_t want, const AttnParams &p, const PagedArgs &g, const RaggedArgs &r, int nwork, const AttnLaunchOpts &l,
+                                hipError_t &e)
+{
+    return ((want == F && ((e = launch_kernel<sage_attn_paged_varlen_kernel<F>>(TileCfg<unpack(F).D, unpack(F).pv_fp8, 1>::LDS_BYTES, p, nwork, l, false, g, r)), true)) || ...);
+}
+
+template <int D, AttnUnit... U>
+hipError_t launch_attn_ragged_units(uint32_t form, const AttnParams &p, const PagedArgs &g, const RaggedArgs &r, int nwork, const AttnLaunchOpts &l)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)(launch_ragged_among(typename UnitForms<U, D>::type{}, form, p, g, r, nwork, l, e) || ...);
+    return e;
+}
+
 }  // namespace sage

@@ -30,4 +30,11 @@ extern template hipError_t launch_attn_paged_units<64, SAGE_PAGED_UNITS>(uint32_
 extern template hipError_t launch_attn_paged_units<128, SAGE_PAGED_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_paged_units<64, SAGE_PAGED_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, int, const AttnLaunchOpts &);
 
+// the ragged paged kernels (packed query rows) of the forms of units U...: sage_attn_d{128,64}_f8pr.hip holds those of F8Q / F8W
+template <int D, AttnUnit... U>
+hipError_t launch_attn_ragged_units(uint32_t form, const AttnParams &p, const PagedArgs &g, const RaggedArgs &r, int nwork, const AttnLaunchOpts &l);
+#define SAGE_RAGGED_UNITS UNIT_F8Q, UNIT_F8W
+extern template hipError_t launch_attn_ragged_units<128, SAGE_RAGGED_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_ragged_units<64, SAGE_RAGGED_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, int, const AttnLaunchOpts &);
+
 }  // namespace sage

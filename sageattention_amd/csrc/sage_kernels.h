@@ -81,6 +81,16 @@ struct PagedArgs {
 };
 constexpr long kPagedArgsOffset = (long)((sizeof(AttnParams) + alignof(PagedArgs) - 1) / alignof(PagedArgs) * alignof(PagedArgs));      // of the second argument in the kernarg segment
 
+// The operands of a RAGGED paged launch (sage_attn_paged_varlen_kernel): a third kernel argument behind PagedArgs, whose size and
+// offset stay what they are.  q / o are then packed [total_q, Hq, D] (q_sl / o_sl: the row strides, q_sb / o_sb unused), lse is [Hq, total_q]
+// with head stride AttnParams::lse_sh, sample b's rows are cu_q[b] .. cu_q[b + 1] - 1 -- both words clamped by the kernel (ragged_rows,
+// sage_ragged.h) before they form an address -- and AttnParams::Lq is max_seqlen_q: it sizes the grid and bounds the rows a sample gets.
+struct RaggedArgs {
+    const int32_t *cu_q;          // int32 [B + 1] in device memory
+    int total_q;                  // rows of q / o / lse
+};
+constexpr long kRaggedArgsOffset = (long)((kPagedArgsOffset + sizeof(PagedArgs) + alignof(RaggedArgs) - 1) / alignof(RaggedArgs) * alignof(RaggedArgs));
+
 // launch attributes of an attention call that are not kernel parameters (the C ABI's SageLaunchAttr, include/sage_gfx950.h)
 struct AttnLaunchOpts {
     hipStream_t stream;
@@ -119,6 +129,8 @@ struct AttnVariant {
                         // the bits of the launch without it (SAGE_ATTR_GQA_PACK); no operand, AttnParams is what it is without
     const PagedArgs *paged; // non-null (host memory, read by the launcher): a kv_lens launch (no split) whose K / V image / K scales are a pool of pages
                         // reached through a block table -- the paged kernel of the same form, same grid, ordinary dispatch (never the ticket route)
+    const RaggedArgs *ragged; // non-null (host memory, with paged, q_start and causal; no gqa_pack, no split): packed query rows with a prefix array --
+                        // the ragged paged kernel of the same form over the dense grid of B * Hq * ceil(AttnParams::Lq / 128) items
 };
 constexpr int attn_qf(bool per_block, int q_dtype) { return (per_block ? 3 : 1) + (q_dtype == 0 ? 0 : 1); }   // q_dtype: DT_F16 (0) / DT_BF16
 // the one attention launcher: plans the work order, checks that the route exists (hipErrorInvalidValue) and launches the variant's kernel.

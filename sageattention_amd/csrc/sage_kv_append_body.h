@@ -1,5 +1,6 @@
-// sage_kv_append_body.h -- the body of kvcache_append_kernel and kvpaged_append_kernel (sage_kv_cache.hip): a code fragment, included INSIDE the
-// two kernel functions with SAGE_KV_APPEND_PAGED defined as 0 / 1 (shared as text: as a function template it gave the unpaged kernels
+// sage_kv_append_body.h -- the body of kvcache_append_kernel, kvpaged_append_kernel and kvpvarlen_append_kernel (sage_kv_cache.hip,
+// sage_kv_paged.hip, sage_kv_varlen.hip): a code fragment, included INSIDE the three kernel functions with SAGE_KV_APPEND_PAGED defined as
+// 0 / 1 / 1 and, by the third alone, SAGE_KV_APPEND_RAGGED as 1 (shared as text: as a function template it gave the unpaged kernels
 // other code).  Not a header of its own: no include guard, no declarations.
     constexpr int CPR = D / 16;                 // 16-element chunks per row
     constexpr int NCH = BLKK * CPR / 256;       // chunks per thread
@@ -11,7 +12,12 @@
     const int j = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const long bh = (long)b * p.H + h;
     int len0, t;
+#if defined(SAGE_KV_APPEND_RAGGED) && SAGE_KV_APPEND_RAGGED      // (packed new rows, sage_kv_varlen.hip: the sample's rows from the prefix array; the preprocessor, as below)
+    int new0;                                   // the sample's first row of the packed k_new / v_new
+    ragged_append_range(p, r, b, len0, t, new0);
+#else
     append_range(p, b, len0, t);
+#endif
     // the scales of the frozen abs-max (every call: the same bytes; a sample that never gets a row has them too)
     if (j == 0 && tid < D) p.v_scale[bh * D + tid] = fp8_v_scale(p.v_amax[bh * D + tid], p.scale_max);
     const int len1 = len0 + t;                  // <= cap
@@ -29,8 +35,13 @@
 #endif
     const int valid = len1 - row0 < BLKK ? len1 - row0 : BLKK;
     const int old = len0 - row0;                // rows r < old of the block are the tails' (j = 0), the rest k_new's / v_new's
+#if defined(SAGE_KV_APPEND_RAGGED) && SAGE_KV_APPEND_RAGGED
+    const uint16_t *k_new = p.k_new + (long)h * p.k_sh + ((long)new0 + (row0 - len0)) * p.k_sl;              // row r of the block (k_sb / v_sb unused)
+    const uint16_t *v_new = p.v_new + (long)h * p.v_sh + ((long)new0 + (row0 - len0)) * p.v_sl;
+#else
     const uint16_t *k_new = p.k_new + (long)b * p.k_sb + (long)h * p.k_sh + (long)(row0 - len0) * p.k_sl;     // row r of the block
     const uint16_t *v_new = p.v_new + (long)b * p.v_sb + (long)h * p.v_sh + (long)(row0 - len0) * p.v_sl;
+#endif
     const uint16_t *k_tail = p.k_tail + bh * (BLKK * D);
     const uint16_t *v_tail = p.v_tail + bh * (BLKK * D);
 
