@@ -84,7 +84,9 @@ class PagedQuantizedKVCache(_KVCacheBase):
         or a 1-D index tensor on the device; indices of a tensor are the caller's to keep inside ``[0, B)`` and distinct) re-seeds ONLY those
         sequence slots -- the reuse of a slot a pool exists for: ``k_mean`` / ``v_amax`` are then ``[len(slots), Hkv, D]``, the cache must have
         been seeded as a whole before, and ``k_mean`` is None exactly if the cache's is (one attention call reads every slot's mean or
-        none).  Device copies only; the block table and the pool are not touched."""
+        none).  Device copies only; the block table and the pool are not touched, and neither is ``v_scale``: a re-seeded slot keeps its old
+        ``v_scale`` row until the next append call writes every slot's from ``v_amax`` -- the call that gives the slot its first key, so no
+        attention call reads the stale row to any effect (a slot without keys returns ``o = 0``, ``lse = -inf``)."""
         if slots is None:
             return self._seed(k_mean, v_amax)
         idx = self._slot_index(slots)

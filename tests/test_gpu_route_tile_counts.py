@@ -130,6 +130,52 @@ def check_sample(oracle, tag, qb, kb, vb, code, D, smooth_k, keep, ob, lb):
     assert lerr <= 5e-3, (tag, lerr)                                     # (tests/test_gpu_window.py::_check)
 
 
+def ref_sample_quantised(oracle, q_bits, k8, k_scale, v8, v_scale, k_mean, code, D, keep):
+    """``ref_sample`` for keys and values that are QUANTISED ALREADY (tests/test_gpu_kvcache_programs.py: the operands a cache's ledger derives):
+    q_bits uint16 ``[Hq, lq, D]`` is quantised by the oracle as the fused quantiser does (per-thread groups, 32-row warps of a 128-row block);
+    k8 int8 / v8 e4m3 bytes ``[Hkv, n, D]``, k_scale fp32 ``[Hkv, 4 * ceil(n / 64)]``, v_scale fp32 ``[Hkv, D]``; k_mean: the uint16 bits
+    ``[Hkv, D]`` the keys were smoothed with, or None -- the LSE takes ``q . k_mean * sm_scale`` as ``ref_sample`` forms it.  numpy only."""
+    hq, lq = q_bits.shape[:2]
+    hkv, n = k8.shape[:2]
+    if n == 0 or lq == 0:
+        return np.zeros((hq, lq, D), np.float32), np.full((hq, lq), -np.inf, np.float32)
+    gq, nq = oracle.group_index(lq, "per_thread", "q", 128, 32)
+    gk, nk = oracle.group_index(n, "per_thread", "k", 64, 64)
+    assert k_scale.shape == (hkv, nk)
+    q8, qs = oracle.quant_int8(np.ascontiguousarray(q_bits)[None], code, gq, nq, style=oracle.STYLE_TRITON_THREAD)
+    sm_scale = 1.0 / (D ** 0.5)
+    c = np.float32(sm_scale) * np.float32(oracle.LOG2E)                 # (oracle.sageattn_dense, per_thread)
+    o, lse = rw.attn_window(q8[0], k8, v8, qs[0], gq, k_scale, gk, v_scale, keep, c=np.float32(c), out_dtype=F16 if code == 0 else BF16)
+    lse = lse.numpy() / np.float32(oracle.LOG2E)
+    if k_mean is not None:
+        kind = "f16" if code == 0 else "bf16"
+        kmf = np.repeat(oracle.to_f32(np.ascontiguousarray(k_mean), code), hq // hkv, axis=0)
+        corr = oracle.to_f32(oracle.convert(np.einsum("hld,hd->hl", oracle.to_f32(np.ascontiguousarray(q_bits), code), kmf), kind), code)
+        lse = lse + corr * np.float32(sm_scale)
+    return o.float().numpy(), lse
+
+
+def check_sample_quantised(oracle, tag, q_bits, k8, k_scale, v8, v_scale, k_mean, code, D, keep, got, lgot):
+    """``check_sample`` on quantised keys and values, at its bar: ``2e-3 max|ref| + 2 output ulps``, LSE within 5e-3, rows without keys exactly
+    +0 / -inf and the predicate's.  got float32 ``[Hq, lq, D]``, lgot float32 ``[Hq, lq]`` (numpy).  Returns (err / bar, the LSE error)."""
+    hq, lq = q_bits.shape[:2]
+    ref, lse_ref = ref_sample_quantised(oracle, q_bits, k8, k_scale, v8, v_scale, k_mean, code, D, keep)
+    keep = keep if isinstance(keep, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(keep))
+    empty = np.broadcast_to(~keep.any(dim=1).numpy() if keep.shape[1] else np.ones((lq,), bool), (hq, lq))
+    assert np.array_equal(np.isneginf(lse_ref), empty), tag
+    scale = float(np.abs(ref).max()) if ref.size else 0.0
+    bar = 2e-3 * scale + 2 * util.out_ulp(scale, code)                  # (check_sample)
+    err = float(np.abs(got - ref).max()) if ref.size else 0.0
+    lerr = float(np.abs(lgot[~empty] - lse_ref[~empty]).max()) if (~empty).any() else 0.0
+    print(f"{tag}: max|diff| {err:.3e} (bar {bar:.3e}), lse {lerr:.3e}, {int(empty[0].sum()) if hq else 0} empty rows")
+    assert np.isfinite(got).all() and not np.isnan(lgot).any(), tag
+    assert np.array_equal(np.isneginf(lgot), empty), tag                 # the rows without keys are the predicate's
+    assert not got[empty].any() and not np.signbit(got[empty]).any(), tag       # +0, not merely small
+    assert err <= bar, (tag, err, bar)
+    assert lerr <= 5e-3, (tag, lerr)
+    return (err / bar if bar > 0 else 0.0), lerr
+
+
 # ---------------------------------------------------------------------------------------------- a. kv_lens
 @pytest.mark.parametrize("causal", [False, True], ids=["nc", "causal"])
 @pytest.mark.parametrize("D", DS)
