@@ -77,7 +77,8 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
     if (v.bottom_right && (!varlen || !v.causal || !v.pv_fp8 || !per_block || !v.two_level || o.fp8_folded)) return false;
     // packed GQA groups: the kv_lens family (above: fused per-thread Q, FP8 PV, the exact score form, dense, no split), a group to pack and
     // no more query rows than one wave's slab holds
-    if (v.gqa_pack && (!v.kv_lens || p.Lq > 32 || p.group < 2 || p.nqblk != 1)) return false;
+    // (a step launch's decode half: p.Lq = max_seqlen_q sizes nothing there, the band bounds the rows a sample may have)
+    if (v.gqa_pack && (!v.kv_lens || p.group < 2 || (v.band != nullptr ? v.band->hi > 32 : (p.Lq > 32 || p.nqblk != 1)))) return false;
     // a pool of pages behind a block table: the kv_lens family, or its split's pass 2 (seeded with kv_lens, checked above: the chunks folded into
     // p.Hkv, the pool's heads p.Hkv / p.kv_split); whole pages of 64 << page_shift keys, p.Lk the logical capacity
     if (v.paged != nullptr && (!v.kv_lens || (v.seeded ? (p.kv_split < 2 || p.Hkv % p.kv_split != 0) : p.kv_split > 1) ||
@@ -86,8 +87,10 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
                                (long)p.Lk != ((long)v.paged->max_pages << (6 + v.paged->page_shift)) || p.nks != (4 << v.paged->page_shift))) return false;
     // packed query rows on that pool: the paged q_start / window kernels (no packed GQA groups, no split); the prefix array is the third kernel
     // argument, p.cu_q stays null -- the dense grid and the dense branches of the kernel -- and the packed lse needs its head stride
-    if (v.ragged != nullptr && (v.paged == nullptr || !v.q_start || !v.causal || v.gqa_pack || v.seeded || varlen || v.ragged->cu_q == nullptr ||
+    if (v.ragged != nullptr && (v.paged == nullptr || !v.q_start || !v.causal || (v.gqa_pack && v.band == nullptr) || v.seeded || varlen || v.ragged->cu_q == nullptr ||
                                 v.ragged->total_q < 1 || (p.lse != nullptr && p.lse_sh < v.ragged->total_q))) return false;
+    // one launch of the step call: packed query rows behind a band (lo, hi] of row counts, 0 <= lo <= hi; with packed GQA groups hi <= 32 (above)
+    if (v.band != nullptr && (v.ragged == nullptr || v.band->lo < 0 || v.band->hi < v.band->lo)) return false;
     return true;
 }
 
@@ -106,6 +109,9 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     const AttnForm f = attn_form(p, v, o);
     if (v.paged != nullptr) {     // the paged kernel of the same form: same grid, the ordinary dispatch
         p.sched = nullptr;
+        if (v.band != nullptr)        // a launch of the step call: the step kernel of the form, from the packed-group list (decode) or the ragged units' lists (chunks)
+            return f.gpack ? (f.D == 128 ? launch_attn_step_units<128, SAGE_STEP_G_UNITS> : launch_attn_step_units<64, SAGE_STEP_G_UNITS>)(pack(f), p, *v.paged, *v.ragged, *v.band, nwork, o)
+                           : (f.D == 128 ? launch_attn_step_units<128, SAGE_STEP_UNITS> : launch_attn_step_units<64, SAGE_STEP_UNITS>)(pack(f), p, *v.paged, *v.ragged, *v.band, nwork, o);
         if (v.ragged != nullptr)      // packed query rows: the ragged paged kernel of the form (the q_start / window forms, route_exists)
             return (f.D == 128 ? launch_attn_ragged_units<128, SAGE_RAGGED_UNITS> : launch_attn_ragged_units<64, SAGE_RAGGED_UNITS>)(pack(f), p, *v.paged, *v.ragged, nwork, o);
         if (f.seed) return (f.D == 128 ? launch_attn_paged_units<128, SAGE_PAGED_KS_UNITS> : launch_attn_paged_units<64, SAGE_PAGED_KS_UNITS>)(pack(f), p, *v.paged, nwork, o);

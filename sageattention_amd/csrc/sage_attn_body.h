@@ -1,8 +1,10 @@
-// sage_attn_body.h -- the body of sage_attn_kernel<FORM>, of sage_attn_paged_kernel<FORM> and of sage_attn_paged_varlen_kernel<FORM>
-// (sage_attn_kernel.h, which documents the flags): a code fragment, included INSIDE the three kernel functions with SAGE_ATTN_BODY_PAGED defined
-// as false / true / true and SAGE_ATTN_BODY_RAGGED as false / false / true.  Not a header of its own: no include guard, no declarations.
+// sage_attn_body.h -- the body of sage_attn_kernel<FORM>, of sage_attn_paged_kernel<FORM>, of sage_attn_paged_varlen_kernel<FORM> and of
+// sage_attn_paged_step_kernel<FORM> (sage_attn_kernel.h, which documents the flags): a code fragment, included INSIDE the four kernel functions
+// with SAGE_ATTN_BODY_PAGED defined as false / true / true / true, SAGE_ATTN_BODY_RAGGED as false / false / true / true and SAGE_ATTN_BODY_BAND as
+// false / false / false / true.  Not a header of its own: no include guard, no declarations.
     static constexpr bool PAGED = SAGE_ATTN_BODY_PAGED;
     static constexpr bool RAGGED = SAGE_ATTN_BODY_RAGGED;
+    static constexpr bool BAND = SAGE_ATTN_BODY_BAND;
     // The form's fields under the names the body uses.  (static: the body's lambdas capture by reference, and a plain constexpr local that one of
     // them passes on by reference becomes a captured stack slot -- folded away later, but sixteen D = 128 FP16-PV kernels then allocate their
     // registers differently, 217 - 229 VGPRs where these give 219 - 226.)
@@ -25,7 +27,8 @@
     static constexpr bool QSTART = F.qstart;
     static constexpr bool KVLEN = F.kvlen;
     static_assert(!PAGED || (KVLEN && PV_FP8), "paged tiles: the kv_lens family, its split (SEED with KVLEN) included");
-    static_assert(!RAGGED || (PAGED && CAUSAL && QSTART && !SEED && !GPACK), "packed query rows: the paged q_start / window kernels");
+    static_assert(!RAGGED || (PAGED && CAUSAL && QSTART && !SEED && (BAND || !GPACK)), "packed query rows: the paged q_start / window kernels (a step launch: their packed-group forms too)");
+    static_assert(!BAND || RAGGED, "the band filter: a ragged launch of the step call");
     // The parameter block is read through the kernarg segment pointer, and inside the persistent loop through a copy of that pointer the
     // compiler cannot see through (an empty asm): otherwise every scalar load of a parameter is hoisted out of the loop and stays live in
     // SGPRs across it (128 SGPRs and 16-400 VGPRs spilled in every instantiation).  AttnParams is the kernel's only explicit argument.
@@ -322,6 +325,13 @@
             typedef const __attribute__((address_space(4))) RaggedArgs *kragged_t;
             const kragged_t r = (kragged_t)((const __attribute__((address_space(4))) char *)kp + kRaggedArgsOffset);
             const int bu = __builtin_amdgcn_readfirstlane(b);
+            if constexpr (BAND) {
+                // (a step launch: the sample's rows only if their count lies in the launch's band -- two more words behind the ragged ones, scalar
+                //  loads; a sample outside the band has Lq = 0 here and its items leave with the blocks past a sample's last row, just below)
+                typedef const __attribute__((address_space(4))) BandArgs *kband_t;
+                const kband_t bd = (kband_t)((const __attribute__((address_space(4))) char *)kp + kBandArgsOffset);
+                ragged_band(((cint_p)r->cu_q)[bu], ((cint_p)r->cu_q)[bu + 1], r->total_q, p.Lq, bd->lo, bd->hi, rq0, Lq);
+            } else
             ragged_rows(((cint_p)r->cu_q)[bu], ((cint_p)r->cu_q)[bu + 1], r->total_q, p.Lq, rq0, Lq);
             if (qblk * BLKQ >= Lq) break;
         }

@@ -1,8 +1,8 @@
 // sage_attn_kernel.h -- fused INT8-QK^T / online-softmax / FP8-or-FP16-PV attention for gfx950: the kernel family and its launcher.
 // Included by the instantiation units sage_attn_d{128,64}_{f8,f8f,f16}.hip (one per head size, PV format and FP8 score form, so that they
-// compile in parallel); sage_attn.hip holds the host-side dispatch.  The kernel's BODY is the fragment sage_attn_body.h, included by the three
-// entries at the end of this file: sage_attn_kernel<FORM>, its paged twin sage_attn_paged_kernel<FORM> and that one's ragged
-// twin sage_attn_paged_varlen_kernel<FORM>.
+// compile in parallel); sage_attn.hip holds the host-side dispatch.  The kernel's BODY is the fragment sage_attn_body.h, included by the four
+// entries at the end of this file: sage_attn_kernel<FORM>, its paged twin sage_attn_paged_kernel<FORM>, that one's ragged
+// twin sage_attn_paged_varlen_kernel<FORM> and the ragged twin behind a band filter, sage_attn_paged_step_kernel<FORM> (3.22).
 //
 // Replaces (behaviourally, not textually) the reference kernels
 //   csrc/qattn/qk_int_sv_f8_cuda_sm89.cuh:46-704   (INT8 QK, FP8 PV, two-level accumulation)
@@ -229,7 +229,9 @@ sage_attn_kernel(const AttnParams p_arg)
 {
 #define SAGE_ATTN_BODY_PAGED false
 #define SAGE_ATTN_BODY_RAGGED false
+#define SAGE_ATTN_BODY_BAND false
 #include "sage_attn_body.h"
+#undef SAGE_ATTN_BODY_BAND
 #undef SAGE_ATTN_BODY_RAGGED
 #undef SAGE_ATTN_BODY_PAGED
 }
@@ -244,7 +246,9 @@ sage_attn_paged_kernel(const AttnParams p_arg, const PagedArgs g_arg)
     (void)g_arg;
 #define SAGE_ATTN_BODY_PAGED true
 #define SAGE_ATTN_BODY_RAGGED false
+#define SAGE_ATTN_BODY_BAND false
 #include "sage_attn_body.h"
+#undef SAGE_ATTN_BODY_BAND
 #undef SAGE_ATTN_BODY_RAGGED
 #undef SAGE_ATTN_BODY_PAGED
 }
@@ -263,7 +267,31 @@ sage_attn_paged_varlen_kernel(const AttnParams p_arg, const PagedArgs g_arg, con
     (void)r_arg;
 #define SAGE_ATTN_BODY_PAGED true
 #define SAGE_ATTN_BODY_RAGGED true
+#define SAGE_ATTN_BODY_BAND false
 #include "sage_attn_body.h"
+#undef SAGE_ATTN_BODY_BAND
+#undef SAGE_ATTN_BODY_RAGGED
+#undef SAGE_ATTN_BODY_PAGED
+}
+
+// the ragged paged kernel of form FORM behind a BAND filter: one launch of the step call (include/sage_kvstep_gfx950.h).  The band's
+// two words are a fourth argument behind the three unchanged ones; a work item whose sample's clamped row count lies outside (lo, hi] leaves where
+// a query block past the sample's last row leaves (ragged_band, sage_ragged.h), every other item runs what sage_attn_paged_varlen_kernel<FORM>
+// runs.  Instantiated for the forms of the ragged units -- the chunk launch, band (32, max_seqlen_q], the ragged launch's grid and work order --
+// and for the QSTART forms of the packed-group list -- the decode launch, band (0, 32]: GPACK's own work item (b, kv head, block of four query
+// heads), each wave taking the sample's <= 32 packed rows of its own head, so a decode sequence streams its K / V once per four heads.
+template <uint32_t FORM>
+__global__ void __launch_bounds__(256, min_waves(unpack(FORM)))
+sage_attn_paged_step_kernel(const AttnParams p_arg, const PagedArgs g_arg, const RaggedArgs r_arg, const BandArgs b_arg)
+{
+    (void)g_arg;
+    (void)r_arg;
+    (void)b_arg;
+#define SAGE_ATTN_BODY_PAGED true
+#define SAGE_ATTN_BODY_RAGGED true
+#define SAGE_ATTN_BODY_BAND true
+#include "sage_attn_body.h"
+#undef SAGE_ATTN_BODY_BAND
 #undef SAGE_ATTN_BODY_RAGGED
 #undef SAGE_ATTN_BODY_PAGED
 }

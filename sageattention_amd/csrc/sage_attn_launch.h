@@ -124,4 +124,31 @@ hipError_t launch_attn_ragged_units(uint32_t form, const AttnParams &p, const Pa
     return e;
 }
 
+// The step units sage_attn_d{128,64}_{f8pb,f8pbg}.hip: the step kernels (sage_attn_paged_step_kernel, the ragged paged kernels behind a band
+// filter) of the QSTART forms of the named units' lists, as above; the band follows the ragged operands.  The filter stands here, where the list
+// is walked: the packed-group list also holds four forms without offsets, which have no ragged meaning and get no kernel (nor a launch).
+template <uint32_t F>
+static hipError_t launch_step_form(const AttnParams &p, const PagedArgs &g, const RaggedArgs &r, const BandArgs &b, int nwork, const AttnLaunchOpts &l)
+{
+    if constexpr (unpack(F).qstart)
+        return launch_kernel<sage_attn_paged_step_kernel<F>>(TileCfg<unpack(F).D, unpack(F).pv_fp8, 1>::LDS_BYTES, p, nwork, l, false, g, r, b);
+    else
+        return hipErrorInvalidValue;
+}
+
+template <uint32_t... F>
+static bool launch_step_among(Forms<F...>, uint32_t want, const AttnParams &p, const PagedArgs &g, const RaggedArgs &r, const BandArgs &b, int nwork,
+                              const AttnLaunchOpts &l, hipError_t &e)
+{
+    return ((want == F && ((e = launch_step_form<F>(p, g, r, b, nwork, l)), true)) || ...);
+}
+
+template <int D, AttnUnit... U>
+hipError_t launch_attn_step_units(uint32_t form, const AttnParams &p, const PagedArgs &g, const RaggedArgs &r, const BandArgs &b, int nwork, const AttnLaunchOpts &l)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)(launch_step_among(typename UnitForms<U, D>::type{}, form, p, g, r, b, nwork, l, e) || ...);
+    return e;
+}
+
 }  // namespace sage

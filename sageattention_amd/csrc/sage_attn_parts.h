@@ -37,4 +37,15 @@ hipError_t launch_attn_ragged_units(uint32_t form, const AttnParams &p, const Pa
 extern template hipError_t launch_attn_ragged_units<128, SAGE_RAGGED_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_ragged_units<64, SAGE_RAGGED_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, int, const AttnLaunchOpts &);
 
+// the step kernels (the ragged paged kernels behind a band filter) of the QSTART forms of units U...: sage_attn_d{128,64}_f8pb.hip
+// holds those of F8Q / F8W (the step call's chunk launch), sage_attn_d{128,64}_f8pbg.hip those of F8G (its decode launch)
+template <int D, AttnUnit... U>
+hipError_t launch_attn_step_units(uint32_t form, const AttnParams &p, const PagedArgs &g, const RaggedArgs &r, const BandArgs &b, int nwork, const AttnLaunchOpts &l);
+#define SAGE_STEP_UNITS UNIT_F8Q, UNIT_F8W
+#define SAGE_STEP_G_UNITS UNIT_F8G
+extern template hipError_t launch_attn_step_units<128, SAGE_STEP_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_step_units<64, SAGE_STEP_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_step_units<128, SAGE_STEP_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_step_units<64, SAGE_STEP_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+
 }  // namespace sage

@@ -4,6 +4,7 @@
 #include "../../include/sage_kvpaged_gfx950.h"
 #include "../../include/sage_kvpsplit_gfx950.h"
 #include "../../include/sage_kvpvarlen_gfx950.h"
+#include "../../include/sage_kvstep_gfx950.h"
 #include "sage_common.h"
 #include "sage_kernels.h"
 #include "sage_work_order.h"
@@ -131,6 +132,7 @@ struct AttnCall {
     const sage::PagedArgs *paged;    // sage_kvpaged_attn: k / v / k_scale are a pool of pages behind a block table (with kv_lens; Lk = the logical capacity)
     const sage::RaggedArgs *ragged;  // sage_kvpvarlen_attn (with paged): q / o packed [total_q, Hq, D] behind cu_seqlens_q, lse [Hq, total_q]; Lq = max_seqlen_q, qs.sb = os.sb = 0
     bool paged_split;                // sage_kvpsplit_attn (with paged): the exact split on that pool -- SAGE_ATTR_KV_SPLIT is required instead of refused
+    bool step;                       // sage_kvstep_attn (with ragged): two launches behind band filters, the decode rows packed by GQA group
     int is_causal, gran, q_warp, pv_accum, q_dtype, out_dtype;
     float sm_scale_log2, q_premul;
     void *stream; const SageLaunchAttr *attr;
@@ -276,17 +278,19 @@ int attn_run(const AttnCall &c)
                                              c.D > 0 ? c.D : 0, S)) return rc;
     } else
     if (c.paged != nullptr && c.attr != nullptr && c.attr->struct_bytes >= 8) {
-        const char *const e = c.ragged != nullptr ? "sage_kvpvarlen_attn" : "sage_kvpaged_attn";
+        const char *const e = c.step ? "sage_kvstep_attn" : c.ragged != nullptr ? "sage_kvpvarlen_attn" : "sage_kvpaged_attn";
         const unsigned f = c.attr->flags;
         SAGE_REQUIRE(!(f & (SAGE_ATTR_KV_SPLIT | (0xffu << SAGE_ATTR_KV_SPLIT_SHIFT))),
                      "%s: SAGE_ATTR_KV_SPLIT is not supported on a paged cache (pass 1 and the split's kernels do not look pages up)", e);
         SAGE_REQUIRE(!(f & SAGE_ATTR_FP8_FOLDED_SCORES), "%s: SAGE_ATTR_FP8_FOLDED_SCORES is not supported on a paged cache (the exact score form only)", e);
         SAGE_REQUIRE(!(f & SAGE_ATTR_FORCE_PERSISTENT), "%s: SAGE_ATTR_FORCE_PERSISTENT is not supported on a paged cache (the ordinary dispatch only)", e);
-        SAGE_REQUIRE(c.ragged == nullptr || !(f & SAGE_ATTR_GQA_PACK), "%s: SAGE_ATTR_GQA_PACK is not supported on packed query rows (one workgroup per query head)", e);
+        SAGE_REQUIRE(c.ragged == nullptr || c.step || !(f & SAGE_ATTR_GQA_PACK), "%s: SAGE_ATTR_GQA_PACK is not supported on packed query rows (one workgroup per query head)", e);
+        SAGE_REQUIRE(!c.step || !(f & SAGE_ATTR_GQA_PACK), "%s: SAGE_ATTR_GQA_PACK is not taken (the entry packs the decode rows of a GQA group on its own)", e);
     }
     if (const int rc = read_attr(c.attr, c.stream, c.mask == nullptr && !split && c.paged == nullptr, la)) return rc;     // (masked, split and paged launches take no launch workspace)
     // (packed query rows: the offsets place every sample's rows, so they are required -- the bottom-right ones are the caller's kv_lens[b] - Lq_b)
-    SAGE_REQUIRE(c.ragged == nullptr || la.q_start != nullptr, "sage_kvpvarlen_attn: SageLaunchAttr.q_start is required (int32 [B]: the key position of each sample's row 0)");
+    SAGE_REQUIRE(c.ragged == nullptr || la.q_start != nullptr, "%s: SageLaunchAttr.q_start is required (int32 [B]: the key position of each sample's row 0)",
+                 c.step ? "sage_kvstep_attn" : "sage_kvpvarlen_attn");
     // ---- the routes a Q form admits
     if (c.kv_lens == nullptr) SAGE_REFUSE_KV_SPLIT(la);
     SAGE_REQUIRE(la.kv_split_flag || la.kv_split == 0, "SAGE_ATTR_KV_SPLIT: a chunk count (%d in flags bits 16-23) without the bit", la.kv_split);
@@ -373,6 +377,24 @@ int attn_run(const AttnCall &c)
     v.two_level = fp8 ? c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : c.pv_accum == SAGE_PV_ACCUM_TRITON;
     v.qf = int8q ? 0 : sage::attn_qf(per_block, c.q_dtype);
     if (la.kv_split_flag) return kv_split_run(c, la, p, v);
+    if (c.step) {
+        // the step call: the decode launch -- the samples of 1 .. 32 rows, GPACK's work item -- always, then the chunk launch -- the samples of more
+        // rows, the ragged launch's grid -- only if max_seqlen_q admits such a sample (host-known: a pure decode step is one launch).  Both on the
+        // call's stream, no host read in between; p.Lq = max_seqlen_q in both, the row bound ragged_band clamps to
+        int grid_d = 0, grid_c = 0;
+        sage::AttnLaunchOpts o = la.opts;
+        if (la.opts.grid_out != nullptr) *la.opts.grid_out = 0;
+        const sage::BandArgs decode{0, 32}, chunk{32, c.Lq};
+        sage::AttnVariant vs = v;
+        vs.gqa_pack = true; vs.band = &decode; o.grid_out = &grid_d;
+        if (const int rc = check_launch(sage::launch_attention(p, vs, o), "sage_kvstep_attn decode launch")) return rc;
+        if (c.Lq > 32) {
+            vs.gqa_pack = false; vs.band = &chunk; o.grid_out = &grid_c;
+            if (const int rc = check_launch(sage::launch_attention(p, vs, o), "sage_kvstep_attn chunk launch")) return rc;
+        }
+        if (la.opts.grid_out != nullptr) *la.opts.grid_out = grid_d + grid_c;
+        return SAGE_OK;
+    }
     return check_launch(sage::launch_attention(p, v, la.opts), int8q ? "sage_attn launch" : per_block ? "sage_attn_fused_qblock launch" :
                         c.ragged != nullptr ? "sage_kvpvarlen_attn launch" : c.paged != nullptr ? "sage_kvpaged_attn launch" : c.kv_lens != nullptr ? "sage_attn_fused_q_pv_f8_kvlens launch" : "sage_attn_fused_q launch");
 }
@@ -1127,6 +1149,44 @@ SAGE_KVPVARLEN_API int sage_kvpvarlen_attn(const void *q, const int8_t *k_int8, 
     AttnCall c{};
     c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
     c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g; c.ragged = &r;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.Lk = max_pages_per_seq * page_size; c.D = D;
+    c.qs = {0, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {0, o_sh, o_sl}; c.lse_sh = lse_sh;
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
+}
+
+// sage_kvpvarlen_attn as one call per engine step (include/sage_kvstep_gfx950.h): the same operands, the decode rows of a GQA
+// group packed four heads to a workgroup, the longer samples on the 128-row kernel -- sorted on the device by a band filter, two launches
+SAGE_KVSTEP_API int sage_kvstep_abi_version(void) { return SAGE_KVSTEP_ABI_VERSION; }
+
+SAGE_KVSTEP_API int sage_kvstep_attn(const void *q, const int8_t *k_int8, const void *v_image, void *o, float *lse,
+                                     const float *k_scale, const float *v_scale, const int32_t *kv_lens, const int32_t *cu_seqlens_q,
+                                     const int32_t *block_table, int64_t bt_stride, int num_pages, int page_size, int max_pages_per_seq,
+                                     int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                                     int64_t q_sl, int64_t q_sh, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                     int64_t o_sl, int64_t o_sh, int64_t lse_sh,
+                                     int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr)
+{
+    const char *const e = "sage_kvstep_attn";
+    SAGE_REQUIRE(q && k_int8 && v_image && o && k_scale && v_scale, "%s: null tensor pointer (only lse may be null)", e);
+    SAGE_REQUIRE(kv_lens, "%s: null kv_lens", e);
+    SAGE_REQUIRE(cu_seqlens_q, "%s: null cu_seqlens_q", e);
+    sage::PagedArgs g;
+    if (const int rc = sage::paged_args(e, block_table, bt_stride, num_pages, page_size, max_pages_per_seq, g)) return rc;
+    if (const int rc = sage::kv_check_batch(e, B, Hkv)) return rc;
+    if (const int rc = sage::paged_check_table_aligned(e, block_table)) return rc;
+    SAGE_REQUIRE((reinterpret_cast<uintptr_t>(cu_seqlens_q) & 3u) == 0, "%s: cu_seqlens_q must be 4-byte aligned", e);
+    SAGE_REQUIRE(total_q >= 1 && max_seqlen_q >= 1, "%s: total_q and max_seqlen_q must be at least 1 (got %d, %d)", e, total_q, max_seqlen_q);
+    SAGE_REQUIRE(is_causal == 1, "%s: is_causal must be 1 (packed query rows are placed by their offsets; got %d)", e, is_causal);
+    SAGE_REQUIRE(Hq >= 1 && (int64_t)B * Hq * ((max_seqlen_q + 127) / 128) < ((int64_t)1 << 31), "%s: B * Hq * ceil(max_seqlen_q / 128) must be in [1, 2^31) (got %d, %d, %d)",
+                 e, B, Hq, max_seqlen_q);
+    SAGE_REQUIRE(lse == nullptr || lse_sh >= total_q, "%s: lse is [Hq, total_q]: its head stride lse_sh must be at least total_q (got %lld)", e, (long long)lse_sh);
+    SAGE_REQUIRE(Hq / Hkv >= 2, "%s: Hq / Hkv must be at least 2, no GQA group to pack (got Hq %d, Hkv %d; sage_kvpvarlen_attn takes such a call)", e, Hq, Hkv);
+    const sage::RaggedArgs r{cu_seqlens_q, total_q};
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
+    c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g; c.ragged = &r;
+    c.step = true;
     c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.Lk = max_pages_per_seq * page_size; c.D = D;
     c.qs = {0, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {0, o_sh, o_sl}; c.lse_sh = lse_sh;
     c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;

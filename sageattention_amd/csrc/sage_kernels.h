@@ -91,6 +91,14 @@ struct RaggedArgs {
 };
 constexpr long kRaggedArgsOffset = (long)((kPagedArgsOffset + sizeof(PagedArgs) + alignof(RaggedArgs) - 1) / alignof(RaggedArgs) * alignof(RaggedArgs));
 
+// The band of a STEP launch (sage_attn_paged_step_kernel): a fourth kernel argument behind RaggedArgs, whose size and offset stay
+// what they are.  A work item whose sample has `rows` query rows (ragged_rows' clamped count) runs iff lo < rows <= hi and leaves otherwise
+// (ragged_band, sage_ragged.h): the step call's decode launch carries (0, 32], its chunk launch (32, max_seqlen_q].
+struct BandArgs {
+    int lo, hi;
+};
+constexpr long kBandArgsOffset = (long)((kRaggedArgsOffset + sizeof(RaggedArgs) + alignof(BandArgs) - 1) / alignof(BandArgs) * alignof(BandArgs));
+
 // launch attributes of an attention call that are not kernel parameters (the C ABI's SageLaunchAttr, include/sage_gfx950.h)
 struct AttnLaunchOpts {
     hipStream_t stream;
@@ -131,6 +139,9 @@ struct AttnVariant {
                         // reached through a block table -- the paged kernel of the same form, same grid, ordinary dispatch (never the ticket route)
     const RaggedArgs *ragged; // non-null (host memory, with paged, q_start and causal; no gqa_pack, no split): packed query rows with a prefix array --
                         // the ragged paged kernel of the same form over the dense grid of B * Hq * ceil(AttnParams::Lq / 128) items
+    const BandArgs *band;   // non-null (host memory, with ragged): one launch of the step call -- the step kernel of the same form, which runs the
+                        // samples inside the band alone.  With gqa_pack it is the decode launch: B * Hkv * ceil(group / 4) items whatever
+                        // AttnParams::Lq = max_seqlen_q is (the band's hi <= 32 bounds the rows instead)
 };
 constexpr int attn_qf(bool per_block, int q_dtype) { return (per_block ? 3 : 1) + (q_dtype == 0 ? 0 : 1); }   // q_dtype: DT_F16 (0) / DT_BF16
 // the one attention launcher: plans the work order, checks that the route exists (hipErrorInvalidValue) and launches the variant's kernel.

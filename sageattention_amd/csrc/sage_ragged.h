@@ -1,6 +1,7 @@
 // sage_ragged.h -- the row range of one sample of a PACKED operand, from two words of a caller-written prefix array: the one clamp the ragged
 // attention kernel (sage_attn_paged_varlen_kernel) and the ragged append (sage_kv_varlen.hip) put between those words and every address.
-// Plain C++ with no include of its own, so that a host program can exercise it (tests/ragged_clamp_main.cpp).
+// Plain C++ with no include of its own, so that a host program can exercise it (tests/ragged_clamp_main.cpp) -- and the band
+// filter the step call's two launches sort the samples with (tests/ragged_band_main.cpp).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -25,6 +26,16 @@ SAGE_RAGGED_HD inline void ragged_rows(int c0, int c1, int total, int max_rows, 
     const int n = q1 - q0;                               // in [0, t]
     first = q0;
     rows = n < m ? n : m;
+}
+
+// ragged_rows behind a band filter (the step call's two launches): the sample's (first, rows) when lo < rows <= hi, rows = 0
+// otherwise -- `first` is ragged_rows' either way.  The filter compares the CLAMPED count (an int in [0, max(max_rows, 0)]) with two ints and
+// forms nothing: the bands (0, 32] and (32, max_rows] of one launch pair split the samples that have rows between them, whatever the words hold.
+SAGE_RAGGED_HD inline void ragged_band(int c0, int c1, int total, int max_rows, int lo, int hi, int &first, int &rows)
+{
+    int n;
+    ragged_rows(c0, c1, total, max_rows, first, n);
+    rows = (lo < n && n <= hi) ? n : 0;
 }
 
 }  // namespace sage
