@@ -20,7 +20,10 @@
  * All strides are in ELEMENTS.  Pointers are device pointers unless stated otherwise and must
  * be 16-byte aligned; row strides must be multiples of 16 elements (the innermost/head_dim
  * stride is 1, as the reference asserts, core.py:274).  head_dim is 64 or 128 (the Python layer
- * pads other sizes exactly as core.py:260-271 does).
+ * pads other sizes exactly as core.py:260-271 does).  The row stride k_sl of the INT8 k that a
+ * sage_attn_* entry reads is non-negative and keeps one 64-key tile below 2 GiB,
+ * 63 * k_sl + head_dim - 16 < 2^31: the kernels address the rows of a tile with 32-bit offsets
+ * (batch, head and tile offsets are 64-bit).
  */
 #ifndef SAGE_GFX950_H
 #define SAGE_GFX950_H

@@ -30,7 +30,7 @@ int sage::set_last_error(int code, const char *fmt, ...)
 
 namespace {
 
-using sage::aligned16, sage::aligned16_strides, sage::multiples_of;      // (sage_host_checks.h, with SAGE_REQUIRE)
+using sage::aligned16, sage::aligned16_strides, sage::multiples_of, sage::k_tile_fits_int;    // (sage_host_checks.h, with SAGE_REQUIRE)
 
 int check_launch(hipError_t e, const char *what)
 {
@@ -342,6 +342,8 @@ int attn_run(const AttnCall &c)
     // q strides: 16 bytes of INT8, or 8 elements of fp16 / bf16
     SAGE_REQUIRE(multiples_of(int8q ? 16 : 8, c.qs), int8q ? "int8 q/k strides must be multiples of 16" : "q strides must be multiples of 8 elements");
     SAGE_REQUIRE(multiples_of(16, c.ks), int8q ? "int8 q/k strides must be multiples of 16" : "int8 k strides must be multiples of 16");
+    SAGE_REQUIRE(k_tile_fits_int(c.ks.sl, c.D), "one 64-key tile of k must span less than 2 GiB (row stride %lld): the kernel addresses a tile's rows with 32-bit offsets",
+                 (long long)c.ks.sl);
     SAGE_REQUIRE(multiples_of(8, c.os), "output strides must be multiples of 8 elements");
     SAGE_REQUIRE(c.pv_accum >= SAGE_PV_ACCUM_SINGLE && c.pv_accum <= SAGE_PV_ACCUM_TRITON && (!fp8 || c.pv_accum != SAGE_PV_ACCUM_TRITON),
                  "bad pv_accum %d", c.pv_accum);
@@ -1382,6 +1384,8 @@ static int split_exact_check(const void *q, const int8_t *k, const float *k_scal
     SAGE_REQUIRE(aligned16(q) && aligned16(k), "q/k must be 16-byte aligned");
     SAGE_REQUIRE(multiples_of(8, q_sl, q_sh, q_sb), "q strides must be multiples of 8 elements");
     SAGE_REQUIRE(multiples_of(16, k_sl, k_sh, k_sb), "int8 k strides must be multiples of 16");
+    SAGE_REQUIRE(k_tile_fits_int(k_sl, D), "one 64-key tile of k must span less than 2 GiB (row stride %lld): the kernel addresses a tile's rows with 32-bit offsets",
+                 (long long)k_sl);
     return SAGE_OK;
 }
 

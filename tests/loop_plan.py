@@ -4,7 +4,7 @@
 tiles (WINDOW: general iterations that cut some row on the left), the six-body pipelined loop (``csrc/sage_attn_loop_f8.h``: ``trips`` times six
 bodies, then ``remainder`` single bodies renamed behind them), the last-tile bodies (``diag_ok`` causal, ``tail_ok`` non-causal) and general
 iterations.  This module restates that arithmetic in plain Python -- C's truncating division included -- so that the GPU sweeps
-(tests/test_gpu_route_tile_counts.py, tests/test_gpu_split_tile_counts.py) can CHOOSE lengths, offsets and windows by the loop forms they reach and ASSERT what the selection
+(tests/test_gpu_route_tile_counts.py, tests/test_gpu_split_tile_counts.py, tests/test_gpu_paged_tile_counts.py) can CHOOSE lengths, offsets and windows by the loop forms they reach and ASSERT what the selection
 covers.  It is not a reference for values, and it imports nothing from ``sageattention_amd``.  tests/test_loop_plan_host.py pins it on the
 CPU against tile ranges recomputed from the definition of visibility (``ref_window.visible``).
 
@@ -455,3 +455,115 @@ def random_split_call(seed: int) -> dict:
     c["S"] = max(2, {"tiles": tiles, "tiles+3": tiles + 3}.get(kind) or int(kind))
     c["pack_gqa"] = bool(Lq <= 32 and c["group"] >= 2 and rng.random() < 0.7)
     return c
+
+
+# ================================================================================================ the paged units (tests/test_gpu_paged_tile_counts.py)
+# The six paged compilation units -- f8p (the kv_lens / q_start / window forms behind a block table), f8pg (pack_gqa), f8pks (pass 2 of the
+# split), f8pr (packed query rows), f8pb / f8pbg (the step call's chunk and decode launches) -- each compile the six-body loop on their own.  A
+# paged launch is a KVLEN-family launch whose padded length is the LOGICAL capacity, so ``dense`` / ``split_chunk`` model it as they stand; a
+# sequence of the ragged and step calls is the causal item of its own row count.
+#
+# ONE cache serves every unsplit route: sample b holds PAGED_SAMPLES[b][0] keys, and every causal call places its row 0 at PAGED_SAMPLES[b][1]
+# (the lengths of sweep (a) bottom-right at Lq 200, then sweep (b)'s pairs).  A route is a list of calls on that cache; a windowed call has one
+# W for all samples, so the windows are chosen greedily by what ALL samples reach under them.
+PAGED_PAGE_SIZES = (64, 256)              # a page boundary behind every tile, and behind every fourth
+PAGED_HKV, PAGED_GROUPS = 2, (1, 4, 5)
+PAGED_RUNS = tuple(range(18))             # 24 tiles: the pipelined run reaches 17 behind a 128-row block's diagonal
+PAGED_SAMPLES = tuple((n, n - LQ) for n in KV_LENS) + Q_START_ALIGNED + Q_START_PAIRS
+PAGED_RAGGED_LQS = (1, 32, 33, 128, 130)  # the decode band and its edge, the chunk band's first count, a whole block, two blocks
+PAGED_ROTATIONS = len(PAGED_RAGGED_LQS)   # call c of the ragged / step sweep gives sample b PAGED_RAGGED_LQS[(b + c) % 5] rows
+
+
+def paged_plans(lq: int, causal: bool, W: int = 0):
+    """{(sample, query block): Plan} of one dense call on the shared cache (f8p; with lq <= 32 also f8pg)."""
+    return {(b, j): dense(128, causal, lq, LKP, n, s if causal else None, W, j) for b, (n, s) in enumerate(PAGED_SAMPLES) for j in range(nblk(lq))}
+
+
+def _paged_window_keys(W):
+    keys = set()
+    for (b, j), p in paged_plans(LQ, True, W).items():
+        if p.n_iters:
+            keys.add(("form", p.nh, p.run))
+    for lq in PACK_LQS:
+        for p in paged_plans(lq, True, W).values():
+            if p.n_iters and p.nh > 0:
+                keys.add(("pack", lq, p.run))
+    return keys
+
+
+PAGED_WINDOW_WANTED = {("form", nh, r) for nh in range(4) for r in RUNS} | {("pack", lq, r) for lq in PACK_LQS for r in RUNS}
+
+
+@functools.lru_cache(maxsize=None)
+def paged_windows():
+    """The W of the windowed calls: each is one call per route on every sample."""
+    return _greedy([64 * m + d for m in range(0, 24) for d in (0, 1, 37, 63) if 64 * m + d >= 1], _paged_window_keys, PAGED_WINDOW_WANTED)
+
+
+def paged_ragged_counts(rotation: int):
+    return tuple(PAGED_RAGGED_LQS[(b + rotation) % PAGED_ROTATIONS] for b in range(len(PAGED_SAMPLES)))
+
+
+def paged_ragged_plans(rotation: int, W: int = 0, bottom_right: bool = False):
+    """{(sample, query block): (band, Plan)} of one ragged / step call: ``band`` names the launch and the block -- "decode" (1 .. 32 rows: the step
+    call's packed-group launch), "chunk" (one block of 33 .. 128 rows), "two0" / "two1" (the blocks of a 130-row sequence).  The offsets are the
+    samples' own (clamped to -Lq_b, which moves no row that sees a key), or with ``bottom_right`` len_b - Lq_b."""
+    out = {}
+    for b, ((n, s), lq) in enumerate(zip(PAGED_SAMPLES, paged_ragged_counts(rotation))):
+        s = n - lq if bottom_right else max(s, -lq)
+        for j in range(nblk(lq)):
+            band = "decode" if lq <= 32 else "chunk" if lq <= BLKQ else f"two{j}"
+            out[(b, j)] = (band, dense(128, True, lq, LKP, n, s, W, j))
+    return out
+
+
+PAGED_BANDS = ("decode", "chunk", "two0", "two1")
+
+# ---- f8pks: a cache of its own, capacity 2560 as sweep (f), so that a chunk of S = 2 holds 20 tiles.  S 3: T = 14 -- with pages of 256 keys chunk
+# 1 starts at tile 2 of page 3 and chunk 2 reaches past the table; S 5: T = 8.  The samples: sweep (f)'s non-causal lengths (bottom-right at the
+# widest block for the causal calls) and its causal pairs.
+PAGED_SPLITS = (2, 3, 5)
+PAGED_SPLIT_LQS = (1, 16, 128)            # packed at 1 and 16 (the groups of 4 and 5), unpacked at 16 and 128
+
+
+@functools.lru_cache(maxsize=None)
+def paged_split_samples():
+    return tuple((n, n - BLKQ) for n in SPLIT_LENS) + split_causal_pairs()
+
+
+def paged_split_plans(causal: bool, lq: int, S: int):
+    return {(b, c): split_chunk(causal, lq, LKP_SPLIT, n, s if causal else None, S, c) for b, (n, s) in enumerate(paged_split_samples()) for c in range(S)}
+
+
+def paged_anchor(plans, key=lambda kk: kk[1] == 0):
+    """(sample, Plan) of the first work item of ``plans`` -- {(sample, block or chunk): Plan or (band, Plan)}, those ``key`` admits -- that runs at
+    least two trips of the six-body loop and a remainder: the sample a sweep holds to the attention reference."""
+    for kk, p in plans.items():
+        p = p if isinstance(p, Plan) else p[1]
+        if key(kk) and p.n_iters and p.trips >= 2 and p.remainder > 0:
+            return kk[0], p
+    raise AssertionError("no work item with two trips and a remainder")
+
+
+@functools.lru_cache(maxsize=None)
+def paged_ragged_anchor(band: str):
+    """(rotation, sample, Plan): the first call of the ragged / step sweep, without a window, that has such a work item in ``band``."""
+    for r in range(PAGED_ROTATIONS):
+        plans = paged_ragged_plans(r)
+        try:
+            return (r,) + paged_anchor(plans, key=lambda kk: plans[kk][0] == band)
+        except AssertionError:
+            continue
+    raise AssertionError(band)
+
+
+@functools.lru_cache(maxsize=None)
+def paged_window_anchor():
+    """(W, sample, Plan): the first windowed call of the dense sweep with such a work item behind head tiles, in either query block."""
+    for W in paged_windows():
+        plans = paged_plans(LQ, True, W)
+        try:
+            return (W,) + paged_anchor(plans, key=lambda kk: plans[kk].nh > 0)
+        except AssertionError:
+            continue
+    raise AssertionError("no window")

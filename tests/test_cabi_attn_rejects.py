@@ -39,6 +39,11 @@ VALID = dict(B=1, nseq=1, Hq=4, Hkv=2, Lq=128, max_seqlen_q=128, Lk=128, Lk_chun
              lse=None, v_mean=None, seq_order=None, work_items=None, work_hdr=None, stream=None, attr=None)
 
 
+# the smallest k row stride (a multiple of 16) whose 64-key tile no longer fits an int offset at head_dim 64: 63 k_sl + 64 - 16 >= 2^31
+K_SL_REFUSED = -(-((1 << 31) - 48) // 63 // 16) * 16
+assert K_SL_REFUSED == 34087056 and 63 * (K_SL_REFUSED - 16) + 48 < 1 << 31 <= 63 * K_SL_REFUSED + 48
+
+
 def all_but(*names):
     return [n for n in ATTN if n not in names]
 
@@ -57,6 +62,10 @@ CASES = [
     ("misaligned o", all_but(*SPLIT, EXACT), dict(o=P + 8), b"q/k/v/o must be 16-byte aligned"),
     ("k stride", INT8_Q, dict(k_sl=72), b"int8 q/k strides must be multiples of 16"),
     ("k stride", all_but(*INT8_Q), dict(k_sh=64 * 128 + 8), b"int8 k strides must be multiples of 16"),
+    # (the kernels form a lane's offset into a 64-key tile as int: 63 k_sl + D - 16 < 2^31.  At D 64 the largest stride of whole 16-byte units that
+    #  passes is 34087040; the next one, and a stride that (int) would truncate to 0)
+    ("k tile, the first stride refused", ATTN, dict(k_sl=K_SL_REFUSED), b"one 64-key tile of k must span less than 2 GiB (row stride 34087056)"),
+    ("k tile, a stride of 2^31", ATTN, dict(k_sl=1 << 31), b"one 64-key tile of k must span less than 2 GiB (row stride 2147483648)"),
     ("o stride", all_but(EXACT), dict(o_sl=68), b"output strides must be multiples of 8 elements"),
     # ---- per Q form
     ("q stride, INT8", INT8_Q, dict(q_sl=72), b"int8 q/k strides must be multiples of 16"),
@@ -133,6 +142,6 @@ def test_every_attention_entry_has_every_shared_case():
         for name in entries:
             covered.setdefault(name, set()).add(what.split(",")[0])
     for name in ATTN:
-        need = {"null tensor", "head_dim 96", "Hq % Hkv", "misaligned q" if name != EXACT else "exact split", "k stride", "q stride", "empty problem"}
+        need = {"null tensor", "head_dim 96", "Hq % Hkv", "misaligned q" if name != EXACT else "exact split", "k stride", "k tile", "q stride", "empty problem"}
         need.add("q dtype code" if name == EXACT else "out dtype code")
         assert need <= covered[name], f"{name}: no case for {sorted(need - covered[name])}"
