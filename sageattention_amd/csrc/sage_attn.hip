@@ -4,6 +4,7 @@
 #include "sage_kernels.h"
 #include "sage_attn_parts.h"
 #include "sage_work_order.h"
+#include "sage_step_list.h"
 #include <cstdlib>
 
 #ifndef SAGE_ORDER_DEFAULT   // causal work order: -1 = grouped / folded (plan_grid), 0 = head-major heavy-first, n = groups of n heads
@@ -33,6 +34,9 @@ static int plan_grid(AttnParams &q, const AttnVariant &v)
     q.order_fold = 0;
     q.order_left = 0;
     const int nheads = q.B * q.Hq;
+    // a launch of the listed step call (sage_step_list.h): whole octets of (decode sequence, kv head) units, or the packed route's grid over the
+    // host-known bound of the chunk list
+    if (v.list) return (int)(v.gqa_pack ? step_decode_grid(q.B, q.Hkv, q.group) : step_chunk_grid(q.Hq, q.items_bound));
     // packed GQA groups (decode-shaped, one query block): (batch, kv head, block of four query heads) in head-major order
     if (v.gqa_pack) return q.B * q.Hkv * ((q.group + 3) / 4);
     if (q.cu_q != nullptr && q.work_items != nullptr)             // varlen, device-built work list: bound of the dense-style grid over it
@@ -91,6 +95,8 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
                                 v.ragged->total_q < 1 || (p.lse != nullptr && p.lse_sh < v.ragged->total_q))) return false;
     // one launch of the step call: packed query rows behind a band (lo, hi] of row counts, 0 <= lo <= hi; with packed GQA groups hi <= 32 (above)
     if (v.band != nullptr && (v.ragged == nullptr || v.band->lo < 0 || v.band->hi < v.band->lo)) return false;
+    // ... of the listed step call: the lists in the two members a paged launch leaves free (the chunk list with the bound its grid is sized by)
+    if (v.list && (v.band == nullptr || p.work_hdr == nullptr || p.work_items == nullptr || (!v.gqa_pack && p.items_bound < 1))) return false;
     return true;
 }
 
@@ -109,6 +115,9 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     const AttnForm f = attn_form(p, v, o);
     if (v.paged != nullptr) {     // the paged kernel of the same form: same grid, the ordinary dispatch
         p.sched = nullptr;
+        if (v.list)                   // a launch of the listed step call: the list kernel of the form, from the same lists of forms as the step call's
+            return f.gpack ? (f.D == 128 ? launch_attn_list_units<128, SAGE_STEP_G_UNITS> : launch_attn_list_units<64, SAGE_STEP_G_UNITS>)(pack(f), p, *v.paged, *v.ragged, *v.band, nwork, o)
+                           : (f.D == 128 ? launch_attn_list_units<128, SAGE_STEP_UNITS> : launch_attn_list_units<64, SAGE_STEP_UNITS>)(pack(f), p, *v.paged, *v.ragged, *v.band, nwork, o);
         if (v.band != nullptr)        // a launch of the step call: the step kernel of the form, from the packed-group list (decode) or the ragged units' lists (chunks)
             return f.gpack ? (f.D == 128 ? launch_attn_step_units<128, SAGE_STEP_G_UNITS> : launch_attn_step_units<64, SAGE_STEP_G_UNITS>)(pack(f), p, *v.paged, *v.ragged, *v.band, nwork, o)
                            : (f.D == 128 ? launch_attn_step_units<128, SAGE_STEP_UNITS> : launch_attn_step_units<64, SAGE_STEP_UNITS>)(pack(f), p, *v.paged, *v.ragged, *v.band, nwork, o);

@@ -1,10 +1,19 @@
 // sage_attn_body.h -- the body of sage_attn_kernel<FORM>, of sage_attn_paged_kernel<FORM>, of sage_attn_paged_varlen_kernel<FORM> and of
 // sage_attn_paged_step_kernel<FORM> (sage_attn_kernel.h, which documents the flags): a code fragment, included INSIDE the four kernel functions
 // with SAGE_ATTN_BODY_PAGED defined as false / true / true / true, SAGE_ATTN_BODY_RAGGED as false / false / true / true and SAGE_ATTN_BODY_BAND as
-// false / false / false / true.  Not a header of its own: no include guard, no declarations.
+// false / false / false / true -- and of sage_attn_paged_list_kernel<FORM> (sage_attn_list_kernel.h), the fifth entry: all three true and
+// SAGE_ATTN_BODY_LIST defined as true.  Not a header of its own: no include guard, no declarations.
     static constexpr bool PAGED = SAGE_ATTN_BODY_PAGED;
     static constexpr bool RAGGED = SAGE_ATTN_BODY_RAGGED;
     static constexpr bool BAND = SAGE_ATTN_BODY_BAND;
+#ifndef SAGE_ATTN_BODY_LIST      // (the four entries of sage_attn_kernel.h leave it undefined: false; sage_attn_list_kernel.h defines it true)
+#define SAGE_ATTN_BODY_LIST false
+#define SAGE_ATTN_BODY_LIST_DEFAULTED
+#endif
+    // LIST (sage_attn_paged_list_kernel, sage_attn_list_kernel.h): a step launch whose work items come from the device-built lists
+    // of sage_kv_list_plan.hip -- p.work_hdr / p.work_items, free in a paged launch -- instead of the dense grid.  Only the work-item site differs.
+    static constexpr bool LIST = SAGE_ATTN_BODY_LIST;
+    static_assert(!LIST || BAND, "the listed step launch: a band launch over a work list");
     // The form's fields under the names the body uses.  (static: the body's lambdas capture by reference, and a plain constexpr local that one of
     // them passes on by reference becomes a captured stack slot -- folded away later, but sixteen D = 128 FP16-PV kernels then allocate their
     // registers differently, 217 - 229 VGPRs where these give 219 - 226.)
@@ -158,7 +167,44 @@
     const int nqblk = p.nqblk;
     int b, h, hk, qblk;
     [[maybe_unused]] bool idle = false;       // (GPACK) wave-uniform: this wave's head lies past the group's last one
-    if constexpr (GPACK) {
+    if constexpr (LIST && GPACK) {
+        // the decode list (hdr[0] sequences, heaviest first): units (list rank, kv head) dealt to the XCDs round-robin, the blocks of a unit on
+        // one XCD.  Every word of the list is clamped before anything is formed from it: a workspace the plan never wrote stays inside the operands
+        typedef const __attribute__((address_space(4))) int *cint_p;          // wave-uniform: scalar loads
+        const int nd_raw = ((cint_p)p.work_hdr)[0];
+        const int nd = nd_raw < 0 ? 0 : (nd_raw < p.B ? nd_raw : p.B);
+        const int ngb = (p.group + 3) >> 2;
+        const int xcd = bid & 7, idx = bid >> 3;
+        const int uj = idx / ngb, gb = idx - uj * ngb;
+        const int unit = uj * 8 + xcd;
+        if (unit >= nd * p.Hkv) break;
+        const int r = unit / p.Hkv;
+        const int bl = ((cint_p)p.work_items)[r];
+        b = bl < 0 ? 0 : (bl < p.B ? bl : p.B - 1);
+        hk = unit - r * p.Hkv;
+        const int hw = 4 * gb + wave_s;
+        idle = hw >= p.group;
+        h = hk * p.group + (idle ? 0 : hw);
+        qblk = 0;
+    } else if constexpr (LIST) {
+        // the chunk list: the statements of the packed route's arm below over hdr {nitems, group, fold, left} and the (sequence, query block)
+        // pairs, with every word clamped -- the count to the host-known bound the grid is sized by, the order to one work_item() deals in full
+        typedef const __attribute__((address_space(4))) int *cint_p;          // wave-uniform: scalar loads
+        const cint_p hdr = (cint_p)p.work_hdr;
+        const int ni_raw = hdr[0], g_raw = hdr[1], hpx = p.Hq >> 3;
+        const int nitems = ni_raw < 0 ? 0 : (ni_raw < p.items_bound ? ni_raw : p.items_bound);
+        const WorkOrder wo = {g_raw < 1 || hpx < 1 ? 1 : (g_raw < hpx ? g_raw : hpx), hdr[2] != 0 ? 1 : 0, p.Hq & 7};
+        const int nwg = 8 * (wo.left * ((nitems + 7) >> 3) + hpx * nitems);
+        int qrank;
+        if (bid >= nwg || !work_item(wo, bid, nwg, p.Hq, nitems, h, qrank)) break;
+        qrank = qrank < 0 ? 0 : (qrank < nitems ? qrank : nitems - 1);
+        h = h < 0 ? 0 : (h < p.Hq ? h : p.Hq - 1);
+        const cint_p items = (cint_p)p.work_items;
+        const int bl = items[2 * qrank], ql = items[2 * qrank + 1];
+        b = bl < 0 ? 0 : (bl < p.B ? bl : p.B - 1);
+        qblk = ql < 0 ? 0 : (ql < nqblk ? ql : nqblk - 1);
+        hk = h / p.group;
+    } else if constexpr (GPACK) {
         // the grid is B * Hkv * ceil(group / 4) items in head-major order, one contiguous run per XCD as below: the blocks of a kv head -- and
         // the kv heads of a sample -- stream K / V through one L2
         const int ngb = (p.group + 3) >> 2;
@@ -1237,3 +1283,7 @@
             }
         }
     }
+#ifdef SAGE_ATTN_BODY_LIST_DEFAULTED
+#undef SAGE_ATTN_BODY_LIST_DEFAULTED
+#undef SAGE_ATTN_BODY_LIST
+#endif

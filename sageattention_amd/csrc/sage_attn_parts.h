@@ -48,4 +48,13 @@ extern template hipError_t launch_attn_step_units<64, SAGE_STEP_UNITS>(uint32_t,
 extern template hipError_t launch_attn_step_units<128, SAGE_STEP_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_step_units<64, SAGE_STEP_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
 
+// the list kernels (the step kernels over device-built work lists, sage_attn_list_kernel.h) of the QSTART forms of the same lists:
+// sage_attn_d{128,64}_f8pl.hip holds those of F8Q / F8W (the listed step call's chunk launch), sage_attn_d{128,64}_f8plg.hip those of F8G (its decode launch)
+template <int D, AttnUnit... U>
+hipError_t launch_attn_list_units(uint32_t form, const AttnParams &p, const PagedArgs &g, const RaggedArgs &r, const BandArgs &b, int nwork, const AttnLaunchOpts &l);
+extern template hipError_t launch_attn_list_units<128, SAGE_STEP_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_list_units<64, SAGE_STEP_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_list_units<128, SAGE_STEP_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_list_units<64, SAGE_STEP_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+
 }  // namespace sage

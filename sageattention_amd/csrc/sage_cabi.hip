@@ -5,9 +5,11 @@
 #include "../../include/sage_kvpsplit_gfx950.h"
 #include "../../include/sage_kvpvarlen_gfx950.h"
 #include "../../include/sage_kvstep_gfx950.h"
+#include "../../include/sage_kvlist_gfx950.h"
 #include "sage_common.h"
 #include "sage_kernels.h"
 #include "sage_work_order.h"
+#include "sage_step_list.h"
 #include "sage_host_checks.h"
 #include "sage_kv_cache.h"
 
@@ -133,6 +135,8 @@ struct AttnCall {
     const sage::RaggedArgs *ragged;  // sage_kvpvarlen_attn (with paged): q / o packed [total_q, Hq, D] behind cu_seqlens_q, lse [Hq, total_q]; Lq = max_seqlen_q, qs.sb = os.sb = 0
     bool paged_split;                // sage_kvpsplit_attn (with paged): the exact split on that pool -- SAGE_ATTR_KV_SPLIT is required instead of refused
     bool step;                       // sage_kvstep_attn (with ragged): two launches behind band filters, the decode rows packed by GQA group
+    bool list; int32_t *list_ws;     // sage_kvlist_attn (with step): the work lists' workspace -- a plan launch in front, the list kernels
+    int64_t list_ws_bytes;
     int is_causal, gran, q_warp, pv_accum, q_dtype, out_dtype;
     float sm_scale_log2, q_premul;
     void *stream; const SageLaunchAttr *attr;
@@ -278,7 +282,7 @@ int attn_run(const AttnCall &c)
                                              c.D > 0 ? c.D : 0, S)) return rc;
     } else
     if (c.paged != nullptr && c.attr != nullptr && c.attr->struct_bytes >= 8) {
-        const char *const e = c.step ? "sage_kvstep_attn" : c.ragged != nullptr ? "sage_kvpvarlen_attn" : "sage_kvpaged_attn";
+        const char *const e = c.list ? "sage_kvlist_attn" : c.step ? "sage_kvstep_attn" : c.ragged != nullptr ? "sage_kvpvarlen_attn" : "sage_kvpaged_attn";
         const unsigned f = c.attr->flags;
         SAGE_REQUIRE(!(f & (SAGE_ATTR_KV_SPLIT | (0xffu << SAGE_ATTR_KV_SPLIT_SHIFT))),
                      "%s: SAGE_ATTR_KV_SPLIT is not supported on a paged cache (pass 1 and the split's kernels do not look pages up)", e);
@@ -290,7 +294,7 @@ int attn_run(const AttnCall &c)
     if (const int rc = read_attr(c.attr, c.stream, c.mask == nullptr && !split && c.paged == nullptr, la)) return rc;     // (masked, split and paged launches take no launch workspace)
     // (packed query rows: the offsets place every sample's rows, so they are required -- the bottom-right ones are the caller's kv_lens[b] - Lq_b)
     SAGE_REQUIRE(c.ragged == nullptr || la.q_start != nullptr, "%s: SageLaunchAttr.q_start is required (int32 [B]: the key position of each sample's row 0)",
-                 c.step ? "sage_kvstep_attn" : "sage_kvpvarlen_attn");
+                 c.list ? "sage_kvlist_attn" : c.step ? "sage_kvstep_attn" : "sage_kvpvarlen_attn");
     // ---- the routes a Q form admits
     if (c.kv_lens == nullptr) SAGE_REFUSE_KV_SPLIT(la);
     SAGE_REQUIRE(la.kv_split_flag || la.kv_split == 0, "SAGE_ATTR_KV_SPLIT: a chunk count (%d in flags bits 16-23) without the bit", la.kv_split);
@@ -379,6 +383,40 @@ int attn_run(const AttnCall &c)
     v.two_level = fp8 ? c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : c.pv_accum == SAGE_PV_ACCUM_TRITON;
     v.qf = int8q ? 0 : sage::attn_qf(per_block, c.q_dtype);
     if (la.kv_split_flag) return kv_split_run(c, la, p, v);
+    if (c.list) {
+        // the listed step call: the step call's two launches behind a plan launch, their items from its lists (sage_step_list.h) -- the workspace
+        // checks first, the last of the entry's; then plan, decode, chunk on the call's stream, no host read in between
+        const char *const e = "sage_kvlist_attn";
+        const int total_q = c.ragged->total_q;
+        const long long need = 4 * sage::step_ws_words(c.B, total_q, c.Lq), bound = sage::step_chunk_bound(c.B, total_q, c.Lq);
+        SAGE_REQUIRE(c.list_ws != nullptr && (reinterpret_cast<uintptr_t>(c.list_ws) & 3u) == 0, "%s: list_ws must be int32 device memory, 4-byte aligned (got %p)", e, (void *)c.list_ws);
+        SAGE_REQUIRE(c.list_ws_bytes >= need, "%s: list_ws holds %lld bytes, sage_kvlist_ws_bytes(B, total_q, max_seqlen_q) = %lld are needed", e, (long long)c.list_ws_bytes, need);
+        SAGE_REQUIRE(c.B <= sage::kVarlenPlanMaxSeq, "%s: B must be at most %d, the sequences one plan launch takes (got %d)", e, sage::kVarlenPlanMaxSeq, c.B);
+        SAGE_REQUIRE(sage::step_decode_grid(c.B, c.Hkv, c.Hq / c.Hkv) < (1LL << 31) && sage::step_chunk_grid(c.Hq, bound) < (1LL << 31), "%s: grid too large", e);
+        sage::KvListPlanParams lp{};
+        lp.cu_q = c.ragged->cu_q; lp.kv_lens = c.kv_lens; lp.q_start = la.q_start;
+        lp.B = c.B; lp.total_q = total_q; lp.max_seqlen_q = c.Lq; lp.Lk = c.Lk; lp.window = la.window;
+        lp.Hq = c.Hq; lp.Hkv = c.Hkv; lp.head_dim = c.D; lp.items_cap = (int)bound; lp.ws = c.list_ws;
+        if (la.opts.grid_out != nullptr) *la.opts.grid_out = 0;
+        if (const int rc = check_launch(sage::launch_kv_list_plan(lp, static_cast<hipStream_t>(c.stream)), "sage_kvlist_attn plan launch")) return rc;
+        int grid_d = 0, grid_c = 0;
+        sage::AttnLaunchOpts o = la.opts;
+        const sage::BandArgs decode{0, sage::kStepDecodeRows}, chunk{sage::kStepDecodeRows, c.Lq};
+        sage::AttnVariant vs = v;
+        sage::AttnParams pl = p;
+        vs.list = true;
+        vs.gqa_pack = true; vs.band = &decode; o.grid_out = &grid_d;
+        pl.work_hdr = c.list_ws; pl.work_items = c.list_ws + sage::kStepHdrWords; pl.items_bound = 0;
+        if (const int rc = check_launch(sage::launch_attention(pl, vs, o), "sage_kvlist_attn decode launch")) return rc;
+        if (c.Lq > sage::kStepDecodeRows && bound > 0) {
+            // (hdr + 1: {n_chunk_items, group, fold, left}, the four words the packed route's header starts with)
+            vs.gqa_pack = false; vs.band = &chunk; o.grid_out = &grid_c;
+            pl.work_hdr = c.list_ws + 1; pl.work_items = c.list_ws + sage::kStepHdrWords + c.B; pl.items_bound = (int)bound;
+            if (const int rc = check_launch(sage::launch_attention(pl, vs, o), "sage_kvlist_attn chunk launch")) return rc;
+        }
+        if (la.opts.grid_out != nullptr) *la.opts.grid_out = grid_d + grid_c;
+        return SAGE_OK;
+    }
     if (c.step) {
         // the step call: the decode launch -- the samples of 1 .. 32 rows, GPACK's work item -- always, then the chunk launch -- the samples of more
         // rows, the ragged launch's grid -- only if max_seqlen_q admits such a sample (host-known: a pure decode step is one launch).  Both on the
@@ -1189,6 +1227,96 @@ SAGE_KVSTEP_API int sage_kvstep_attn(const void *q, const int8_t *k_int8, const 
     c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
     c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g; c.ragged = &r;
     c.step = true;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.Lk = max_pages_per_seq * page_size; c.D = D;
+    c.qs = {0, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {0, o_sh, o_sl}; c.lse_sh = lse_sh;
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
+}
+
+// sage_kvstep_attn with its launches over device-built work lists, heaviest first (include/sage_kvlist_gfx950.h)
+SAGE_KVLIST_API int sage_kvlist_abi_version(void) { return SAGE_KVLIST_ABI_VERSION; }
+
+SAGE_KVLIST_API int64_t sage_kvlist_ws_bytes(int B, int total_q, int max_seqlen_q)
+{
+    if (B < 1 || total_q < 1 || max_seqlen_q < 1) return sage::set_last_error(SAGE_EINVAL, "sage_kvlist_ws_bytes: B, total_q and max_seqlen_q must be at least 1 (got %d, %d, %d)", B, total_q, max_seqlen_q);
+    return 4 * sage::step_ws_words(B, total_q, max_seqlen_q);
+}
+
+// the checks sage_kvlist_plan and sage_kvlist_plan_host share (`e`: the entry's name); fills the plan's parameters
+static int kvlist_plan_args(const char *e, const int32_t *cu_seqlens_q, const int32_t *kv_lens, const int32_t *q_start, int B, int total_q, int max_seqlen_q,
+                            int capacity, int window, int Hq, int Hkv, int D, int32_t *list_ws, int64_t list_ws_bytes, sage::KvListPlanParams &lp)
+{
+    SAGE_REQUIRE(cu_seqlens_q && kv_lens && q_start, "%s: null cu_seqlens_q, kv_lens or q_start", e);
+    SAGE_REQUIRE(((reinterpret_cast<uintptr_t>(cu_seqlens_q) | reinterpret_cast<uintptr_t>(kv_lens) | reinterpret_cast<uintptr_t>(q_start)) & 3u) == 0,
+                 "%s: cu_seqlens_q, kv_lens and q_start must be 4-byte aligned", e);
+    SAGE_REQUIRE(B >= 1 && B <= sage::kVarlenPlanMaxSeq, "%s: B must be in 1 .. %d (got %d)", e, sage::kVarlenPlanMaxSeq, B);
+    SAGE_REQUIRE(total_q >= 1 && max_seqlen_q >= 1 && capacity >= 1, "%s: total_q, max_seqlen_q and capacity must be at least 1 (got %d, %d, %d)", e, total_q, max_seqlen_q, capacity);
+    SAGE_REQUIRE(window >= 0, "%s: window = %d: the number of keys a row sees up to its diagonal, 0 = unbounded", e, window);
+    SAGE_REQUIRE(Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0, "%s: Hq (%d) must be divisible by Hkv (%d)", e, Hq, Hkv);
+    SAGE_REQUIRE_HEAD_DIM(D, "");
+    SAGE_REQUIRE((int64_t)B * Hq * ((max_seqlen_q + 127) / 128) < ((int64_t)1 << 31), "%s: B * Hq * ceil(max_seqlen_q / 128) must be below 2^31 (got %d, %d, %d)", e, B, Hq, max_seqlen_q);
+    const long long need = 4 * sage::step_ws_words(B, total_q, max_seqlen_q);
+    SAGE_REQUIRE(list_ws != nullptr && (reinterpret_cast<uintptr_t>(list_ws) & 3u) == 0 && list_ws_bytes >= need,
+                 "%s: list_ws is %lld bytes of int32 memory, 4-byte aligned (got %lld bytes at %p)", e, need, (long long)list_ws_bytes, (void *)list_ws);
+    lp = sage::KvListPlanParams{};
+    lp.cu_q = cu_seqlens_q; lp.kv_lens = kv_lens; lp.q_start = q_start;
+    lp.B = B; lp.total_q = total_q; lp.max_seqlen_q = max_seqlen_q; lp.Lk = capacity; lp.window = window;
+    lp.Hq = Hq; lp.Hkv = Hkv; lp.head_dim = D; lp.items_cap = (int)sage::step_chunk_bound(B, total_q, max_seqlen_q); lp.ws = list_ws;
+    return SAGE_OK;
+}
+
+SAGE_KVLIST_API int sage_kvlist_plan(const int32_t *cu_seqlens_q, const int32_t *kv_lens, const int32_t *q_start,
+                                     int B, int total_q, int max_seqlen_q, int capacity, int window, int Hq, int Hkv, int D,
+                                     int32_t *list_ws, int64_t list_ws_bytes, void *stream)
+{
+    sage::KvListPlanParams lp;
+    if (const int rc = kvlist_plan_args("sage_kvlist_plan", cu_seqlens_q, kv_lens, q_start, B, total_q, max_seqlen_q, capacity, window, Hq, Hkv, D, list_ws, list_ws_bytes, lp)) return rc;
+    return check_launch(sage::launch_kv_list_plan(lp, static_cast<hipStream_t>(stream)), "sage_kvlist_plan launch");
+}
+
+SAGE_KVLIST_API int sage_kvlist_plan_host(const int32_t *cu_seqlens_q, const int32_t *kv_lens, const int32_t *q_start,
+                                          int B, int total_q, int max_seqlen_q, int capacity, int window, int Hq, int Hkv, int D,
+                                          int32_t *list_ws, int64_t list_ws_bytes, int *decode_grid, int *chunk_grid)
+{
+    sage::KvListPlanParams lp;
+    if (const int rc = kvlist_plan_args("sage_kvlist_plan_host", cu_seqlens_q, kv_lens, q_start, B, total_q, max_seqlen_q, capacity, window, Hq, Hkv, D, list_ws, list_ws_bytes, lp)) return rc;
+    int scratch[3 * sage::kVarlenPlanMaxSeq];
+    sage::step_plan_serial(cu_seqlens_q, kv_lens, q_start, B, total_q, max_seqlen_q, capacity, window, Hq, Hkv, D, lp.items_cap,
+                           scratch, scratch + sage::kVarlenPlanMaxSeq, scratch + 2 * sage::kVarlenPlanMaxSeq, list_ws);
+    if (decode_grid != nullptr) *decode_grid = (int)sage::step_decode_grid(B, Hkv, Hq / Hkv);
+    if (chunk_grid != nullptr) *chunk_grid = max_seqlen_q > sage::kStepDecodeRows ? (int)sage::step_chunk_grid(Hq, lp.items_cap) : 0;
+    return SAGE_OK;
+}
+
+SAGE_KVLIST_API int sage_kvlist_attn(const void *q, const int8_t *k_int8, const void *v_image, void *o, float *lse,
+                                     const float *k_scale, const float *v_scale, const int32_t *kv_lens, const int32_t *cu_seqlens_q,
+                                     const int32_t *block_table, int64_t bt_stride, int num_pages, int page_size, int max_pages_per_seq,
+                                     int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                                     int64_t q_sl, int64_t q_sh, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                     int64_t o_sl, int64_t o_sh, int64_t lse_sh,
+                                     int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr,
+                                     int32_t *list_ws, int64_t list_ws_bytes)
+{
+    const char *const e = "sage_kvlist_attn";
+    SAGE_REQUIRE(q && k_int8 && v_image && o && k_scale && v_scale, "%s: null tensor pointer (only lse may be null)", e);
+    SAGE_REQUIRE(kv_lens, "%s: null kv_lens", e);
+    SAGE_REQUIRE(cu_seqlens_q, "%s: null cu_seqlens_q", e);
+    sage::PagedArgs g;
+    if (const int rc = sage::paged_args(e, block_table, bt_stride, num_pages, page_size, max_pages_per_seq, g)) return rc;
+    if (const int rc = sage::kv_check_batch(e, B, Hkv)) return rc;
+    if (const int rc = sage::paged_check_table_aligned(e, block_table)) return rc;
+    SAGE_REQUIRE((reinterpret_cast<uintptr_t>(cu_seqlens_q) & 3u) == 0, "%s: cu_seqlens_q must be 4-byte aligned", e);
+    SAGE_REQUIRE(total_q >= 1 && max_seqlen_q >= 1, "%s: total_q and max_seqlen_q must be at least 1 (got %d, %d)", e, total_q, max_seqlen_q);
+    SAGE_REQUIRE(is_causal == 1, "%s: is_causal must be 1 (packed query rows are placed by their offsets; got %d)", e, is_causal);
+    SAGE_REQUIRE(Hq >= 1 && (int64_t)B * Hq * ((max_seqlen_q + 127) / 128) < ((int64_t)1 << 31), "%s: B * Hq * ceil(max_seqlen_q / 128) must be in [1, 2^31) (got %d, %d, %d)",
+                 e, B, Hq, max_seqlen_q);
+    SAGE_REQUIRE(lse == nullptr || lse_sh >= total_q, "%s: lse is [Hq, total_q]: its head stride lse_sh must be at least total_q (got %lld)", e, (long long)lse_sh);
+    SAGE_REQUIRE(Hq / Hkv >= 2, "%s: Hq / Hkv must be at least 2, no GQA group to pack (got Hq %d, Hkv %d; sage_kvpvarlen_attn takes such a call)", e, Hq, Hkv);
+    const sage::RaggedArgs r{cu_seqlens_q, total_q};
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
+    c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g; c.ragged = &r;
+    c.step = true; c.list = true; c.list_ws = list_ws; c.list_ws_bytes = list_ws_bytes;
     c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.Lk = max_pages_per_seq * page_size; c.D = D;
     c.qs = {0, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {0, o_sh, o_sl}; c.lse_sh = lse_sh;
     c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;

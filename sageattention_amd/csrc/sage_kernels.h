@@ -142,6 +142,9 @@ struct AttnVariant {
     const BandArgs *band;   // non-null (host memory, with ragged): one launch of the step call -- the step kernel of the same form, which runs the
                         // samples inside the band alone.  With gqa_pack it is the decode launch: B * Hkv * ceil(group / 4) items whatever
                         // AttnParams::Lq = max_seqlen_q is (the band's hi <= 32 bounds the rows instead)
+    bool list;          // (with band) a launch of the LISTED step call (sage_kvlist_attn): the list kernel of the same form, its items from
+                        // AttnParams::work_hdr / work_items (device memory, written by launch_kv_list_plan).  With gqa_pack the decode list, grid
+                        // 8 * ceil(B * Hkv / 8) * ceil(group / 4); without, the chunk list, the packed route's grid over AttnParams::items_bound
 };
 constexpr int attn_qf(bool per_block, int q_dtype) { return (per_block ? 3 : 1) + (q_dtype == 0 ? 0 : 1); }   // q_dtype: DT_F16 (0) / DT_BF16
 // the one attention launcher: plans the work order, checks that the route exists (hipErrorInvalidValue) and launches the variant's kernel.
@@ -196,6 +199,19 @@ struct VarlenPlanParams {
                                          // device are clamped to them (hdr reports the clamped counts), so an inconsistent cu_seqlens cannot write past
 };
 hipError_t launch_varlen_plan(const VarlenPlanParams &p, hipStream_t stream);
+
+// the listed step call's work lists from one small launch (sage_kv_list_plan.hip; the arithmetic is sage_step_list.h's), B <= kVarlenPlanMaxSeq
+constexpr int kStepListHdrWords = 16;    // hdr: n_decode, n_chunk_items, group, fold, left, chunk items before the clamp, max key count of a chunk sequence, 0 ...
+struct KvListPlanParams {
+    const int32_t *cu_q;                 // [B + 1] the packed query rows' prefix array
+    const int32_t *kv_lens, *q_start;    // [B]
+    int B, total_q, max_seqlen_q;
+    int Lk, window;                      // the logical capacity; SageLaunchAttr.window (0: none)
+    int Hq, Hkv, head_dim;               // for the chunk launch's plan (hdr) only
+    int items_cap;                       // (sequence, query block) pairs the chunk list holds: step_chunk_bound()
+    int32_t *ws;                         // hdr[kStepListHdrWords], decode_list[B], chunk_items[2 * items_cap]
+};
+hipError_t launch_kv_list_plan(const KvListPlanParams &p, hipStream_t stream);
 
 // ---- per-channel statistics over the sequence (K mean, V amax / mean) -----------------------------
 #ifndef SAGE_STATS_SLAB
