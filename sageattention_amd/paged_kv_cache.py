@@ -10,7 +10,8 @@ block alone: the paged cache holds, at the places the table names, byte for byte
 Device rules: attention reads the table entries of tiles that hold a key it requests and no others, and clamps every id to
 ``[0, num_pages - 1]`` before it forms an address; an append does not write a block whose id lies outside ``[0, num_pages)`` (``lens`` still
 advance).  A bad table gives wrong numbers, never an access outside the pool.  Two sequences that append into one page are the caller's error
-and are not detected; there is no allocator here.
+and are not detected; there is no allocator here (:mod:`~sageattention_amd.paged_kv_pool` keeps one on the device, over a cache whose table it
+alone writes).
 
 Sequences share pages through :meth:`PagedQuantizedKVCache.fork`: the child's table names the parent's closed pages, the
 parent's open page is copied into a page of the child's own, and the child takes the parent's frozen statistics -- which is what makes the
