@@ -70,7 +70,8 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
     if (v.seeded != (p.seed_max != nullptr) || (v.seeded && p.kv_split < 1)) return false;
     if (v.kv_lens && (p.cu_k == nullptr || (p.kv_split > 1 && !v.seeded))) return false;
     // the kv_lens family's split (seeded with kv_lens): one query block, chunks of whole tiles folded into the kv heads, no window
-    if (v.seeded && v.kv_lens && (p.nqblk != 1 || p.kv_split < 2 || p.kv_base <= 0 || (p.kv_base & 63) != 0 || p.Hkv % p.kv_split != 0 ||
+    // (the split step call's pass 2 -- a listed decode launch, below: p.Lq = max_seqlen_q sizes nothing there, the band bounds the rows)
+    if (v.seeded && v.kv_lens && ((v.list && v.band != nullptr ? v.band->hi > 32 : p.nqblk != 1) || p.kv_split < 2 || p.kv_base <= 0 || (p.kv_base & 63) != 0 || p.Hkv % p.kv_split != 0 ||
                                   p.seed_chunks != p.kv_split || p.seed_first != 0 || v.window != 0 || p.sched != nullptr)) return false;
     if (v.q_start != (!varlen && p.cu_qs != nullptr) || (v.q_start && (!v.kv_lens || !v.causal))) return false;
     // a window: the causal kv_lens kernels (offsets optional), or -- without kv_lens -- a packed bottom-right launch (the next line's conditions);
@@ -91,8 +92,10 @@ static bool route_exists(const AttnParams &p, const AttnVariant &v, const AttnLa
                                (long)p.Lk != ((long)v.paged->max_pages << (6 + v.paged->page_shift)) || p.nks != (4 << v.paged->page_shift))) return false;
     // packed query rows on that pool: the paged q_start / window kernels (no packed GQA groups, no split); the prefix array is the third kernel
     // argument, p.cu_q stays null -- the dense grid and the dense branches of the kernel -- and the packed lse needs its head stride
-    if (v.ragged != nullptr && (v.paged == nullptr || !v.q_start || !v.causal || (v.gqa_pack && v.band == nullptr) || v.seeded || varlen || v.ragged->cu_q == nullptr ||
-                                v.ragged->total_q < 1 || (p.lse != nullptr && p.lse_sh < v.ragged->total_q))) return false;
+    if (v.ragged != nullptr && (v.paged == nullptr || !v.q_start || !v.causal || (v.gqa_pack && v.band == nullptr) || (v.seeded && !(v.list && v.gqa_pack && v.kv_lens)) || varlen ||
+                                v.ragged->cu_q == nullptr || v.ragged->total_q < 1 ||
+                                // (the split step call's pass 2: the partials are dense -- p.lse is lse_part, p.lse_sh the rows per (sequence, head) of the workspace)
+                                (v.seeded ? (p.lse == nullptr || p.lse_sh < 1 || p.lse_sh > 32) : (p.lse != nullptr && p.lse_sh < v.ragged->total_q)))) return false;
     // one launch of the step call: packed query rows behind a band (lo, hi] of row counts, 0 <= lo <= hi; with packed GQA groups hi <= 32 (above)
     if (v.band != nullptr && (v.ragged == nullptr || v.band->lo < 0 || v.band->hi < v.band->lo)) return false;
     // ... of the listed step call: the lists in the two members a paged launch leaves free (the chunk list with the bound its grid is sized by)
@@ -115,6 +118,8 @@ hipError_t launch_attention(const AttnParams &p_in, const AttnVariant &v, const 
     const AttnForm f = attn_form(p, v, o);
     if (v.paged != nullptr) {     // the paged kernel of the same form: same grid, the ordinary dispatch
         p.sched = nullptr;
+        if (v.list && f.seed)         // pass 2 of the split step call: the list kernel of the seeded packed-group form (route_exists: gqa_pack with kv_lens)
+            return (f.D == 128 ? launch_attn_lsplit_units<128, SAGE_STEP_KS_UNITS> : launch_attn_lsplit_units<64, SAGE_STEP_KS_UNITS>)(pack(f), p, *v.paged, *v.ragged, *v.band, nwork, o);
         if (v.list)                   // a launch of the listed step call: the list kernel of the form, from the same lists of forms as the step call's
             return f.gpack ? (f.D == 128 ? launch_attn_list_units<128, SAGE_STEP_G_UNITS> : launch_attn_list_units<64, SAGE_STEP_G_UNITS>)(pack(f), p, *v.paged, *v.ragged, *v.band, nwork, o)
                            : (f.D == 128 ? launch_attn_list_units<128, SAGE_STEP_UNITS> : launch_attn_list_units<64, SAGE_STEP_UNITS>)(pack(f), p, *v.paged, *v.ragged, *v.band, nwork, o);

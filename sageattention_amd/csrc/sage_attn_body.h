@@ -2,7 +2,8 @@
 // sage_attn_paged_step_kernel<FORM> (sage_attn_kernel.h, which documents the flags): a code fragment, included INSIDE the four kernel functions
 // with SAGE_ATTN_BODY_PAGED defined as false / true / true / true, SAGE_ATTN_BODY_RAGGED as false / false / true / true and SAGE_ATTN_BODY_BAND as
 // false / false / false / true -- and of sage_attn_paged_list_kernel<FORM> (sage_attn_list_kernel.h), the fifth entry: all three true and
-// SAGE_ATTN_BODY_LIST defined as true.  Not a header of its own: no include guard, no declarations.
+// SAGE_ATTN_BODY_LIST defined as true (a SEED form under that entry is pass 2 of the split step call).  Not a header of its own: no
+// include guard, no declarations.
     static constexpr bool PAGED = SAGE_ATTN_BODY_PAGED;
     static constexpr bool RAGGED = SAGE_ATTN_BODY_RAGGED;
     static constexpr bool BAND = SAGE_ATTN_BODY_BAND;
@@ -36,7 +37,11 @@
     static constexpr bool QSTART = F.qstart;
     static constexpr bool KVLEN = F.kvlen;
     static_assert(!PAGED || (KVLEN && PV_FP8), "paged tiles: the kv_lens family, its split (SEED with KVLEN) included");
-    static_assert(!RAGGED || (PAGED && CAUSAL && QSTART && !SEED && (BAND || !GPACK)), "packed query rows: the paged q_start / window kernels (a step launch: their packed-group forms too)");
+    // LSPLIT: pass 2 of the split step call -- the list entry over a SEED form: the decode list's sequences as p.kv_split key-range chunks each,
+    // Q from the packed rows, the FP32 partials into the dense split workspace whose rows per (sequence, head) are p.lse_sh (min(max_seqlen_q, 32))
+    static constexpr bool LSPLIT = LIST && SEED;
+    static_assert(!LSPLIT || (GPACK && KVLEN && !WINDOW), "the split step launch: the seeded packed-group forms with offsets, no window");
+    static_assert(!RAGGED || (PAGED && CAUSAL && QSTART && (LSPLIT || !SEED) && (BAND || !GPACK)), "packed query rows: the paged q_start / window kernels (a step launch: their packed-group forms too; the split step launch: the seeded ones)");
     static_assert(!BAND || RAGGED, "the band filter: a ragged launch of the step call");
     // The parameter block is read through the kernarg segment pointer, and inside the persistent loop through a copy of that pointer the
     // compiler cannot see through (an empty asm): otherwise every scalar load of a parameter is hoisted out of the loop and stays live in
@@ -167,7 +172,23 @@
     const int nqblk = p.nqblk;
     int b, h, hk, qblk;
     [[maybe_unused]] bool idle = false;       // (GPACK) wave-uniform: this wave's head lies past the group's last one
-    if constexpr (LIST && GPACK) {
+    if constexpr (LSPLIT) {
+        // the decode list again, every sequence as p.kv_split chunks: units (list rank, chunk, kv head) dealt as the arm below deals (list rank, kv head)
+        // -- step_split_item, sage_step_list.h -- with the chunk folded into the kv heads as the dense split folds it (hk = hk0 * S + chunk, p.Hkv =
+        // Hkv * S).  Every word of the list is clamped before anything is formed from it
+        typedef const __attribute__((address_space(4))) int *cint_p;          // wave-uniform: scalar loads
+        const int nd_raw = ((cint_p)p.work_hdr)[0];
+        const int nd = nd_raw < 0 ? 0 : (nd_raw < p.B ? nd_raw : p.B);
+        int r, ck, hk0, gb;
+        if (!step_split_item(bid, nd, p.kv_split, p.Hkv / p.kv_split, p.group, r, ck, hk0, gb)) break;
+        const int bl = ((cint_p)p.work_items)[r];
+        b = bl < 0 ? 0 : (bl < p.B ? bl : p.B - 1);
+        hk = hk0 * p.kv_split + ck;
+        const int hw = 4 * gb + wave_s;
+        idle = hw >= p.group;
+        h = hk * p.group + (idle ? 0 : hw);
+        qblk = 0;
+    } else if constexpr (LIST && GPACK) {
         // the decode list (hdr[0] sequences, heaviest first): units (list rank, kv head) dealt to the XCDs round-robin, the blocks of a unit on
         // one XCD.  Every word of the list is clamped before anything is formed from it: a workspace the plan never wrote stays inside the operands
         typedef const __attribute__((address_space(4))) int *cint_p;          // wave-uniform: scalar loads
@@ -319,13 +340,29 @@
         const int bu = __builtin_amdgcn_readfirstlane(b);
         const int len = ((cint_p)p.cu_k)[bu];
         const int lenb = len < 0 ? 0 : (len < p.Lk ? len : p.Lk);
+        // (RAGGED: the split step launch) the sample's rows of the packed q, by the band arm's statements below: Lq is the sample's own row count
+        // from here on, as in the dense split call of that many rows; a sample outside the band leaves.  (ragged_band_rows: ragged_band itself
+        // under the name of this second site, sage_ragged.h)
+        [[maybe_unused]] int rq0 = 0;
+        if constexpr (RAGGED) {
+            typedef const __attribute__((address_space(4))) RaggedArgs *kragged_t;
+            typedef const __attribute__((address_space(4))) BandArgs *kband_t;
+            const kragged_t r = (kragged_t)((const __attribute__((address_space(4))) char *)kp + kRaggedArgsOffset);
+            const kband_t bd = (kband_t)((const __attribute__((address_space(4))) char *)kp + kBandArgsOffset);
+            ragged_band_rows(((cint_p)r->cu_q)[bu], ((cint_p)r->cu_q)[bu + 1], r->total_q, p.Lq, bd->lo, bd->hi, rq0, Lq);
+            if (qblk * BLKQ >= Lq) break;
+        }
         if constexpr (QSTART) {            // (p.cu_qs may be null: offsets 0, the top-left mask)
             const int s = p.cu_qs != nullptr ? ((cint_p)p.cu_qs)[bu] : 0;
+            if constexpr (RAGGED) qstart = s < -Lq ? -Lq : (s < p.Lk ? s : p.Lk);         // (the sample's own row count where the dense kernel has the call's)
+            else
             qstart = s < -p.Lq ? -p.Lq : (s < p.Lk ? s : p.Lk);
         }
         kc0w = kc0;
         const int left = lenb - kc0;
         Lk = left < 0 ? 0 : (left < p.kv_base ? left : p.kv_base);
+        if constexpr (RAGGED) q_off = (long)rq0 * p.q_sl + (long)(hk0 * p.group + (h - hk * p.group)) * p.q_sh;
+        else
         q_off = (long)b * p.q_sb + (long)(hk0 * p.group + (h - hk * p.group)) * p.q_sh;
         if constexpr (PAGED) k_off = (long)hk0 * p.k_sh;             // (the page's p.k_sb and the tile inside it come per tile: k_tile, through pt0)
         else
@@ -779,10 +816,18 @@
     if constexpr (SEED && KVLEN) {
         // as below, for this wave's head (GPACK: an idle wave reads its group's first head and stores nothing); up to 254 chunks stand in
         // front, so the values are requested four at a time instead of one memory round trip each
+        // (RAGGED: the split step launch -- the workspace's rows per (sequence, head) are p.lse_sh, a quantity of its own; Lq is the sample's)
         if (my_row < Lq) {
             const int hk0 = hk / p.kv_split;
-            const long gl = (long)p.group * Lq;
-            const float *sm = p.seed_max + ((long)b * (p.Hkv / p.kv_split) + hk0) * p.seed_chunks * gl + (long)(h - hk * p.group) * Lq + my_row;
+            long gl;
+            const float *sm;
+            if constexpr (RAGGED) {
+                gl = (long)p.group * p.lse_sh;
+                sm = p.seed_max + ((long)b * (p.Hkv / p.kv_split) + hk0) * p.seed_chunks * gl + (long)(h - hk * p.group) * p.lse_sh + my_row;
+            } else {
+            gl = (long)p.group * Lq;
+            sm = p.seed_max + ((long)b * (p.Hkv / p.kv_split) + hk0) * p.seed_chunks * gl + (long)(h - hk * p.group) * Lq + my_row;
+            }
             const int c_end = hk - hk0 * p.kv_split;
             int c = 0;
             for (; c + 4 <= c_end; c += 4) {
@@ -1155,6 +1200,8 @@
     const float inv = l_tot > 0.0f ? __builtin_amdgcn_rcpf(l_tot) : 0.0f;
     if (p.lse != nullptr && g == 0 && my_row < Lq_w) {
         long lidx;
+        if constexpr (RAGGED && SEED) lidx = ((long)b * p.Hq + h) * p.lse_sh + my_row;      // (the split step launch: lse_part [B, Hq * S, p.lse_sh], dense)
+        else
         if constexpr (RAGGED) {
             // the packed index, from the clamped first row: the two words are read and clamped again here (a pointer the compiler cannot see
             // through) instead of a value kept in an SGPR across the key loop

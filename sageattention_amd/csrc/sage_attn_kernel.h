@@ -44,6 +44,7 @@
 #include "sage_quant_math.h"
 #include "sage_work_order.h"
 #include "sage_ragged.h"
+#include "sage_step_list.h"
 #include <atomic>
 #include <climits>
 #include <cstdlib>

@@ -1,6 +1,7 @@
 // sage_attn_list_kernel.h -- the fifth entry over sage_attn_body.h: sage_attn_paged_list_kernel<FORM>, the step kernel of form FORM whose work
 // items come from the device-built lists of sage_kv_list_plan.hip (include/sage_kvlist_gfx950.h).  A header of its own: the four
-// entries of sage_attn_kernel.h and their switches stay what they are, and only the units sage_attn_d{128,64}_{f8pl,f8plg}.hip include this one.
+// entries of sage_attn_kernel.h and their switches stay what they are, and only the units sage_attn_d{128,64}_{f8pl,f8plg}.hip include this one
+// (and, through sage_attn_lsplit_kernel.h, the units sage_attn_d{128,64}_f8plks.hip: the same entry over SEED forms).
 //
 // The arguments are the step kernel's, argument for argument -- the parameter block, the paged, the ragged and the band operands at their
 // offsets; the lists travel in AttnParams::work_hdr / work_items, which a paged launch leaves free (AttnParams::cu_q stays null: the dense

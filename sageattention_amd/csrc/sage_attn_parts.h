@@ -57,4 +57,12 @@ extern template hipError_t launch_attn_list_units<64, SAGE_STEP_UNITS>(uint32_t,
 extern template hipError_t launch_attn_list_units<128, SAGE_STEP_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
 extern template hipError_t launch_attn_list_units<64, SAGE_STEP_G_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
 
+// pass 2 of the split step call (the list kernels of the seeded packed-group forms, sage_attn_lsplit_kernel.h):
+// sage_attn_d{128,64}_f8plks.hip holds those of the QSTART + GPACK forms of F8KS
+template <int D, AttnUnit... U>
+hipError_t launch_attn_lsplit_units(uint32_t form, const AttnParams &p, const PagedArgs &g, const RaggedArgs &r, const BandArgs &b, int nwork, const AttnLaunchOpts &l);
+#define SAGE_STEP_KS_UNITS UNIT_F8KS
+extern template hipError_t launch_attn_lsplit_units<128, SAGE_STEP_KS_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+extern template hipError_t launch_attn_lsplit_units<64, SAGE_STEP_KS_UNITS>(uint32_t, const AttnParams &, const PagedArgs &, const RaggedArgs &, const BandArgs &, int, const AttnLaunchOpts &);
+
 }  // namespace sage

@@ -6,6 +6,7 @@
 #include "../../include/sage_kvpvarlen_gfx950.h"
 #include "../../include/sage_kvstep_gfx950.h"
 #include "../../include/sage_kvlist_gfx950.h"
+#include "../../include/sage_kvlsplit_gfx950.h"
 #include "sage_common.h"
 #include "sage_kernels.h"
 #include "sage_work_order.h"
@@ -137,6 +138,7 @@ struct AttnCall {
     bool step;                       // sage_kvstep_attn (with ragged): two launches behind band filters, the decode rows packed by GQA group
     bool list; int32_t *list_ws;     // sage_kvlist_attn (with step): the work lists' workspace -- a plan launch in front, the list kernels
     int64_t list_ws_bytes;
+    bool lsplit;                     // sage_kvlsplit_attn (with list): the decode sequences as S chunks -- SAGE_ATTR_KV_SPLIT is required instead of refused
     int is_causal, gran, q_warp, pv_accum, q_dtype, out_dtype;
     float sm_scale_log2, q_premul;
     void *stream; const SageLaunchAttr *attr;
@@ -256,6 +258,73 @@ int kv_split_run(const AttnCall &c, const LaunchAttr &la, const sage::AttnParams
                         "sage_attn_fused_q_pv_f8_kvlens (SAGE_ATTR_KV_SPLIT) merge launch");
 }
 
+// The split step call (sage_kvlsplit_attn) behind the listed call's checks (c, p / v describe the listed call, lp its plan launch):
+// the entry's own checks in the header's order -- the flag, S, no window, the split workspace -- then plan, pass 1, pass 2, merge and the listed
+// chunk launch on the call's stream, no host read in between.  The decode sequences' partials go to the dense workspace of Lq_ws =
+// min(max_seqlen_q, 32) rows per (sequence, head); pass 2 carries that stride in AttnParams::lse_sh, free in a seeded launch.
+int kv_lsplit_run(const AttnCall &c, const LaunchAttr &la, const sage::AttnParams &p0, const sage::AttnVariant &v0, const sage::KvListPlanParams &lp)
+{
+    const char *const e = "sage_kvlsplit_attn";
+    const int S = la.kv_split;
+    SAGE_REQUIRE(la.kv_split_flag, "%s: attr must carry SAGE_ATTR_KV_SPLIT (the unsplit step call is sage_kvlist_attn)", e);
+    SAGE_REQUIRE(S >= 2 && S <= 255, "%s: a chunk count of 2 .. 255 in flags bits 16-23 (got %d)", e, S);
+    SAGE_REQUIRE(la.window == 0, "%s: no window with a split (got %d)", e, la.window);
+    const int lq_ws = sage::step_split_ws_rows(c.Lq), group = c.Hq / c.Hkv;
+    if (const int rc = kv_split_ws_check("sage_kvlsplit_attn: SAGE_ATTR_KV_SPLIT", la.split_ws, la.split_ws_bytes, c.B, c.Hq, lq_ws, c.D, S)) return rc;
+    const long long bound = lp.items_cap;
+    SAGE_REQUIRE(sage::step_split_grid(c.B, S, c.Hkv, group) < (1LL << 31), "%s: grid too large", e);
+    const int tiles = sage::step_split_tiles(c.Lk, S);
+    const int64_t rows = (int64_t)c.B * c.Hq * S * lq_ws;
+    float *chunk_max = static_cast<float *>(la.split_ws);
+    float *lse_part = reinterpret_cast<float *>(static_cast<char *>(la.split_ws) + r128(4 * rows));
+    float *o_part = reinterpret_cast<float *>(static_cast<char *>(la.split_ws) + 2 * r128(4 * rows));
+    const hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    if (la.opts.grid_out != nullptr) *la.opts.grid_out = 0;
+    if (const int rc = check_launch(sage::launch_kv_list_plan(lp, stream), "sage_kvlsplit_attn plan launch")) return rc;
+
+    sage::ChunkMaxLensParams m{};
+    m.q = c.q; m.k = c.k; m.k_scale = c.k_scale; m.out = chunk_max; m.kv_lens = c.kv_lens; m.q_start = la.q_start;
+    m.B = c.B; m.Hq = c.Hq; m.Hkv = c.Hkv; m.group = group; m.Lq = c.Lq; m.Lk = c.Lk; m.D = c.D;
+    m.S = S; m.tiles = tiles; m.nks = p0.nks;
+    m.q_sb = 0; m.q_sh = c.qs.sh; m.q_sl = c.qs.sl; m.k_sb = c.ks.sb; m.k_sh = c.ks.sh; m.k_sl = c.ks.sl;
+    m.sm_scale_log2 = c.sm_scale_log2; m.q_dtype = c.q_dtype; m.causal = 1;
+    if (const int rc = check_launch(sage::launch_chunk_max_lens_ragged(m, *c.paged, *c.ragged, lq_ws, stream), "sage_kvlsplit_attn pass 1 launch")) return rc;
+
+    // pass 2: the listed decode launch over the seeded form, the chunks folded into the kv-head dimension (kv head hk0 * S + chunk); FP32 partials
+    // [B, Hq * S, Lq_ws, D] = [B, Hkv, S, group, Lq_ws, D], LSEs [B, Hq * S, Lq_ws]
+    int grid_d = 0, grid_c = 0;
+    sage::AttnLaunchOpts o = la.opts;
+    const sage::BandArgs decode{0, sage::kStepDecodeRows}, chunk{sage::kStepDecodeRows, c.Lq};
+    {
+        sage::AttnParams p = p0;
+        sage::AttnVariant v = v0;
+        p.Hq = c.Hq * S; p.Hkv = c.Hkv * S; p.kv_split = S; p.kv_base = 64 * tiles;
+        p.o = o_part; p.lse = lse_part; p.lse_sh = lq_ws;
+        p.o_sb = (int64_t)p.Hq * lq_ws * c.D; p.o_sh = (int64_t)lq_ws * c.D; p.o_sl = c.D;
+        p.seed_max = chunk_max; p.seed_chunks = S; p.seed_first = 0;
+        p.sched = nullptr;
+        p.work_hdr = c.list_ws; p.work_items = c.list_ws + sage::kStepHdrWords; p.items_bound = 0;
+        v.seeded = true; v.list = true; v.gqa_pack = true; v.band = &decode; o.grid_out = &grid_d;
+        if (const int rc = check_launch(sage::launch_attention(p, v, o), "sage_kvlsplit_attn pass 2 launch")) return rc;
+    }
+    sage::SplitMergeParams g{};
+    g.o_part = o_part; g.lse_part = lse_part; g.o_tail = nullptr; g.lse_tail = nullptr; g.o_out = c.o; g.lse_out = c.lse;
+    g.B = c.B; g.S = S; g.H = c.Hq; g.L = lq_ws; g.D = c.D; g.group = group;
+    g.o_sb = 0; g.o_sh = c.os.sh; g.o_sl = c.os.sl; g.dtype = c.out_dtype;
+    if (const int rc = check_launch(sage::launch_merge_split_ragged(g, *c.ragged, c.Lq, (long)c.lse_sh, stream), "sage_kvlsplit_attn merge launch")) return rc;
+
+    if (c.Lq > sage::kStepDecodeRows && bound > 0) {
+        // the listed call's chunk launch as that call makes it (hdr + 1: {n_chunk_items, group, fold, left})
+        sage::AttnParams pl = p0;
+        sage::AttnVariant vs = v0;
+        vs.list = true; vs.gqa_pack = false; vs.band = &chunk; o.grid_out = &grid_c;
+        pl.work_hdr = c.list_ws + 1; pl.work_items = c.list_ws + sage::kStepHdrWords + c.B; pl.items_bound = (int)bound;
+        if (const int rc = check_launch(sage::launch_attention(pl, vs, o), "sage_kvlsplit_attn chunk launch")) return rc;
+    }
+    if (la.opts.grid_out != nullptr) *la.opts.grid_out = grid_d + grid_c;
+    return SAGE_OK;
+}
+
 // validates the call, fills the kernel parameter block, launches
 int attn_run(const AttnCall &c)
 {
@@ -282,9 +351,9 @@ int attn_run(const AttnCall &c)
                                              c.D > 0 ? c.D : 0, S)) return rc;
     } else
     if (c.paged != nullptr && c.attr != nullptr && c.attr->struct_bytes >= 8) {
-        const char *const e = c.list ? "sage_kvlist_attn" : c.step ? "sage_kvstep_attn" : c.ragged != nullptr ? "sage_kvpvarlen_attn" : "sage_kvpaged_attn";
+        const char *const e = c.lsplit ? "sage_kvlsplit_attn" : c.list ? "sage_kvlist_attn" : c.step ? "sage_kvstep_attn" : c.ragged != nullptr ? "sage_kvpvarlen_attn" : "sage_kvpaged_attn";
         const unsigned f = c.attr->flags;
-        SAGE_REQUIRE(!(f & (SAGE_ATTR_KV_SPLIT | (0xffu << SAGE_ATTR_KV_SPLIT_SHIFT))),
+        SAGE_REQUIRE(c.lsplit || !(f & (SAGE_ATTR_KV_SPLIT | (0xffu << SAGE_ATTR_KV_SPLIT_SHIFT))),
                      "%s: SAGE_ATTR_KV_SPLIT is not supported on a paged cache (pass 1 and the split's kernels do not look pages up)", e);
         SAGE_REQUIRE(!(f & SAGE_ATTR_FP8_FOLDED_SCORES), "%s: SAGE_ATTR_FP8_FOLDED_SCORES is not supported on a paged cache (the exact score form only)", e);
         SAGE_REQUIRE(!(f & SAGE_ATTR_FORCE_PERSISTENT), "%s: SAGE_ATTR_FORCE_PERSISTENT is not supported on a paged cache (the ordinary dispatch only)", e);
@@ -294,11 +363,12 @@ int attn_run(const AttnCall &c)
     if (const int rc = read_attr(c.attr, c.stream, c.mask == nullptr && !split && c.paged == nullptr, la)) return rc;     // (masked, split and paged launches take no launch workspace)
     // (packed query rows: the offsets place every sample's rows, so they are required -- the bottom-right ones are the caller's kv_lens[b] - Lq_b)
     SAGE_REQUIRE(c.ragged == nullptr || la.q_start != nullptr, "%s: SageLaunchAttr.q_start is required (int32 [B]: the key position of each sample's row 0)",
-                 c.list ? "sage_kvlist_attn" : c.step ? "sage_kvstep_attn" : "sage_kvpvarlen_attn");
+                 c.lsplit ? "sage_kvlsplit_attn" : c.list ? "sage_kvlist_attn" : c.step ? "sage_kvstep_attn" : "sage_kvpvarlen_attn");
     // ---- the routes a Q form admits
     if (c.kv_lens == nullptr) SAGE_REFUSE_KV_SPLIT(la);
-    SAGE_REQUIRE(la.kv_split_flag || la.kv_split == 0, "SAGE_ATTR_KV_SPLIT: a chunk count (%d in flags bits 16-23) without the bit", la.kv_split);
-    SAGE_REQUIRE(!la.kv_split_flag || (la.kv_split >= 2 && c.Lq <= 128 && la.window == 0 && !la.opts.fp8_folded),
+    // (sage_kvlsplit_attn checks the bit, the count and the window by its own name behind the listed call's checks, below)
+    SAGE_REQUIRE(c.lsplit || la.kv_split_flag || la.kv_split == 0, "SAGE_ATTR_KV_SPLIT: a chunk count (%d in flags bits 16-23) without the bit", la.kv_split);
+    SAGE_REQUIRE(c.lsplit || !la.kv_split_flag || (la.kv_split >= 2 && c.Lq <= 128 && la.window == 0 && !la.opts.fp8_folded),
                  "SAGE_ATTR_KV_SPLIT: a chunk count of 2 .. 255 in flags bits 16-23 (got %d), Lq <= 128 (got %d), no window (got %d) and the exact score form only",
                  la.kv_split, c.Lq, la.window);
     // (pass 2 would add the mean to every chunk's partial, and a row without a visible key would merge to 0 where the unsplit kernel gives the mean)
@@ -382,11 +452,11 @@ int attn_run(const AttnCall &c)
     // FP16 PV: the kernel's TWO_LEVEL parameter selects the Triton kernel form (true) or the CUDA kernel form (false)
     v.two_level = fp8 ? c.pv_accum == SAGE_PV_ACCUM_TWO_LEVEL : c.pv_accum == SAGE_PV_ACCUM_TRITON;
     v.qf = int8q ? 0 : sage::attn_qf(per_block, c.q_dtype);
-    if (la.kv_split_flag) return kv_split_run(c, la, p, v);
+    if (la.kv_split_flag && !c.lsplit) return kv_split_run(c, la, p, v);
     if (c.list) {
         // the listed step call: the step call's two launches behind a plan launch, their items from its lists (sage_step_list.h) -- the workspace
         // checks first, the last of the entry's; then plan, decode, chunk on the call's stream, no host read in between
-        const char *const e = "sage_kvlist_attn";
+        const char *const e = c.lsplit ? "sage_kvlsplit_attn" : "sage_kvlist_attn";
         const int total_q = c.ragged->total_q;
         const long long need = 4 * sage::step_ws_words(c.B, total_q, c.Lq), bound = sage::step_chunk_bound(c.B, total_q, c.Lq);
         SAGE_REQUIRE(c.list_ws != nullptr && (reinterpret_cast<uintptr_t>(c.list_ws) & 3u) == 0, "%s: list_ws must be int32 device memory, 4-byte aligned (got %p)", e, (void *)c.list_ws);
@@ -397,6 +467,7 @@ int attn_run(const AttnCall &c)
         lp.cu_q = c.ragged->cu_q; lp.kv_lens = c.kv_lens; lp.q_start = la.q_start;
         lp.B = c.B; lp.total_q = total_q; lp.max_seqlen_q = c.Lq; lp.Lk = c.Lk; lp.window = la.window;
         lp.Hq = c.Hq; lp.Hkv = c.Hkv; lp.head_dim = c.D; lp.items_cap = (int)bound; lp.ws = c.list_ws;
+        if (c.lsplit) return kv_lsplit_run(c, la, p, v, lp);
         if (la.opts.grid_out != nullptr) *la.opts.grid_out = 0;
         if (const int rc = check_launch(sage::launch_kv_list_plan(lp, static_cast<hipStream_t>(c.stream)), "sage_kvlist_attn plan launch")) return rc;
         int grid_d = 0, grid_c = 0;
@@ -1317,6 +1388,51 @@ SAGE_KVLIST_API int sage_kvlist_attn(const void *q, const int8_t *k_int8, const 
     c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
     c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g; c.ragged = &r;
     c.step = true; c.list = true; c.list_ws = list_ws; c.list_ws_bytes = list_ws_bytes;
+    c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.Lk = max_pages_per_seq * page_size; c.D = D;
+    c.qs = {0, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {0, o_sh, o_sl}; c.lse_sh = lse_sh;
+    c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;
+    return attn_run(c);
+}
+
+// sage_kvlist_attn with every decode sequence as S key-range chunks, exactly (include/sage_kvlsplit_gfx950.h)
+SAGE_KVLSPLIT_API int sage_kvlsplit_abi_version(void) { return SAGE_KVLSPLIT_ABI_VERSION; }
+
+SAGE_KVLSPLIT_API int64_t sage_kvlsplit_ws_bytes(int B, int Hq, int max_seqlen_q, int D, int S)
+{
+    if (B < 1 || Hq < 1 || max_seqlen_q < 1 || (D != 64 && D != 128) || S < 2 || S > 255)
+        return sage::set_last_error(SAGE_EINVAL, "sage_kvlsplit_ws_bytes: B, Hq and max_seqlen_q at least 1, D 64 or 128, S in 2 .. 255 (got %d, %d, %d, %d, %d)", B, Hq, max_seqlen_q, D, S);
+    return kv_split_ws_bytes(B, Hq, sage::step_split_ws_rows(max_seqlen_q), D, S);
+}
+
+SAGE_KVLSPLIT_API int sage_kvlsplit_attn(const void *q, const int8_t *k_int8, const void *v_image, void *o, float *lse,
+                                     const float *k_scale, const float *v_scale, const int32_t *kv_lens, const int32_t *cu_seqlens_q,
+                                     const int32_t *block_table, int64_t bt_stride, int num_pages, int page_size, int max_pages_per_seq,
+                                     int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int D,
+                                     int64_t q_sl, int64_t q_sh, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+                                     int64_t o_sl, int64_t o_sh, int64_t lse_sh,
+                                     int is_causal, float sm_scale_log2, int q_dtype, int out_dtype, void *stream, const SageLaunchAttr *attr,
+                                     int32_t *list_ws, int64_t list_ws_bytes)
+{
+    const char *const e = "sage_kvlsplit_attn";
+    SAGE_REQUIRE(q && k_int8 && v_image && o && k_scale && v_scale, "%s: null tensor pointer (only lse may be null)", e);
+    SAGE_REQUIRE(kv_lens, "%s: null kv_lens", e);
+    SAGE_REQUIRE(cu_seqlens_q, "%s: null cu_seqlens_q", e);
+    sage::PagedArgs g;
+    if (const int rc = sage::paged_args(e, block_table, bt_stride, num_pages, page_size, max_pages_per_seq, g)) return rc;
+    if (const int rc = sage::kv_check_batch(e, B, Hkv)) return rc;
+    if (const int rc = sage::paged_check_table_aligned(e, block_table)) return rc;
+    SAGE_REQUIRE((reinterpret_cast<uintptr_t>(cu_seqlens_q) & 3u) == 0, "%s: cu_seqlens_q must be 4-byte aligned", e);
+    SAGE_REQUIRE(total_q >= 1 && max_seqlen_q >= 1, "%s: total_q and max_seqlen_q must be at least 1 (got %d, %d)", e, total_q, max_seqlen_q);
+    SAGE_REQUIRE(is_causal == 1, "%s: is_causal must be 1 (packed query rows are placed by their offsets; got %d)", e, is_causal);
+    SAGE_REQUIRE(Hq >= 1 && (int64_t)B * Hq * ((max_seqlen_q + 127) / 128) < ((int64_t)1 << 31), "%s: B * Hq * ceil(max_seqlen_q / 128) must be in [1, 2^31) (got %d, %d, %d)",
+                 e, B, Hq, max_seqlen_q);
+    SAGE_REQUIRE(lse == nullptr || lse_sh >= total_q, "%s: lse is [Hq, total_q]: its head stride lse_sh must be at least total_q (got %lld)", e, (long long)lse_sh);
+    SAGE_REQUIRE(Hq / Hkv >= 2, "%s: Hq / Hkv must be at least 2, no GQA group to pack (got Hq %d, Hkv %d; sage_kvpvarlen_attn takes such a call)", e, Hq, Hkv);
+    const sage::RaggedArgs r{cu_seqlens_q, total_q};
+    AttnCall c{};
+    c.q_form = Q_FUSED_THREAD; c.pv_fp8 = true; c.pv_accum = SAGE_PV_ACCUM_TWO_LEVEL;
+    c.q = q; c.k = k_int8; c.v = v_image; c.o = o; c.lse = lse; c.k_scale = k_scale; c.v_scale = v_scale; c.kv_lens = kv_lens; c.paged = &g; c.ragged = &r;
+    c.step = true; c.list = true; c.lsplit = true; c.list_ws = list_ws; c.list_ws_bytes = list_ws_bytes;
     c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Lq = max_seqlen_q; c.Lk = max_pages_per_seq * page_size; c.D = D;
     c.qs = {0, q_sh, q_sl}; c.ks = {k_sb, k_sh, k_sl}; c.os = {0, o_sh, o_sl}; c.lse_sh = lse_sh;
     c.is_causal = is_causal; c.sm_scale_log2 = sm_scale_log2; c.q_dtype = q_dtype; c.out_dtype = out_dtype; c.stream = stream; c.attr = attr;

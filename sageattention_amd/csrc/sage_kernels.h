@@ -334,6 +334,9 @@ struct SplitMergeParams {
 hipError_t launch_merge_split(const SplitMergeParams &p, hipStream_t stream);
 // the same merge over FP32 partials (o_part, o_tail: float; the exact split's pass 2 writes them)
 hipError_t launch_merge_split_f32(const SplitMergeParams &p, hipStream_t stream);
+// ... for the decode sequences of a step alone (the split step call): FP32 partials [B, Hkv, S, group, L] with L = min(max_seqlen_q, 32),
+// the results packed behind r -- o_out [total_q, H, D] (o_sl / o_sh), lse_out [H, total_q] (lse_sh); other sequences and rows are not touched
+hipError_t launch_merge_split_ragged(const SplitMergeParams &p, const RaggedArgs &r, int max_seqlen_q, long lse_sh, hipStream_t stream);
 
 // ---- the exact split's pass 1: per (batch, query head, query row, chunk) the row maximum the attention kernel forms over the chunk's keys ---------
 struct ChunkMaxParams {
@@ -371,6 +374,9 @@ struct ChunkMaxLensParams {
 hipError_t launch_chunk_max_lens(const ChunkMaxLensParams &p, hipStream_t stream);
 // ... over a paged cache (sage_split_paged.hip): k / k_scale / k_sb / Hkv / nks describe the pool of pages, Lk is the logical capacity, g the table
 hipError_t launch_chunk_max_lens_paged(const ChunkMaxLensParams &p, const PagedArgs &g, hipStream_t stream);
+// ... for the decode sequences of a step (sage_split_ragged.hip): Lq = max_seqlen_q, q packed behind r (q_sl the row stride), causal; out is
+// [B, Hkv, S, group, lq_ws] with lq_ws = min(max_seqlen_q, 32), written for the rows of the sequences of 1 .. 32 rows alone
+hipError_t launch_chunk_max_lens_ragged(const ChunkMaxLensParams &p, const PagedArgs &g, const RaggedArgs &r, int lq_ws, hipStream_t stream);
 
 // ---- the C ABI's error channel for entry points defined outside sage_cabi.hip (sage_kv_cache.hip): stores the thread-local message that
 // sage_last_error() returns and hands `code` back

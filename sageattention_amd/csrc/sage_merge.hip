@@ -10,6 +10,8 @@
 // 32 B of accumulator + 16 B of new output in, 32 B (+16 B on the last step) out.
 #include "sage_common.h"
 #include "sage_kernels.h"
+#include "sage_ragged.h"
+#include "sage_step_list.h"
 
 namespace sage {
 
@@ -99,6 +101,38 @@ __device__ __forceinline__ void ld_part8(const PT *src, float (&x)[8])
     }
 }
 
+// One row of the merge, 8 channels of it: the S partials la[s * HL] / oa[s * HL * D ..] (HL: the chunk stride in rows), an optional tail (ot
+// non-null) with LSE lt (-inf without one); the merged channels go to oo, the row's LSE to *lo if lo is non-null.  The arithmetic both merge
+// kernels run: the maximum over the LSEs, exp2 of the differences, a chunk of LSE -inf skipped, the sum in the order s = 0 .. S - 1 (tail last),
+// one reciprocal, m + log2(wsum).
+template <int DT, typename PT>
+__device__ __forceinline__ void merge_split_row(const float *la, const PT *oa, long HL, int S, int D, const PT *ot, float lt, uint16_t *oo, float *lo)
+{
+    const bool tail = ot != nullptr;
+    float m = lt;
+    for (int s = 0; s < S; s++) m = fmaxf(m, la[(long)s * HL]);
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, wsum = 0.0f;
+    auto add = [&](const PT *src, float lse) {
+        if (lse == -INFINITY) return;                       // chunk with no visible key for this row
+        const float w = __builtin_amdgcn_exp2f(lse - m);
+        float x[8];
+        ld_part8(src, x);
+#pragma unroll
+        for (int j = 0; j < 8; j++) acc[j] += w * x[j];
+        wsum += w;
+    };
+    if (m != -INFINITY) {
+        for (int s = 0; s < S; s++) add(oa + (long)s * HL * D, la[(long)s * HL]);
+        if (tail) add(ot, lt);
+    }
+    const float inv = wsum > 0.0f ? 1.0f / wsum : 0.0f;
+    v4u pk;
+#pragma unroll
+    for (int w = 0; w < 4; w++) pk[w] = (unsigned)st16<DT>(acc[2 * w] * inv) | ((unsigned)st16<DT>(acc[2 * w + 1] * inv) << 16);
+    *reinterpret_cast<v4u *>(oo) = pk;
+    if (lo != nullptr) *lo = wsum > 0.0f ? m + __builtin_amdgcn_logf(wsum) : -INFINITY;   // v_log_f32 = log2
+}
+
 template <int DT, typename PT>
 __global__ void __launch_bounds__(256)
 merge_split_kernel(const SplitMergeParams p)
@@ -119,29 +153,38 @@ merge_split_kernel(const SplitMergeParams p)
     const PT *oa = reinterpret_cast<const PT *>(p.o_part) + r0 * p.D + c8;
     const bool tail = p.o_tail != nullptr;
     const float lt = tail ? p.lse_tail[row] : -INFINITY;
-    float m = lt;
-    for (int s = 0; s < p.S; s++) m = fmaxf(m, la[(long)s * HL]);
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, wsum = 0.0f;
-    auto add = [&](const PT *src, float lse) {
-        if (lse == -INFINITY) return;                       // chunk with no visible key for this row
-        const float w = __builtin_amdgcn_exp2f(lse - m);
-        float x[8];
-        ld_part8(src, x);
-#pragma unroll
-        for (int j = 0; j < 8; j++) acc[j] += w * x[j];
-        wsum += w;
-    };
-    if (m != -INFINITY) {
-        for (int s = 0; s < p.S; s++) add(oa + (long)s * HL * p.D, la[(long)s * HL]);
-        if (tail) add(reinterpret_cast<const PT *>(p.o_tail) + row * p.D + c8, lt);
-    }
-    const float inv = wsum > 0.0f ? 1.0f / wsum : 0.0f;
     uint16_t *oo = reinterpret_cast<uint16_t *>(p.o_out) + (long)b * p.o_sb + (long)h * p.o_sh + (long)l * p.o_sl + c8;
-    v4u pk;
-#pragma unroll
-    for (int w = 0; w < 4; w++) pk[w] = (unsigned)st16<DT>(acc[2 * w] * inv) | ((unsigned)st16<DT>(acc[2 * w + 1] * inv) << 16);
-    *reinterpret_cast<v4u *>(oo) = pk;
-    if (p.lse_out != nullptr && c8 == 0) p.lse_out[row] = wsum > 0.0f ? m + __builtin_amdgcn_logf(wsum) : -INFINITY;   // v_log_f32 = log2
+    merge_split_row<DT, PT>(la, oa, HL, p.S, p.D, tail ? reinterpret_cast<const PT *>(p.o_tail) + row * p.D + c8 : nullptr, lt, oo,
+                            (p.lse_out != nullptr && c8 == 0) ? p.lse_out + row : nullptr);
+}
+
+// ---- the split step call's merge: the same rows, for the DECODE sequences of a step alone -------------------------------------
+// The partials are the dense workspace of the call -- lse_part [B, Hkv, S, group, L], o_part [.., D] (FP32) with L = min(max_seqlen_q, 32) rows
+// per (sequence, head) -- and the results are packed: row l of sequence b lies at packed row first_b + l of o [total_q, H, D] (o_sl / o_sh) and of
+// lse [H, total_q] (lse_sh).  One thread owns 8 channels of workspace row (b, h, l); ragged_band with the band (0, 32] decides: a sequence
+// outside the band and a row at or beyond n_b are not touched.
+template <int DT>
+__global__ void __launch_bounds__(256)
+merge_split_ragged_kernel(const SplitMergeParams p, const RaggedArgs ra, const int max_seqlen_q, const long lse_sh)
+{
+    const int cpr = p.D / 8;
+    const int cpr_pad = p.cpr_pad;
+    const long row = (long)blockIdx.x * (256 / cpr_pad) + threadIdx.x / cpr_pad;
+    const int c = threadIdx.x % cpr_pad;
+    if (row >= (long)p.B * p.H * p.L || c >= cpr) return;
+    const int c8 = c * 8;
+    const int l = (int)(row % p.L);
+    const long bh = row / p.L;
+    const int h = (int)(bh % p.H), b = (int)(bh / p.H);
+    int first, nb;
+    ragged_band(ra.cu_q[b], ra.cu_q[b + 1], ra.total_q, max_seqlen_q, 0, kStepDecodeRows, first, nb);
+    if (l >= nb) return;
+    const int hk = h / p.group, gq = h - hk * p.group;
+    const long HL = (long)p.group * p.L;                                              // chunk stride in rows
+    const long r0 = step_split_ws_row(b, hk, 0, gq, l, p.H / p.group, p.S, p.group, p.L);    // row of chunk 0
+    uint16_t *oo = reinterpret_cast<uint16_t *>(p.o_out) + (long)(first + l) * p.o_sl + (long)h * p.o_sh + c8;
+    merge_split_row<DT, float>(p.lse_part + r0, reinterpret_cast<const float *>(p.o_part) + r0 * p.D + c8, HL, p.S, p.D, nullptr, -INFINITY, oo,
+                               (p.lse_out != nullptr && c8 == 0) ? p.lse_out + (long)h * lse_sh + first + l : nullptr);
 }
 
 template <typename PT>
@@ -162,6 +205,23 @@ static hipError_t merge_split(const SplitMergeParams &p, hipStream_t stream)
 
 hipError_t launch_merge_split(const SplitMergeParams &p, hipStream_t stream) { return merge_split<uint16_t>(p, stream); }
 hipError_t launch_merge_split_f32(const SplitMergeParams &p, hipStream_t stream) { return merge_split<float>(p, stream); }
+
+// p: o_part / lse_part the workspace (L = its rows per (sequence, head)), o_out / lse_out the packed results (o_sl / o_sh; o_sb unused)
+hipError_t launch_merge_split_ragged(const SplitMergeParams &p, const RaggedArgs &r, int max_seqlen_q, long lse_sh, hipStream_t stream)
+{
+    const long rows = (long)p.B * p.H * p.L;
+    if (rows <= 0) return hipSuccess;
+    if (r.cu_q == nullptr || r.total_q < 1 || p.L != step_split_ws_rows(max_seqlen_q) || p.o_tail != nullptr) return hipErrorInvalidValue;
+    SplitMergeParams q = p;
+    q.cpr_pad = 1;
+    while (q.cpr_pad < p.D / 8) q.cpr_pad *= 2;
+    if (q.cpr_pad > 64) return hipErrorInvalidValue;
+    const long rpb = 256 / q.cpr_pad;
+    const dim3 grid((unsigned)((rows + rpb - 1) / rpb));
+    if (p.dtype == DT_F16) hipLaunchKernelGGL(merge_split_ragged_kernel<DT_F16>, grid, dim3(256), 0, stream, q, r, max_seqlen_q, lse_sh);
+    else hipLaunchKernelGGL(merge_split_ragged_kernel<DT_BF16>, grid, dim3(256), 0, stream, q, r, max_seqlen_q, lse_sh);
+    return hipGetLastError();
+}
 
 hipError_t launch_merge_states(const MergeParams &p, hipStream_t stream)
 {

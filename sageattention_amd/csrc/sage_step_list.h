@@ -175,4 +175,50 @@ SAGE_STEP_HD inline void step_plan_serial(const int *cu_q, const int *kv_lens, c
     }
 }
 
+// ---- the split step call (include/sage_kvlsplit_gfx950.h): every decode sequence as S key-range chunks ------------------------
+// A chunk is T whole 64-key tiles of the LOGICAL key axis (3.20's rule): T = ceil(ceil(Lk / 64) / S), the same for every sequence of the call.
+SAGE_STEP_HD inline int step_split_tiles(int Lk, int S)
+{
+    const long long nt = ((long long)(Lk > 0 ? Lk : 0) + 63) >> 6;
+    return S > 0 ? (int)((nt + S - 1) / S) : 0;
+}
+// the rows per (sequence, head) of the split workspace: what a decode sequence can have under this max_seqlen_q
+SAGE_STEP_HD inline int step_split_ws_rows(int max_seqlen_q) { return max_seqlen_q < kStepDecodeRows ? (max_seqlen_q > 0 ? max_seqlen_q : 0) : kStepDecodeRows; }
+// pass 2's grid: units (decode-list rank r, chunk c, kv head hk), u = (r * S + c) * Hkv + hk, in whole octets, ceil(group / 4) blocks each
+SAGE_STEP_HD inline long long step_split_grid(int B, int S, int Hkv, int group) { return 8 * (((long long)B * S * Hkv + 7) / 8) * ((group + 3) / 4); }
+
+// Workgroup `bid` of that grid: the units go to the XCDs round-robin by 3.23's decode rule -- unit = (idx / ngb) * 8 + xcd with xcd = bid & 7,
+// idx = bid >> 3 -- so the ngb = ceil(group / 4) blocks of a unit stay on one XCD.  nd: the decode list's count, clamped to [0, B] by the caller.
+// False for a workgroup past the last unit; else r < nd, c < S, hk < Hkv, gb < ngb.  (S, Hkv, group >= 1.)
+SAGE_STEP_HD inline bool step_split_item(int bid, int nd, int S, int Hkv, int group, int &r, int &c, int &hk, int &gb)
+{
+    const int ngb = (group + 3) >> 2;
+    const int xcd = bid & 7, idx = bid >> 3;
+    const int uj = idx / ngb;
+    gb = idx - uj * ngb;
+    const long long unit = (long long)uj * 8 + xcd;
+    if (bid < 0 || unit >= (long long)nd * S * Hkv) return false;
+    const int rc = (int)(unit / Hkv);
+    hk = (int)(unit - (long long)rc * Hkv);
+    r = rc / S;
+    c = rc - r * S;
+    return true;
+}
+
+// the logical tiles chunk c of a sequence of `len` keys (clamped to [0, Lk] by the caller) may read: [t0, t1) = [c T, min((c + 1) T,
+// ceil(len / 64))), empty (t1 <= t0) for a chunk at or behind ceil(len / 64) -- the only table entries a chunk's kernels look up
+SAGE_STEP_HD inline void step_split_tile_range(int c, int T, int len, int &t0, int &t1)
+{
+    const long long a = (long long)c * T, e = a + T, nt = ((long long)(len > 0 ? len : 0) + 63) >> 6;
+    t0 = (int)(a < 0x7fffffff ? a : 0x7fffffff);
+    t1 = (int)(e < nt ? e : nt);
+    if (t1 < t0) t1 = t0;
+}
+
+// row (b, kv head hk, chunk c, head gq of the group, row l) of chunk_max / lse_part [B, Hkv, S, group, lq_ws]; o_part holds D floats per row
+SAGE_STEP_HD inline long long step_split_ws_row(int b, int hk, int c, int gq, int l, int Hkv, int S, int group, int lq_ws)
+{
+    return ((((long long)b * Hkv + hk) * S + c) * group + gq) * lq_ws + l;
+}
+
 }  // namespace sage

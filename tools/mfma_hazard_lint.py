@@ -52,6 +52,9 @@ UNITS_PAGED_RAGGED = ("sage_attn_d128_f8pr.hip", "sage_attn_d64_f8pr.hip")
 UNITS_PAGED_STEP = ("sage_attn_d128_f8pb.hip", "sage_attn_d64_f8pb.hip", "sage_attn_d128_f8pbg.hip", "sage_attn_d64_f8pbg.hip")
 # the listed step call's kernels (sage_attn_paged_list_kernel: the step kernels over device-built work lists), four kernels each; a list of their own likewise
 UNITS_PAGED_LIST = ("sage_attn_d128_f8pl.hip", "sage_attn_d64_f8pl.hip", "sage_attn_d128_f8plg.hip", "sage_attn_d64_f8plg.hip")
+# the split step call's pass 2 (sage_attn_paged_list_kernel over the seeded packed-group forms: a decode sequence as key-range chunks), two kernels
+# each; a list of their own likewise
+UNITS_PAGED_LIST_SPLIT = ("sage_attn_d128_f8plks.hip", "sage_attn_d64_f8plks.hip")
 NEED = {"v_mfma_f32_32x32x64_f8f6f4": 19, "v_mfma_scale_f32_32x32x64_f8f6f4": 19}        # 16 passes; everything else used here: 8 passes
 NEED_DEFAULT = 11
 PASSES = {k: 16 for k in NEED}
@@ -207,7 +210,7 @@ def lint(asm_text):
 
 
 def main(argv):
-    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW + UNITS_PACKED_BR + UNITS_PACKED_WINDOW + UNITS_GQA_PACK + UNITS_KV_SPLIT + UNITS_PAGED + UNITS_PAGED_SPLIT + UNITS_PAGED_RAGGED + UNITS_PAGED_STEP + UNITS_PAGED_LIST
+    units = argv or UNITS + UNITS_PAIR + UNITS_WINDOW + UNITS_PACKED_BR + UNITS_PACKED_WINDOW + UNITS_GQA_PACK + UNITS_KV_SPLIT + UNITS_PAGED + UNITS_PAGED_SPLIT + UNITS_PAGED_RAGGED + UNITS_PAGED_STEP + UNITS_PAGED_LIST + UNITS_PAGED_LIST_SPLIT
     total = 0
     for u in units:
         f, n = lint(listing(u))
