@@ -373,14 +373,20 @@ def test_a_give_up_reroutes_the_device_to_the_kernel_sequence():
     assert quant.prepass_fused_ok(k)
 
 
-def _cu_mask_stream(ncus_lo, ncus_hi):
-    """A torch stream restricted to compute units [ncus_lo, ncus_hi) of XCD-interleaved numbering (hipExtStreamCreateWithCUMask)."""
+_XCDS = 8       # of an MI355X: compute unit c of the XCD-interleaved numbering is unit c // 8 of XCD c % 8
+
+
+def _cu_mask_stream(cus):
+    """A torch stream restricted to the compute units `cus` of XCD-interleaved numbering (hipExtStreamCreateWithCUMask).  Where the
+    MI355X is passed through to a virtual machine the runtime refuses (hipErrorOutOfMemory) a mask that leaves an XCD without a compute
+    unit, so every mask here has one in each."""
     import ctypes
     hip = ctypes.CDLL("libamdhip64.so")
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    assert {c % _XCDS for c in cus} == set(range(_XCDS)) and max(cus) < ncu, cus
     words = (ncu + 31) // 32
     mask = (ctypes.c_uint32 * words)()
-    for c in range(ncus_lo, ncus_hi):
+    for c in cus:
         mask[c // 32] |= 1 << (c % 32)
     st = ctypes.c_void_p()
     rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(st), ctypes.c_uint32(words), mask)
@@ -402,14 +408,20 @@ def test_compute_units_held_by_another_stream_cost_time_not_correctness():
     torch.cuda.synchronize()
     guard = quant._PrepassGuard.of(k.device)
     guard.reset()
-    s8, h8, hip = _cu_mask_stream(0, 8)
-    s6, h6, _ = _cu_mask_stream(0, 6)
+    s8, h8, hip = _cu_mask_stream(range(8))
+    # six of those eight, and for the two XCDs left a compute unit each that s8 cannot use (the second unit of XCDs 6 and 7)
+    s6, h6, _ = _cu_mask_stream([0, 1, 2, 3, 4, 5, _XCDS + 6, _XCDS + 7])
     try:
         with torch.cuda.stream(s8):
             assert quant.prepass_fused_ok(k) and int(lib.sage_prepass_max_seqlen_stream(s8.cuda_stream)) == 8 * 512
             assert not quant.prepass_fused_ok(_mk(1, 1, 8192, 128, torch.bfloat16, "HND", 1)[0])     # 16 slabs: the sequence, by the stream-aware bound
-        # two 1024-thread workgroups fill a compute unit's wave slots: 12 of them hold the six units for 2.5 s
-        assert lib.sage_debug_spin(2500, 12, s6.cuda_stream) == 0
+            # a stream's first call zeroes its sync buffer: behind the spinner that one-workgroup launch would wait for a held compute
+            # unit, and the pre-pass after it would meet none held
+            assert torch.equal(sa.sageattn(q, k, v, is_causal=True), want)
+        s8.synchronize()
+        assert quant.prepass_fused_ok(k)                       # undisturbed, that call's pre-pass did not give up
+        # two 1024-thread workgroups fill a compute unit's wave slots: 16 of them hold the spinner's eight units, six of them s8's, for 2.5 s
+        assert lib.sage_debug_spin(2500, 16, s6.cuda_stream) == 0
         with torch.cuda.stream(s8):
             first = sa.sageattn(q, k, v, is_causal=True)
         s8.synchronize()
@@ -422,7 +434,7 @@ def test_compute_units_held_by_another_stream_cost_time_not_correctness():
         assert torch.equal(first, want), "a pre-pass that could not get its head resident must still be right"
         REPORT_TRIPPED.append(guard.tripped)
         if guard.tripped:                                      # the contention did bite (it does on an otherwise idle MI355X)
-            assert len([x for x in w if "kernel sequence from now on" in str(x.message)]) == 1
+            assert len([x for x in w if "take the kernel sequence for the next" in str(x.message)]) == 1, [str(x.message) for x in w]
         assert torch.equal(second, want) and torch.equal(third, want)
     finally:
         torch.cuda.synchronize()
