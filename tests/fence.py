@@ -10,9 +10,10 @@ allocator put next to the buffer -- invisible on random data.  Under the fence
   * the guards -- and the body of an ``empty`` -- hold the fill byte: ``0xFF`` (NaN as fp16 / bf16 / fp32 / e4m3, -1 as int8 / int32) or ``0x5A``
     (finite; the pattern of the allocator soak test).  A stray store changes a guard byte (``check()`` fails); a stray load that is used reads
     NaN under one fill and a finite value under the other, so the result differs between the fills, or from the unfenced run;
-  * ``GUARD`` is 64 KiB: more than two pipeline stages of the largest instantiation -- a K tile of 8 KiB plus an fp16 V image tile of 16 KiB,
+  * ``GUARD``, the default guard, is 64 KiB: more than two pipeline stages of the largest instantiation -- a K tile of 8 KiB plus an fp16 V image tile of 16 KiB,
     two tiles ahead = 48 KiB -- so any stray access of the prefetch distance the loops use lands inside it; a multiple of 128, so the body keeps
-    the 128-byte alignment that the ticket workspace needs.
+    the 128-byte alignment that the ticket workspace needs.  ``Fence(fill, guard=...)`` takes another size for kernels with larger stages
+    (tests/test_gpu_fence_wide.py).
 
 CPU allocations, zero-sized ones, anything under graph capture and any call with arguments the fence does not model (``out=``, pinned memory,
 a non-strided layout) pass through untouched.  What torch allocates itself (``F.pad``, ``.contiguous()``, ``.to()``, arithmetic) is not fenced.
@@ -41,13 +42,13 @@ class FenceViolation(AssertionError):
 
 class _Arena:
     """One allocation: ``arena`` (uint8) = pad | guard | body | guard; ``lo`` is the body's byte offset inside it."""
-    __slots__ = ("arena", "lo", "nbytes", "shape", "dtype", "site", "func", "in_pkg", "kind", "gap")
+    __slots__ = ("arena", "lo", "nbytes", "shape", "dtype", "site", "func", "in_pkg", "kind", "gap", "guard")
 
     def describe(self):
         return f"{self.kind} {tuple(self.shape)} {str(self.dtype).replace('torch.', '')} allocated at {self.site}"
 
     def guards(self):
-        return (("below", self.arena[self.lo - GUARD:self.lo]), ("above", self.arena[self.lo + self.nbytes:self.lo + self.nbytes + GUARD]))
+        return (("below", self.arena[self.lo - self.guard:self.lo]), ("above", self.arena[self.lo + self.nbytes:self.lo + self.nbytes + self.guard]))
 
 
 def _is_cuda(dev: torch.device) -> bool:
@@ -78,11 +79,14 @@ def _shape_of(size):
 
 class Fence:
     """``with Fence(fill) as f: out = call(f.input(q), ...); f.check()`` -- see the module docstring.  ``device_ok``: which devices are fenced
-    (the default: CUDA; the CPU self-tests of this helper pass ``lambda d: True``)."""
+    (the default: CUDA; the CPU self-tests of this helper pass ``lambda d: True``).  ``guard``: the bytes of each guard region (the default:
+    ``GUARD``), a multiple of ``ALIGN``; kernels whose pipeline stages are larger than the default covers are fenced with their own."""
 
-    def __init__(self, fill: int, device_ok=_is_cuda):
+    def __init__(self, fill: int, device_ok=_is_cuda, *, guard: int = GUARD):
         assert 0 <= fill <= 0xFF
+        assert guard > 0 and guard % ALIGN == 0, "the guard is a positive multiple of ALIGN: the body keeps its alignment"
         self.fill = int(fill)
+        self.guard = int(guard)
         self.device_ok = device_ok
         self.arenas = []
         self._saved = None
@@ -137,11 +141,11 @@ class Fence:
         for s in shape:
             numel *= s
         nbytes = numel * dtype.itemsize
-        raw = e(ALIGN + 2 * GUARD + nbytes, dtype=torch.uint8, device=dev)
+        raw = e(ALIGN + 2 * self.guard + nbytes, dtype=torch.uint8, device=dev)
         raw.fill_(self.fill)
         r = _Arena()
-        r.arena, r.nbytes, r.shape, r.dtype, r.kind, r.gap = raw, nbytes, tuple(shape), dtype, kind, None
-        r.lo = (-raw.data_ptr()) % ALIGN + GUARD
+        r.arena, r.nbytes, r.shape, r.dtype, r.kind, r.gap, r.guard = raw, nbytes, tuple(shape), dtype, kind, None, self.guard
+        r.lo = (-raw.data_ptr()) % ALIGN + self.guard
         r.site, r.func, r.in_pkg = _site()
         body = raw[r.lo:r.lo + nbytes]
         if zero:
@@ -240,7 +244,7 @@ class Fence:
                     idx = bad.nonzero().flatten()
                     first, last = int(idx[0]), int(idx[-1])
                     if side == "below":
-                        first, last = first - GUARD, last - GUARD
+                        first, last = first - r.guard, last - r.guard
                     problems.append(f"{r.describe()}: {int(idx.numel())} guard byte(s) {side} the buffer changed, "
                                     f"first at {first:+d}, last at {last:+d} (fill 0x{self.fill:02X})")
             if r.gap is not None:

@@ -128,6 +128,37 @@ def test_check_fails_with_site_side_and_offsets_when_a_guard_byte_changes(fill, 
         del keep
 
 
+@pytest.mark.parametrize("fill", FILLS)
+def test_a_larger_guard_is_laid_out_checked_and_reported_with_its_own_offsets(fill):
+    """``Fence(fill, guard=...)``: 136 KiB, the guard of tests/test_gpu_fence_wide.py.  Both guards have that size, the default fence next to it
+    keeps 64 KiB, and a stray byte just inside the far end of either larger guard -- outside what the default guard covers -- is reported with
+    its offset from the buffer's edge."""
+    from sageattention_amd import ops
+    wide = 2 * (36864 + 32768)
+    assert wide % fence.ALIGN == 0 and wide > GUARD
+    with Fence(fill, device_ok=ANY, guard=wide) as f:
+        assert f.guard == wide and Fence(fill).guard == GUARD
+        lse = ops._lse_alloc(torch.zeros(2, 3, 5, 8), 1, 1)
+        t = f.input(torch.arange(24, dtype=torch.float32).view(2, 3, 4), device="cpu")
+        for x in (lse, t):
+            r = _rec(f, x)
+            (_, lo), (_, hi) = r.guards()
+            assert lo.numel() == hi.numel() == wide and r.lo >= wide and x.data_ptr() % fence.ALIGN == 0
+            assert lo.data_ptr() + wide == x.data_ptr() and hi.data_ptr() == x.data_ptr() + r.nbytes
+            assert r.arena.numel() >= 2 * wide + r.nbytes and bool((lo == fill).all()) and bool((hi == fill).all())
+        f.check()
+        r = _rec(f, lse)
+        for side, at, want in (("above", r.lo + r.nbytes + wide - 1, f"+{wide - 1}"), ("below", r.lo - wide, f"-{wide}")):
+            r.arena[at] = fill ^ 0x80
+            with pytest.raises(FenceViolation) as ei:
+                f.check()
+            msg = str(ei.value)
+            assert "(2, 3, 5) float32" in msg and f"1 guard byte(s) {side} the buffer" in msg and f"first at {want}, last at {want}" in msg, msg
+            assert "(2, 3, 4)" not in msg, "the untouched arena is not blamed"
+            r.arena[at] = fill
+            f.check()
+
+
 @pytest.mark.parametrize("layout", ["HND", "NHD"])
 def test_inputs_with_gap_rows_are_views_whose_gap_is_checked(layout):
     g = torch.Generator().manual_seed(0)

@@ -32,6 +32,11 @@ CASES = [
     (2, 128, [449, 257], 449, BF16, True, None),        # second row block, steady state, position 0 one key short
     (3, 48, [200, 70], 200, F16, True, 0.03),           # 144 rows: a block holds two positions, a limit inside a tile
     (4, 16, [2, 0], 64, BF16, True, None),              # positions in front of key 0 and a keyless sample: exact +0 / -inf
+    (1, 128, [63, 64], 64, BF16, True, None),           # a full block of heads, the last key on either side of the first tile boundary ...
+    (1, 128, [65, 127], 127, F16, True, None),
+    (1, 128, [128, 129], 129, BF16, False, None),       # ... and of the second
+    (8, 16, [200, 70], 200, F16, True, None),           # Lq 8, the documented upper end: one block of eight positions
+    (8, 32, [129, 7], 129, BF16, True, None),           # two blocks; fewer keys than positions: position 0 of sample 1 in front of key 0
 ]
 
 

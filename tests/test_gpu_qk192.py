@@ -35,6 +35,23 @@ CASES = [
     (200, 72, True, 160, 64, (4, 2), "NHD", BF16, False, None),
     (72, 200, True, 192, 128, (4, 2), "HND", BF16, True, None),         # top-left with more keys than rows
     (72, 200, True, 136, 72, (2, 2), "NHD", F16, True, 0.03),
+    (33, 63, False, 192, 128, (2, 2), "NHD", BF16, True, None),         # the last key on either side of the first and the second tile boundary
+    (33, 64, False, 192, 128, (4, 2), "HND", F16, True, None),
+    (33, 65, False, 160, 72, (2, 2), "NHD", F16, False, None),
+    (33, 127, False, 192, 128, (2, 2), "HND", BF16, True, None),
+    (33, 128, False, 192, 128, (4, 2), "NHD", F16, True, None),
+    (33, 129, False, 192, 128, (2, 2), "HND", BF16, False, None),
+    (33, 129, True, 192, 128, (2, 2), "NHD", F16, True, None),
+    (127, 192, False, 192, 128, (2, 2), "HND", F16, True, None),        # the last row on either side of the first and the second block boundary
+    (127, 192, True, 192, 128, (4, 2), "NHD", BF16, True, None),
+    (128, 192, False, 192, 128, (4, 2), "NHD", BF16, True, None),
+    (128, 192, True, 192, 128, (2, 2), "HND", F16, True, None),
+    (255, 192, False, 160, 64, (2, 2), "NHD", F16, True, None),
+    (255, 192, True, 192, 128, (2, 2), "HND", BF16, True, None),
+    (256, 192, False, 192, 128, (2, 2), "HND", BF16, False, None),
+    (256, 192, True, 192, 128, (4, 2), "NHD", F16, True, None),
+    (129, 65, True, 192, 128, (8, 1), "HND", F16, True, None),          # GQA groups of 8 and 4 at the smallest shape with two query blocks
+    (129, 65, False, 192, 128, (8, 2), "NHD", BF16, True, None),
 ]
 
 

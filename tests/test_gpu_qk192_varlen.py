@@ -30,6 +30,12 @@ CASES = [
     ([(129, 192), (0, 70), (257, 449)], 192, 128, (2, 2), F16, False, None),         # a sequence without rows, the ring wrapping, steady state
     ([(72, 200), (40, 0), (200, 72)], 136, 128, (4, 2), BF16, True, 0.07),           # a sequence without keys in the middle, more rows than keys
     ([(130, 450), (64, 64)], 192, 128, (2, 2), F16, True, None),                     # bottom-right shift that is no multiple of 32
+    ([(33, 63), (33, 64), (33, 65)], 192, 128, (2, 2), BF16, True, None),            # the last key on either side of the first tile boundary ...
+    ([(33, 127), (33, 128), (33, 129)], 192, 128, (4, 2), F16, True, None),          # ... and of the second
+    ([(127, 192), (128, 192)], 192, 128, (2, 2), F16, True, None),                   # the last row on either side of the first block boundary ...
+    ([(255, 192), (256, 192)], 160, 72, (4, 2), BF16, False, None),                  # ... and of the second
+    ([(129, 65)], 192, 128, (8, 1), F16, True, None),                                # GQA groups of 8 and 4 at the smallest shape with two query blocks
+    ([(129, 65), (130, 64)], 192, 128, (8, 2), BF16, True, None),
 ]
 IDS = ["-".join(f"{a}x{b}" for a, b in c[0]) for c in CASES]
 
