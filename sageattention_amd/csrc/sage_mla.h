@@ -5,6 +5,8 @@
 #include "sage_common.h"
 #include "sage_quant_math.h"
 
+#include <atomic>
+
 namespace sage {
 
 constexpr int MLA_DQK = 576;                           // channels of a latent row: 512 compressed + 64 rope
@@ -72,5 +74,12 @@ __device__ __forceinline__ int mla_kv_len(const int32_t *kv_lens, int b, int Lk)
 
 hipError_t launch_mla_attn(const MlaAttnParams &p, int dtype, hipStream_t stream);
 hipError_t launch_mla_prepass(const MlaPrepParams &p, int dtype, hipStream_t stream);
+
+// host side of sage_mla_attn (sage_mla_attn.hip), shared with sage_mlasplit_attn (sage_mla_split.hip): the argument checks in front of the LDS
+// check with the parameter block they allow, and the once-per-device opt-in to more than 64 KiB of dynamic LDS for `count` kernels
+int mla_attn_prepare(const char *e, const void *q, const void *k_image, const void *v_image, const float *k_scale, const float *v_scale,
+                     const int32_t *kv_lens, void *o, float *lse, int B, int Lq, int Hq, int Lk, int width_qk, int width_v, int64_t q_sb,
+                     int64_t q_sl, int64_t q_sh, float sm_scale, int dtype, MlaAttnParams &p);
+int mla_raise_lds(const char *e, std::atomic<unsigned long long> &done, int bytes, const void *const *kernels, const int *kernel_bytes, int count);
 
 }  // namespace sage

@@ -14,7 +14,7 @@ from typing import Optional, Union
 
 import torch
 
-from . import _cabi, _cabi_mla
+from . import _cabi, _cabi_mla, _cabi_mlasplit
 from .core import _finish
 from .quant import _aligned, _p, _stream
 
@@ -92,16 +92,51 @@ def mla_quantize_latent(kv: torch.Tensor, kv_lens: Optional[torch.Tensor] = None
     return MlaLatent(k_img, v_img, k_scale, v_scale, k_mean, kv_lens, bool(smooth_k), Lk)
 
 
+# The "auto" plan's constants, read off profiles/mla_split_probe.json (tools/mla_split_probe.py; bf16, Hq 128, Lq 1 / 2, B 1 .. 128, Lk 4096 ..
+# 32768): with W = B * ceil(rows / 128) work items the fastest S measured is the power of two that brings S * W to about one workgroup per CU
+# (W 1 .. 8 -> 32, 16 -> 16, 32 -> 8, 64 -> 4, 128 -> 2; x0.08 .. x0.88 of the unsplit launch, spreads <= 0.03), and at W = 256 every S is slower
+# than the unsplit launch.  Nothing below Lk 4096 was measured.
+_AUTO_MIN_LK, _AUTO_WORKGROUPS, _AUTO_MAX_SPLITS, _AUTO_MAX_ITEMS = 4096, 256, 32, 128
+
+
+def _auto_num_splits(B: int, rows: int, Lk: int) -> int:
+    """The ``num_splits="auto"`` plan, from shapes only: the number of chunks for ``B * ceil(rows / 128)`` work items against ``Lk`` keys, or 1
+    for the unsplit launch -- which it is wherever the probe did not show the split faster by more than both spreads."""
+    items = B * ((rows + 127) // 128)
+    if Lk < _AUTO_MIN_LK or items > _AUTO_MAX_ITEMS:
+        return 1
+    S = min(_AUTO_MAX_SPLITS, _AUTO_WORKGROUPS // items)
+    return 1 << (S.bit_length() - 1)
+
+
+def _resolve_num_splits(num_splits, name: str) -> int:
+    """``num_splits`` as an int: 1 the unsplit launch, 2 .. 255 that many chunks, 0 the plan from the shapes."""
+    if num_splits is None:
+        return 1
+    if torch.compiler.is_compiling():
+        raise ValueError(f"{name}: num_splits is not supported under torch.compile: call it from eager code (torch.compiler.disable)")
+    if isinstance(num_splits, str) and num_splits == "auto":
+        return 0
+    if isinstance(num_splits, int) and not isinstance(num_splits, bool) and 0 <= num_splits <= 255:
+        return num_splits
+    raise ValueError(f"{name}: num_splits must be None or 1 (one workgroup per sample and 128-row block), an int from 2 to 255 (that many "
+                     f"key-range chunks, exactly the unsplit arithmetic) or 'auto' / 0 (got {num_splits!r})")
+
+
 def sageattn_mla_decode(q: torch.Tensor, kv: Union[torch.Tensor, MlaLatent], kv_lens: Optional[torch.Tensor] = None,
-                        sm_scale: Optional[float] = None, smooth_k: bool = True, return_lse: bool = False):
+                        sm_scale: Optional[float] = None, smooth_k: bool = True, return_lse: bool = False, num_splits=None):
     """INT8 QK^T + FP8 (e4m3) PV attention of ``q [B, Lq, Hq, 576]`` (last dim contiguous, any strides in front) against the latent cache
     ``kv [B, Lk, 576]`` with V = ``kv[..., :512]``: ``o [B, Lq, Hq, 512]`` in the dtype of ``q``, with ``return_lse`` also the natural-log LSE
     ``[B, Hq, Lq]`` in fp32.  The mask is the decode one: query position i of sample b sees key j iff ``j <= kv_lens[b] - Lq + i``
     (``kv_lens`` int32 ``[B]`` on the device, default ``Lk``); a position in front of key 0 gives ``o = +0``, ``lse = -inf``.  ``Lq = 1`` is the
     plain decode step, ``Lq = 2 .. 8`` multi-token prediction.  ``sm_scale`` defaults to ``576 ** -0.5``.  ``kv`` may be the result of
     :func:`mla_quantize_latent`, which skips the pre-pass (``kv_lens`` and ``smooth_k`` are then the quantised state's); the two ways are bit
-    for bit the same.  Nothing synchronises with the host.  Everything else raises ``ValueError`` and names the entry to call."""
+    for bit the same.  ``num_splits=S`` (2 .. 255) runs every work item as S key-range chunks on S times as many workgroups, exactly: every
+    e4m3 P is the unsplit call's, only the FP32 summation order of O and l differs; it is for small batches against long
+    latents, where the unsplit launch fills a fraction of the chip.  ``None`` / 1 is the unsplit launch, ``"auto"`` / 0 a plan from the
+    shapes.  Nothing synchronises with the host.  Everything else raises ``ValueError`` and names the entry to call."""
     name = "sageattn_mla_decode"
+    S = _resolve_num_splits(num_splits, name)
     if isinstance(kv, MlaLatent):
         if torch.compiler.is_compiling():
             raise ValueError(f"{name} is not supported under torch.compile: call it from eager code (torch.compiler.disable)")
@@ -135,9 +170,19 @@ def sageattn_mla_decode(q: torch.Tensor, kv: Union[torch.Tensor, MlaLatent], kv_
     o = torch.empty((B, Lq, Hq, WIDTH_V), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, Lq), dtype=torch.float32, device=q.device) if return_lse else None
     code = _cabi.DTYPE_F16 if q.dtype == torch.float16 else _cabi.DTYPE_BF16
-    rc = lib.sage_mla_attn(_p(q), _p(lat.k_img), _p(lat.v_img), _p(lat.k_scale), _p(lat.v_scale), _p(lat.kv_lens), _p(o), _p(lse), B, Lq, Hq,
-                           lat.Lk, WIDTH_QK, WIDTH_V, q.stride(0), q.stride(1), q.stride(2), float(sm_scale), code, _stream(q))
-    _cabi.check(rc, "sage_mla_attn")
+    args = (_p(q), _p(lat.k_img), _p(lat.v_img), _p(lat.k_scale), _p(lat.v_scale), _p(lat.kv_lens), _p(o), _p(lse), B, Lq, Hq, lat.Lk, WIDTH_QK,
+            WIDTH_V, q.stride(0), q.stride(1), q.stride(2), float(sm_scale), code, _stream(q))
+    if S == 0:
+        S = _auto_num_splits(B, Lq * Hq, lat.Lk)
+    if S == 1:
+        _cabi.check(lib.sage_mla_attn(*args), "sage_mla_attn")
+    else:
+        split = _cabi_mlasplit.load()
+        ws_bytes = split.sage_mlasplit_ws_bytes(B, Lq, Hq, S)
+        if ws_bytes < 0:
+            _cabi.check(-1, "sage_mlasplit_ws_bytes")
+        ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=q.device)      # chunk_max, lse_part, o_part: sized from the shapes alone
+        _cabi.check(split.sage_mlasplit_attn(*args, S, _p(ws), ws_bytes), "sage_mlasplit_attn")
     lse_correction = None
     if return_lse and lat.smooth_k:
         # q . mean per row in FP32 over the 576 channels (the product's rounding to bf16 would cost the LSE close to 1e-2), [B, Hq, Lq]
